@@ -10,9 +10,15 @@ train.py:157-303, minus its loss heads).  For --gpus N > 1 every rank renders a 
 Gaussian-gradient buffer.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full      # + every secondary figure (see below)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, the sizing pass, pre-roll and
+warm-up, the timed steps, and the line (metric, value, unit, higher_is_better, dtype, ms_per_step, config, step_ms).
+--full adds what takes runs of its own: the HIP-event profile of the compositing kernels inside the timed window, the
+per-kernel pass, the roofline, the two-view / fp32-variant / two-stream windows, whole training iterations and the CPU
+baselines.  --dump-outputs DIR writes what the last timed step returned (maps, radii, gradients) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -125,6 +131,39 @@ def cpu_baseline(scene_cpu, cam, feat, tile_step, budget_s):
     return dt, o.num_rendered, o.pairs_done
 
 
+DUMP_MAX_ELEMS = 1 << 20       # per array: larger outputs are written as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(path, out, params):
+    """What the last timed step handed its caller -- render()'s maps, radii and visibility, and the gradients autograd left in
+    the parameters and the screen-space points -- as float32 `path/<name>.npy`.  An array of more than DUMP_MAX_ELEMS elements
+    is written as the elements at DUMP_MAX_ELEMS sorted indices drawn from a generator seeded by the array's size alone, so two
+    builds run with the same arguments write the same positions (13 arrays x 4 MiB at most)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    vsp = out.get("viewspace_points")
+    arrays = [(k, out.get(k)) for k in ("render", "render_gaussian_features", "depth", "radii", "visibility_filter")]
+    arrays += [("grad_" + n, p.grad) for n, p in zip(("xyz", "features_dc", "features_rest", "scaling", "rotation", "opacity",
+                                                      "gaussian_features"), params)]
+    arrays.append(("grad_viewspace_points", None if vsp is None else vsp.grad))
+    written = 0
+    for name, t in arrays:
+        if t is None:
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(flat.numel())
+            idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        a = flat.float().cpu().numpy()
+        if flat.numel() == t.numel():
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(path, name + ".npy"), a)
+        written += a.nbytes
+    assert written <= 64 * 10 ** 6, f"--dump-outputs wrote {written} bytes"
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -166,7 +205,14 @@ def main():
     ap.add_argument("--cpu-budget-s", type=float, default=16.0, help="wall-time budget of the CPU preprocess baseline")
     ap.add_argument("--cpu-oracle-budget-s", type=float, default=1.0, help="forward wall-time budget of the oracle sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every host core (os.cpu_count())")
-    ap.add_argument("--kernel-breakdown", action="store_true", help="(kept for old command lines: the per-kernel pass always runs)")
+    ap.add_argument("--kernel-breakdown", action="store_true", help="(kept for old command lines: the per-kernel pass runs with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: HIP events around the compositing kernels inside the timed "
+                         "window, the per-kernel pass and the roofline, batched_2_views, fp32_variant, views_in_flight_2, "
+                         "iteration_ms and the CPU baselines (off by default: a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps write what the last one returned (maps, radii, gradients) as DIR/<name>.npy, "
+                         "float32; arrays above 1 Mi elements as a fixed seeded sample")
     ap.add_argument("--policy", choices=["free", "sync"], default="free",
                     help="capacity policy of the timed steps: free = set_sync(False) with a measured capacity (default, what the "
                          "metric is quoted on); sync = the drop-in default (pair count read back every forward, exact allocation)")
@@ -201,18 +247,22 @@ def main():
     assert torch.cuda.is_available(), "bench.py needs a GPU"
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if world != args.gpus:
         if "RANK" in os.environ or "LOCAL_RANK" in os.environ:
             sys.exit(f"bench.py: --gpus {args.gpus} but launched with WORLD_SIZE={world}; pass --nproc-per-node {args.gpus}")
         if torch.cuda.device_count() < args.gpus:
             sys.exit(f"bench.py: --gpus {args.gpus} requested but only {torch.cuda.device_count()} GPU(s) are visible")
-        # plain `python bench.py --gpus N`: spawn the N ranks ourselves, exactly like the driver's launch line
+        # plain `python bench.py --gpus N`: spawn the N ranks ourselves, exactly like the driver's launch line -- as a child
+        # process (this one has already opened the GPU runtime above, so it is not replaced)
         import socket
+        import subprocess
         with socket.socket() as so:
             so.bind(("127.0.0.1", 0))
             port = so.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
     # TEST MODE (tests/test_gpu_bench_ranks.py): several ranks share the visible GPU(s) and talk over gloo -- every N > 1 code
     # path of this file (bucket, exchange schedules, barrier, MAX over ranks, rank 0's line) runs on a one-GPU box; the line it
     # prints says so and is not a measurement
@@ -293,9 +343,11 @@ def main():
     tiles_mode = args.shard == "tiles"
     strip = {"part": None}          # tile-row partition of the current job (tiles mode)
 
-    def step(i):
+    last = {}                   # --dump-outputs: what the last timed step returned (kept for that step only)
+
+    def step(i, keep=False):
         if tiles_mode:
-            return step_tiles(i)
+            return step_tiles(i, keep=keep)
         if bucket is not None and not use_sink:
             bucket.zero()                 # autograd accumulates into the bucket views
         else:
@@ -318,6 +370,9 @@ def main():
             img, radii, feats, depth = GaussianRasterizer(raster_settings=st)(
                 means3D=pc.get_xyz, means2D=means2D, shs=pc.get_features, sh_objs=sh_objs, colors_precomp=None,
                 opacities=pc.get_opacity, scales=pc.get_scaling, rotations=pc.get_rotation, cov3D_precomp=None)
+            out = {"render": img, "viewspace_points": means2D, "radii": radii, "render_gaussian_features": feats, "depth": depth}
+        if keep:
+            last["out"] = out
         torch.autograd.backward([img, feats], [g_img, g_feat])
         if bucket is not None and phased:
             ex = bucket.allreduce_phased(first=[pc._xyz], sh_rest=(pc._features_rest, args.active_sh_degree))
@@ -327,7 +382,7 @@ def main():
             bucket.allreduce()
         return radii
 
-    def step_tiles(i, rows=None):
+    def step_tiles(i, rows=None, keep=False):
         """One rank's share of ONE view: its strip of tile rows (forward), all-gather of the RGB strips (the full frame a
         style loss needs), backward of the strip, all-reduce of the partial gradients."""
         from trase_amd import dp
@@ -337,14 +392,19 @@ def main():
         if args.forward_only:          # rendering one frame (inference / GUI / evaluation): no backward, no gradient exchange
             with torch.no_grad(), (R.tile_rows(b, e) if (b, e) != (0, 0) else _nullctx()):
                 out = render(cams_dev[i % n_views], pc, pipe, bg, 0.0, 0.0, 0.0)
+                full_ = out["render"]
                 if world > 1 and (b, e) != (0, 0):       # (the whole-view sizing pass has nothing to gather)
-                    dp.allgather_strips(out["render"], strip["part"], H)
+                    full_ = dp.allgather_strips(out["render"], strip["part"], H)
+            if keep:
+                last["out"] = dict(out, render=full_)
             return out["radii"]
         with R.tile_rows(b, e) if (b, e) != (0, 0) else _nullctx():
             out = render(cams_dev[i % n_views], pc, pipe, bg, 0.0, 0.0, 0.0)
             img, radii, feats = out["render"], out["radii"], out["render_gaussian_features"]
             if world > 1 and (b, e) != (0, 0):
                 img = dp.allgather_strips(img, strip["part"], H)
+            if keep:
+                last["out"] = dict(out, render=img)
             torch.autograd.backward([img, feats], [g_img, g_feat])
         if bucket is not None:
             bucket.allreduce()
@@ -461,8 +521,8 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except Exception:
             pass
-    if not args.graph:           # (a replayed launch graph has no per-kernel events: --graph takes the kernel times of the untimed pass below)
-        R.profile_enable(2)      # HIP events around the compositing kernels only, on the launch stream
+    if args.full and not args.graph:   # (a replayed launch graph has no per-kernel events: --graph takes the kernel times of the untimed pass below)
+        R.profile_enable(2)      # HIP events around the compositing kernels only, on the launch stream (the roofline's live kernel times)
     import gc
     gc.disable()                 # no collector pause inside the 20-step window (NOT gc.collect(): tens of ms of idle GPU in front
                                  # of the timed steps cost 7-9 %, see above)
@@ -472,8 +532,9 @@ def main():
     step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     step_ev[0].record()
     t0 = time.perf_counter()
+    keep_last = bool(args.dump_outputs)
     for i in range(args.steps):
-        step(i)
+        step(i, keep=keep_last and i == args.steps - 1)
         step_ev[i + 1].record()
         host_t.append(time.perf_counter())
     if phase["ex"] is not None:
@@ -486,7 +547,7 @@ def main():
     gc.enable()
     host_gaps = [round((b - a) * 1e3, 3) for a, b in zip([t0] + host_t[:-1], host_t)]
     log(f"host ms per step() call: {host_gaps}; drain {(t1 - host_t[-1]) * 1e3:.3f} ms")
-    prof = R.profile_report() if not args.graph else {}
+    prof = R.profile_report() if (args.full and not args.graph) else {}
     R.profile_enable(0)
     exchange_ms = bucket.exchange_ms() if bucket is not None else None      # the last timed step's collective(s)
     status = R.last_status()
@@ -504,29 +565,34 @@ def main():
                "slowest_step": dev_raw.index(dev_steps[-1]),
                "what": "device time between the events recorded behind consecutive timed steps (this rank); ms_per_step is the host clock over all of them"}
     log(f"timed: {ms_per_step:.3f} ms/step, {views_per_s:.1f} views/s")
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, last.pop("out"), params)
+        log(f"outputs of the last timed step (view {(args.steps - 1) % n_views}): {nbytes / 1e6:.1f} MB in {args.dump_outputs}")
+    last.clear()
 
     breakdown, launches = None, None
-    # the per-kernel table is part of the line: roofline.forward, backward_frac and launches_per_view are built from it
-    R.profile_enable(1)
-    nb = min(4, n_views)
-    for i in range(nb):
-        step(i)
-    torch.cuda.synchronize()
-    rep_ = R.profile_report()
-    breakdown = {k: round(v["ms"] * v["n"] / nb, 4) for k, v in rep_.items()}
-    # kernel launches per view of the library's own launch sequences (one profiling scope = one launch, except scan_tiles
-    # = 2); memsets and the torch-side kernels of the wrapper are not counted
-    per_scope = {k: (2 if k == "scan_tiles" else 1) * v["n"] / nb for k, v in rep_.items()}
-    chain = ("radix_hist", "radix_scan", "radix_scatter", "depth_sort", "emit_pairs", "scan_tiles", "tile_ranges")
-    launches = {"binning_chain": round(sum(v for k, v in per_scope.items() if k in chain), 2),
-                "all_kernels": round(sum(per_scope.values()), 2)}
-    R.profile_enable(0)
+    # --full: the per-kernel table (roofline.forward, backward_frac and launches_per_view are built from it)
+    if args.full:
+        R.profile_enable(1)
+        nb = min(4, n_views)
+        for i in range(nb):
+            step(i)
+        torch.cuda.synchronize()
+        rep_ = R.profile_report()
+        breakdown = {k: round(v["ms"] * v["n"] / nb, 4) for k, v in rep_.items()}
+        # kernel launches per view of the library's own launch sequences (one profiling scope = one launch, except scan_tiles
+        # = 2); memsets and the torch-side kernels of the wrapper are not counted
+        per_scope = {k: (2 if k == "scan_tiles" else 1) * v["n"] / nb for k, v in rep_.items()}
+        chain = ("radix_hist", "radix_scan", "radix_scatter", "depth_sort", "emit_pairs", "scan_tiles", "tile_ranges")
+        launches = {"binning_chain": round(sum(v for k, v in per_scope.items() if k in chain), 2),
+                    "all_kernels": round(sum(per_scope.values()), 2)}
+        R.profile_enable(0)
 
     # ---- extra key: two views per launch sequence (trase_amd.renderer.render_views: ONE depth sort for both views) ---------------
     # not the headline (the reference renders one view per iteration, train.py:180): what a loop that accumulates two views per
     # optimizer step, or an evaluation sweep, gets; same views, same cotangents, forward + backward of both
     batched = None
-    if world == 1 and not tiles_mode and not args.unfused and args.policy == "free" and bucket is None and not args.forward_only:
+    if args.full and world == 1 and not tiles_mode and not args.unfused and args.policy == "free" and bucket is None and not args.forward_only:
         try:
             from trase_amd.renderer import render_views
 
@@ -568,7 +634,7 @@ def main():
     # the same steps with the packed-FP32 compositing kernels (TRASE_VARIANT_VALU_FORWARD | _BACKWARD: every product in fp32), same
     # run, right after the headline; and how far the two forwards' maps are apart on view 0
     fp32_variant = None
-    if world == 1 and not tiles_mode and not args.unfused and F == 32 and not args.forward_only and bucket is None:
+    if args.full and world == 1 and not tiles_mode and not args.unfused and F == 32 and not args.forward_only and bucket is None:
         try:
             v0 = R._Policy.variant
             with torch.no_grad():
@@ -615,7 +681,7 @@ def main():
     # same views go round-robin to two streams (the wrapper's cross-stream ordering off), gradients through torch.autograd.grad,
     # and every view's maps + gradients are checked bit for bit against the serial run IN THIS RUN before the rate is reported
     in_flight = None
-    if world == 1 and not tiles_mode and not args.unfused and args.policy == "free" and bucket is None and not args.forward_only:
+    if args.full and world == 1 and not tiles_mode and not args.unfused and args.policy == "free" and bucket is None and not args.forward_only:
         try:
             def view_ad(i, digest):
                 o_ = render(cams_dev[i % n_views], pc, pipe, bg, 0.0, 0.0, 0.0)
@@ -671,7 +737,7 @@ def main():
 
     # ---- secondary window: whole training iterations, iter_start -> iter_end of train.py:157-303 -------
     iteration_ms = None
-    if world == 1 and not tiles_mode and not args.no_iteration_window and not args.unfused and (N, W, H, F) == (300_000, 1920, 1080, 32):
+    if args.full and world == 1 and not tiles_mode and not args.no_iteration_window and not args.unfused and (N, W, H, F) == (300_000, 1920, 1080, 32):
         try:
             from trase_amd.bench_iterations import make_feature_iteration, make_gaussian_iteration, time_iterations
             log("secondary window: 16 GAUSSIAN-state + 16 FEATURE-state iterations ...")
@@ -711,37 +777,6 @@ def main():
             iteration_ms = {"error": f"{type(e).__name__}: {e}"}
 
     if rank == 0:
-        r_used = sum(r_list[i % n_views] for i in range(args.steps)) / args.steps
-        dom = max(prof.items(), key=lambda kv: kv[1]["ms"] * kv[1]["n"])[0] if prof else "render_bwd"
-        dom_ms = prof[dom]["ms"] if prof else (breakdown or {}).get(dom, float("nan"))
-        a_bytes = algorithmic_bytes(dom, N, r_used, P, F)
-        achieved = a_bytes / (dom_ms * 1e-3) / 1e9
-        # per-launch PMC figures of the same command (profiles/run_pmc.sh -> profiles/pmc_per_launch.json):
-        # HBM bytes = (2*FETCH_SIZE + WRITE_SIZE) KiB per the gfx950 note of MI355X_MICROARCH.md; VALU wave-instructions
-        # These are REPLAYED from a tracked table, not counters of this run; `counters_source` says so, and they are only
-        # reported when the table was collected on the kernel sources this library is built from.
-        traffic = valu_insts = mfma_insts = None
-        counters_source = None
-        fwd_rec = {}
-        tpath = os.path.join(ROOT, "profiles", "pmc_per_launch.json")
-        if os.path.exists(tpath) and (N, W, H, F) == (300_000, 1920, 1080, 32) and not args.unfused:   # collected on S4 only
-            try:
-                table = json.load(open(tpath))
-                rec = table.get(dom) or {}
-                sha_tab, sha_now = table.get("_source_sha16"), source_sha16()
-                if sha_tab == sha_now:
-                    traffic, valu_insts, mfma_insts = rec.get("hbm_bytes"), rec.get("valu_insts"), rec.get("mfma_insts")
-                    fwd_rec = table.get("render_fwd") or {}
-                    counters_source = (f"replayed from profiles/pmc_per_launch.json ({table.get('_from', '?')}; rocprofv3 PMC passes of "
-                                       f"this command on kernel sources {sha_tab}) -- not counters of this run")
-                else:
-                    counters_source = (f"none: profiles/pmc_per_launch.json was collected on kernel sources {sha_tab}, this build is "
-                                       f"{sha_now}; traffic / valu_frac withheld")
-            except Exception:
-                pass
-        # VALU fraction ("report HBM fraction AND VALU fraction"): a wave64 VALU instruction occupies its SIMD
-        # for 4 cycles; 256 CUs x 4 SIMDs at the 2.4 GHz peak clock
-        valu_frac = None if valu_insts is None else valu_insts * 4.0 / (N_SIMD * dom_ms * 1e-3 * CLOCK_HZ)
         out = {
             # BASELINE.json's metric names the S4 configuration; other sizes (parity-test configurations) say so
             "metric": ("TEST MODE (ranks share a GPU over gloo: not a measurement) " if shared_gpu_test else "") + ("views/sec (fwd+bwd), 1080p, 300k Gaussians, 32-d feat" if (N, W, H, F) == (300_000, 1920, 1080, 32)
@@ -771,50 +806,85 @@ def main():
                                     + ("zero + accumulate" if not use_sink else
                                        (f"sink, all-reduce in {args.exchange_chunks} Gaussian ranges overlapped with the backward tail"
                                         if args.exchange_chunks > 1 else "sink, one all-reduce after the backward")))},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                         "counters_source": counters_source,
-                         "valu_frac": None if valu_frac is None else round(valu_frac, 4), "valu_insts": valu_insts,
-                         "mfma_insts": mfma_insts,
-                         "kernel_ms": round(dom_ms, 4), "algorithmic_bytes": int(a_bytes),
-                         "view_frac": round(view_bytes(N, r_used, P, F) * views_per_s / (1 if tiles_mode else world) / 1e9 / HBM_PEAK_GBS, 5)},
-            "kernels_ms_per_view": breakdown,
-            "launches_per_view": launches,
-            "iteration_ms": iteration_ms,
             "step_ms": step_ms,
-            "fp32_variant": fp32_variant,
-            "views_in_flight_2": in_flight,
-            "batched_2_views_per_s": (None if batched is None else batched.get("views_per_s")),
-            "batched_2_views": batched,
+            "full": bool(args.full),
         }
-        # the forward compositing kernel beside the dominant one, and the VALU-issue fraction of the two together: both kernels
-        # sit at ~0.65-0.70 of the VALU issue rate at their register-limited residency, i.e. the roofline that binds them is NOT
-        # the HBM one `frac` is quoted on (SURVEY 8d predicted the VALU ceiling) -- VERDICT r4 item 7
-        fwd_ms = (prof.get("render_fwd") or {}).get("ms") if prof else None
-        if fwd_ms is None:
-            fwd_ms = (breakdown or {}).get("render_fwd")
-        if fwd_ms:
-            f_bytes = algorithmic_bytes("render_fwd", N, r_used, P, F)
-            f_valu = fwd_rec.get("valu_insts")
-            out["roofline"]["forward"] = {
-                "kernel": "render_fwd", "kernel_ms": round(fwd_ms, 4), "algorithmic_bytes": int(f_bytes),
-                "achieved": round(f_bytes / (fwd_ms * 1e-3) / 1e9, 2), "frac": round(f_bytes / (fwd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                "traffic": fwd_rec.get("hbm_bytes"), "valu_insts": f_valu, "mfma_insts": fwd_rec.get("mfma_insts"),
-                "valu_frac": None if f_valu is None else round(f_valu * 4.0 / (N_SIMD * fwd_ms * 1e-3 * CLOCK_HZ), 4)}
-            if f_valu is not None and valu_insts is not None and dom == "render_bwd":
-                out["roofline"]["compositing_valu_frac"] = round((f_valu + valu_insts) * 4.0 / (N_SIMD * (fwd_ms + dom_ms) * 1e-3 * CLOCK_HZ), 4)
-            out["roofline"]["bound_note"] = (
-                "frac / forward.frac are HBM fractions of SURVEY 8(d)'s algorithmic bytes; both compositing kernels are VALU-issue-bound "
-                "at those fractions (valu_frac, forward.valu_frac, compositing_valu_frac = VALU wave-instructions x 4 cycles / "
-                f"({N_SIMD} SIMDs x kernel time x {CLOCK_HZ / 1e9:.1f} GHz), registers limiting residency): the binding roofline is the "
-                "vector ALU issue rate, not HBM bandwidth")
-        if breakdown and breakdown.get("render_bwd") and breakdown.get("reduce_rows") and dom == "render_bwd":
-            # SURVEY 8(d) charges the per-Gaussian gradient write to the backward compositing; in this design reduce_rows does
-            # that write (and re-reads the per-pair rows): backward compositing as 8(d) defines it = render_bwd + reduce_rows
-            both_ms = breakdown["render_bwd"] + breakdown["reduce_rows"]
-            out["roofline"]["backward_frac"] = round(a_bytes / (both_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-            out["roofline"]["backward_ms"] = round(both_ms, 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            r_used = sum(r_list[i % n_views] for i in range(args.steps)) / args.steps
+            dom = max(prof.items(), key=lambda kv: kv[1]["ms"] * kv[1]["n"])[0] if prof else "render_bwd"
+            dom_ms = prof[dom]["ms"] if prof else (breakdown or {}).get(dom, float("nan"))
+            a_bytes = algorithmic_bytes(dom, N, r_used, P, F)
+            achieved = a_bytes / (dom_ms * 1e-3) / 1e9
+            # per-launch PMC figures of the same command (profiles/run_pmc.sh -> profiles/pmc_per_launch.json):
+            # HBM bytes = (2*FETCH_SIZE + WRITE_SIZE) KiB per the gfx950 note of MI355X_MICROARCH.md; VALU wave-instructions
+            # These are REPLAYED from a tracked table, not counters of this run; `counters_source` says so, and they are only
+            # reported when the table was collected on the kernel sources this library is built from.
+            traffic = valu_insts = mfma_insts = None
+            counters_source = None
+            fwd_rec = {}
+            tpath = os.path.join(ROOT, "profiles", "pmc_per_launch.json")
+            if os.path.exists(tpath) and (N, W, H, F) == (300_000, 1920, 1080, 32) and not args.unfused:   # collected on S4 only
+                try:
+                    table = json.load(open(tpath))
+                    rec = table.get(dom) or {}
+                    sha_tab, sha_now = table.get("_source_sha16"), source_sha16()
+                    if sha_tab == sha_now:
+                        traffic, valu_insts, mfma_insts = rec.get("hbm_bytes"), rec.get("valu_insts"), rec.get("mfma_insts")
+                        fwd_rec = table.get("render_fwd") or {}
+                        counters_source = (f"replayed from profiles/pmc_per_launch.json ({table.get('_from', '?')}; rocprofv3 PMC passes of "
+                                           f"this command on kernel sources {sha_tab}) -- not counters of this run")
+                    else:
+                        counters_source = (f"none: profiles/pmc_per_launch.json was collected on kernel sources {sha_tab}, this build is "
+                                           f"{sha_now}; traffic / valu_frac withheld")
+                except Exception:
+                    pass
+            # VALU fraction ("report HBM fraction AND VALU fraction"): a wave64 VALU instruction occupies its SIMD
+            # for 4 cycles; 256 CUs x 4 SIMDs at the 2.4 GHz peak clock
+            valu_frac = None if valu_insts is None else valu_insts * 4.0 / (N_SIMD * dom_ms * 1e-3 * CLOCK_HZ)
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                             "counters_source": counters_source,
+                             "valu_frac": None if valu_frac is None else round(valu_frac, 4), "valu_insts": valu_insts,
+                             "mfma_insts": mfma_insts,
+                             "kernel_ms": round(dom_ms, 4), "algorithmic_bytes": int(a_bytes),
+                             "view_frac": round(view_bytes(N, r_used, P, F) * views_per_s / (1 if tiles_mode else world) / 1e9 / HBM_PEAK_GBS, 5)},
+                "kernels_ms_per_view": breakdown,
+                "launches_per_view": launches,
+                "iteration_ms": iteration_ms,
+                "fp32_variant": fp32_variant,
+                "views_in_flight_2": in_flight,
+                "batched_2_views_per_s": (None if batched is None else batched.get("views_per_s")),
+                "batched_2_views": batched,
+            })
+            # the forward compositing kernel beside the dominant one, and the VALU-issue fraction of the two together: both kernels
+            # sit at ~0.65-0.70 of the VALU issue rate at their register-limited residency, i.e. the roofline that binds them is NOT
+            # the HBM one `frac` is quoted on (SURVEY 8d predicted the VALU ceiling) -- VERDICT r4 item 7
+            fwd_ms = (prof.get("render_fwd") or {}).get("ms") if prof else None
+            if fwd_ms is None:
+                fwd_ms = (breakdown or {}).get("render_fwd")
+            if fwd_ms:
+                f_bytes = algorithmic_bytes("render_fwd", N, r_used, P, F)
+                f_valu = fwd_rec.get("valu_insts")
+                out["roofline"]["forward"] = {
+                    "kernel": "render_fwd", "kernel_ms": round(fwd_ms, 4), "algorithmic_bytes": int(f_bytes),
+                    "achieved": round(f_bytes / (fwd_ms * 1e-3) / 1e9, 2), "frac": round(f_bytes / (fwd_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                    "traffic": fwd_rec.get("hbm_bytes"), "valu_insts": f_valu, "mfma_insts": fwd_rec.get("mfma_insts"),
+                    "valu_frac": None if f_valu is None else round(f_valu * 4.0 / (N_SIMD * fwd_ms * 1e-3 * CLOCK_HZ), 4)}
+                if f_valu is not None and valu_insts is not None and dom == "render_bwd":
+                    out["roofline"]["compositing_valu_frac"] = round((f_valu + valu_insts) * 4.0 / (N_SIMD * (fwd_ms + dom_ms) * 1e-3 * CLOCK_HZ), 4)
+                out["roofline"]["bound_note"] = (
+                    "frac / forward.frac are HBM fractions of SURVEY 8(d)'s algorithmic bytes; both compositing kernels are VALU-issue-bound "
+                    "at those fractions (valu_frac, forward.valu_frac, compositing_valu_frac = VALU wave-instructions x 4 cycles / "
+                    f"({N_SIMD} SIMDs x kernel time x {CLOCK_HZ / 1e9:.1f} GHz), registers limiting residency): the binding roofline is the "
+                    "vector ALU issue rate, not HBM bandwidth")
+            if breakdown and breakdown.get("render_bwd") and breakdown.get("reduce_rows") and dom == "render_bwd":
+                # SURVEY 8(d) charges the per-Gaussian gradient write to the backward compositing; in this design reduce_rows does
+                # that write (and re-reads the per-pair rows): backward compositing as 8(d) defines it = render_bwd + reduce_rows
+                both_ms = breakdown["render_bwd"] + breakdown["reduce_rows"]
+                out["roofline"]["backward_frac"] = round(a_bytes / (both_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                out["roofline"]["backward_ms"] = round(both_ms, 4)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             host = os.cpu_count() or 1
             # the reference's Python preprocess is a chain of small elementwise torch ops: with one thread per core of a
             # big host the intra-op thread pool costs more than it gives, so the leg is timed twice -- on every core (as

@@ -1,7 +1,8 @@
 #!/bin/bash
-# After `gpurun -- bash profiles/run_evidence.sh <tag>`: copy what is to be judged from gpurun_out/ into profiles/.
+# After `bash profiles/run_evidence.sh <tag>` (its output folder brought back here): copy what is to be judged from $OUT
+# (a folder at the repository root, default evidence_out/) into profiles/.  Usage: [OUT=dir] bash profiles/copy_evidence.sh <tag>
 T=${1:-r6}
-cd "$(dirname "$0")/../gpurun_out" || exit 1
+cd "$(dirname "$0")/.." && cd "${OUT:-evidence_out}" || exit 1
 cp trace_$T.md ../profiles/${T}_kernel_stats.md
 cp trace_${T}_bench.json ../profiles/${T}_bench_under_rocprof.json
 cp pmc_$T.md ../profiles/${T}_pmc.md

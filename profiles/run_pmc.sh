@@ -1,16 +1,17 @@
 #!/bin/bash
 # rocprofv3 PMC counters of the bench workload, one pass per counter group (gpurun refuses --pmc combined with
 # sys/hip traces; kernel-trace is fine; FETCH_SIZE and WRITE_SIZE do not fit one pass).
-# Usage on the GPU box:  bash profiles/run_pmc.sh <tag> [group ...]      groups: sq sq2 vmem tcp tcc ta fetch write
-# Writes gpurun_out/pmc_<tag>.md (per-kernel averages per launch) and gpurun_out/pmc_<tag>.json.
+# Usage on the GPU box:  [OUT=dir] bash profiles/run_pmc.sh <tag> [group ...]      groups: sq sq2 vmem tcp tcc ta fetch write
+# Writes $OUT/pmc_<tag>.md (per-kernel averages per launch) and $OUT/pmc_<tag>.json (default OUT: evidence_out/).
 set -u
 TAG=${1:-rX}; shift
 GROUPS_="${*:-sq sq2 fetch write}"
 R=$PWD
+O=$(realpath -m "${OUT:-evidence_out}")
 export TMPDIR=/tmp
-mkdir -p $R/gpurun_out/pmc_$TAG
+mkdir -p $O/pmc_$TAG
 cd /tmp
-CMD="${PMC_CMD:-python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-iteration-window}"     # PMC_CMD: another workload (e.g. profiles/bench_mlp.py)
+CMD="${PMC_CMD:-python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-iteration-window --full}"     # PMC_CMD: another workload (e.g. profiles/bench_mlp.py)
 declare -A G
 G[sq]="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_LDS"
 G[sq2]="SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_SCA SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS"
@@ -25,9 +26,9 @@ G[fetch]="FETCH_SIZE"
 G[write]="WRITE_SIZE"
 DBS=""
 for g in $GROUPS_; do
-  timeout ${PMC_TIMEOUT:-120} rocprofv3 --kernel-trace --pmc ${G[$g]} -d $R/gpurun_out/pmc_$TAG -o $g -- $CMD > /dev/null 2> $R/gpurun_out/pmc_$TAG/$g.err
-  [ -f $R/gpurun_out/pmc_$TAG/${g}_results.db ] && DBS="$DBS gpurun_out/pmc_$TAG/${g}_results.db" || tail -3 $R/gpurun_out/pmc_$TAG/$g.err
+  timeout ${PMC_TIMEOUT:-120} rocprofv3 --kernel-trace --pmc ${G[$g]} -d $O/pmc_$TAG -o $g -- $CMD > /dev/null 2> $O/pmc_$TAG/$g.err
+  [ -f $O/pmc_$TAG/${g}_results.db ] && DBS="$DBS ${O#$R/}/pmc_$TAG/${g}_results.db" || tail -3 $O/pmc_$TAG/$g.err
 done
 cd $R
-python profiles/summarize_pmc.py gpurun_out/pmc_${TAG}.md $DBS > /dev/null
-rm -rf gpurun_out/pmc_$TAG
+python profiles/summarize_pmc.py $O/pmc_${TAG}.md $DBS > /dev/null
+rm -rf $O/pmc_$TAG

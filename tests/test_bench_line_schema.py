@@ -1,5 +1,5 @@
 """The contract of bench.py's JSON line, checked on the line committed with the round's evidence (profiles/r6_bench_default.json --
-produced by `python bench.py` on an MI355X; this test needs no GPU): every key the driver and the judge read is there, the roofline
+produced by the full bench run on an MI355X, today `python bench.py --full`; this test needs no GPU): every key the driver and the judge read is there, the roofline
 object is self-consistent, the CPU baseline says what it timed."""
 import json
 import os
