@@ -384,6 +384,69 @@ def test_knn_points_matches_kdtree_self_and_cross():
     assert (out1.idx[0, :, 0].cpu().numpy() == i1).mean() > 0.999
 
 
+def _knn_clouds(rng, n):
+    """A volume cloud, a planar cloud (z = 0) and a collinear one (y = z = 0): the three cell-size branches of
+    knn_params_kernel (knn.hip), which sizes cells by the cloud's effective dimensionality.  The line's points are jittered
+    off a regular grid so that no two coincide in fp32 (uniform draws would: ~6000^2 / 2 pairs at 1e-7 spacing)."""
+    vol = rng.uniform(-1.3, 1.3, size=(n, 3))
+    plane = np.concatenate([rng.uniform(-1.0, 1.0, size=(n, 2)), np.zeros((n, 1))], 1)
+    xs = rng.permutation((np.arange(n) + rng.uniform(0.1, 0.9, size=n)) * (4.0 / n) - 2.0)
+    line = np.concatenate([xs[:, None], np.zeros((n, 2))], 1)
+    return {"volume": vol, "planar": plane, "collinear": line}
+
+
+def _knn_check(out, p1, p2, K, strict_order=True):
+    """Every batch against scipy's exact KD-tree in float64, with the bars and tie rule of the K = 1 / 16 test; besides, the
+    float64 distance of every RETURNED index must be the reference's distance at that rank (so a differently ordered pair
+    must really be a tie).  strict_order=False drops the 99.9 % index rule, for queries off a line, which have many
+    neighbours whose squared distances differ by less than the fp32 rounding of the kernel's."""
+    from scipy.spatial import cKDTree
+    for b in range(p1.shape[0]):
+        d, i = cKDTree(p2[b].astype(np.float64)).query(p1[b].astype(np.float64), k=K)
+        d, i = d.reshape(len(p1[b]), K), i.reshape(len(p1[b]), K)
+        idx = out.idx[b].cpu().numpy()
+        np.testing.assert_allclose(out.dists[b].cpu().numpy(), d ** 2, rtol=2e-4, atol=1e-9)
+        own = ((p1[b][:, None, :].astype(np.float64) - p2[b][idx].astype(np.float64)) ** 2).sum(-1)
+        np.testing.assert_allclose(own, d ** 2, rtol=2e-4, atol=1e-9)
+        assert (np.sort(idx, 1)[:, 1:] != np.sort(idx, 1)[:, :-1]).all()    # K distinct neighbours
+        if strict_order:
+            assert (idx == i).mean() > 0.999          # equidistant neighbours may be ordered differently
+
+
+@pytest.mark.parametrize("K", [2, 4, 5, 6, 8, 9, 15])
+def test_knn_points_every_k_batched_self_and_cross(K):
+    """knn_points at every top-K kernel instance (KT = 4, 8, 16 for 2 <= K <= 15; loss_cls_3d uses K = 6,
+    utils/loss_utils.py:144) against scipy's cKDTree: B = 2 (a different cloud per batch), self-KNN (each point first) and
+    cross-KNN with queries partly outside the bounding box, on volume, planar and collinear clouds."""
+    from pytorch3d.ops import knn_points
+    rng = np.random.default_rng(100 + K)
+    for kind in ("volume", "planar", "collinear"):
+        p = np.stack([_knn_clouds(rng, 6000)[kind] for _ in range(2)]).astype(np.float32)
+        q = (np.stack([_knn_clouds(rng, 1500)[kind] for _ in range(2)]) * 1.5
+             + rng.normal(size=(2, 1500, 3)) * 0.05).astype(np.float32)
+        tp, tq = torch.from_numpy(p).cuda(), torch.from_numpy(q).cuda()
+        out = knn_points(tp, tp, K=K)
+        assert out.idx.shape == (2, 6000, K) and out.idx.dtype == torch.int64, kind
+        _knn_check(out, p, p, K)
+        assert (out.idx[:, :, 0].cpu().numpy() == np.arange(6000)).all(), kind
+        _knn_check(knn_points(tq, tp, K=K), q, p, K, strict_order=kind == "volume")
+
+
+@pytest.mark.parametrize("n2,K", [(1, 2), (3, 4), (3, 6), (5, 9), (14, 15)])
+def test_knn_points_fewer_points_than_k_pads(n2, K):
+    """N2 < K: the N2 real neighbours in order, then the padding this module documents (pytorch3d's): idx 0, dist 0."""
+    from pytorch3d.ops import knn_points
+    rng = np.random.default_rng(n2 * 31 + K)
+    p = rng.uniform(-1.0, 1.0, size=(2, n2, 3)).astype(np.float32)
+    q = rng.uniform(-1.5, 1.5, size=(2, 200, 3)).astype(np.float32)
+    out = knn_points(torch.from_numpy(q).cuda(), torch.from_numpy(p).cuda(), K=K)
+    d2 = ((q[:, :, None, :].astype(np.float64) - p[:, None, :, :]) ** 2).sum(-1)        # (2, 200, n2), brute force
+    idx, dist = out.idx.cpu().numpy(), out.dists.cpu().numpy()
+    assert (idx[:, :, :n2] == np.argsort(d2, axis=-1, kind="stable")).mean() > 0.999
+    np.testing.assert_allclose(dist[:, :, :n2], np.sort(d2, axis=-1), rtol=2e-4, atol=1e-9)
+    assert (idx[:, :, n2:] == 0).all() and (dist[:, :, n2:] == 0).all()
+
+
 def test_feature_smoothing_path_with_knn_shim():
     """get_smoothed_gaussian_features (scene/gaussian_model.py:79-104) restated: KNN(16) indices from the
     shim, gather of L2-normalised features of a neighbour subset, mean -> (N,1,32); gradients flow."""

@@ -93,19 +93,32 @@ __device__ __forceinline__ int act_off(int m, int k) {   // element offset of (r
 // ---- helpers shared by the block-GEMM kernels ------------------------------------------------------------
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
+// sin / cos of v 2^f with the argument reduced to (-1/2, 1/2] revolutions first.  __sinf(a) is v_sin_f32(a / 2pi): the
+// rounding of that product costs 2^-24 |a| / 2pi revolutions, ~5e-5 at |a| = 2^9 and ~1e-3 rad at scene-sized |v| = 40 --
+// up to a quarter of a bf16 ulp of the encoding.  Here v / 2pi is carried as hi + lo (the product's rounding error exactly,
+// by fma), scaled by 2^f exactly, and the whole revolutions are removed exactly: ~3e-8 revolutions for any |v 2^f| < 2^24.
+// sin and cos of one (v, f) share the reduction (the compiler merges the identical expressions of the two columns).
+__device__ __forceinline__ float pe_rev(float v, int f) {
+  constexpr float INV2PI_HI = 0x1.45f306p-3f, INV2PI_LO = 0x1.b93910p-28f;   // 1 / 2pi = HI + LO + O(2^-53)
+  const float hi = v * INV2PI_HI;
+  const float lo = fmaf(v, INV2PI_HI, -hi) + v * INV2PI_LO;
+  const float s = (float)(1 << f), u = hi * s;
+  return (u - rintf(u)) + lo * s;
+}
+
 __device__ __forceinline__ float pe_const(int c, float x0, float x1, float x2, float t, const float* __restrict__ temb) {   // c is a compile-time constant
   if (c < 3) return c == 0 ? x0 : (c == 1 ? x1 : x2);
   if (c < 63) {
     const int q = c - 3, f = q / 6, r = q % 6, d = r % 3;
-    const float v = (d == 0 ? x0 : (d == 1 ? x1 : x2)) * (float)(1 << f);
-    return r < 3 ? __sinf(v) : __cosf(v);
+    const float u = pe_rev(d == 0 ? x0 : (d == 1 ? x1 : x2), f);
+    return r < 3 ? __builtin_amdgcn_sinf(u) : __builtin_amdgcn_cosf(u);
   }
   if (temb) return c < EMB_B ? temb[c - 63] : 0.f;       // wave-uniform pointer and address: scalar loads
   if (c == 63) return t;
   if (c < EMB_T) {
     const int q = c - 64, f = q >> 1;
-    const float v = t * (float)(1 << f);
-    return (q & 1) ? __cosf(v) : __sinf(v);
+    const float u = pe_rev(t, f);
+    return (q & 1) ? __builtin_amdgcn_cosf(u) : __builtin_amdgcn_sinf(u);
   }
   return 0.f;
 }
