@@ -578,6 +578,30 @@ int trase_featnorm_forward(const float* feats, int32_t F, int64_t HW, float* out
 int trase_featnorm_backward(const float* feats, int32_t F, int64_t HW, const float* out2, const float* g, float* dL_dfeats,
                             int32_t device, trase_stream_t stream);
 
+/* ---- segmentation after training: K-means and query masks (gui.py:248-270, render.py:97-105 + :334-345) ------------------
+ * trase_kmeans_steps: n_steps Lloyd steps of kmeans_pytorch.kmeans(X, K, distance='euclidean') (gui.py:248-270,
+ *   gui_standalone.py:685-707; 0.3's loop, see trase_amd/segment.py), entirely on the device.  X (N,D) fp32, centres_inout
+ *   (K,D) fp32 (the start centres in, the step's new centres out), ids_out (N) int32 = the assignment made against the centres
+ *   the step started from (argmin of the squared distance, ties to the lowest index).  An empty cluster k in iteration i
+ *   (counted from 0) takes row splitmix64(reseed_key ^ (i << 32 | k)) mod N.  state (int32[4], device, zeroed by the caller
+ *   before the first step) = {iterations, done, center_shift of the last step as float bits, 0}; a step sets done when
+ *   center_shift^2 < tol or iter_limit != 0 and iterations >= iter_limit, and every step of a state with done set does
+ *   nothing, so the host may enqueue steps in batches and read the state once per batch.  Per-cluster sums are reduced in a
+ *   fixed order without atomics: bitwise reproducible.  Limits: 1 <= K <= 128, 1 <= D <= 64, N >= K.
+ *   Workspace: trase_kmeans_sizes(N, D, K).
+ * trase_segment_mask: render.py:97-105 postprocessing OR-ed over the selected ids as the loop at render.py:334-345 does, for
+ *   fp32 features X (N,D) and int32 cluster ids (N): a point whose id is sel[s] (S <= 128 ids) is scored against
+ *   q = normalize(mean of the rows with id sel[s]) as fp16(fp16(x / |x|) . fp16(q)) with fp32 sums; mask_out (N bytes) = score
+ *   >= fp16(threshold).  Points with no selected id, negative ids, zero rows and empty clusters give 0.  S = 0: all 0.
+ *   Workspace: trase_segment_mask_sizes(N, D, S). */
+int trase_kmeans_sizes(int32_t N, int32_t D, int32_t K, size_t* ws_bytes);
+int trase_kmeans_steps(const float* X, int32_t N, int32_t D, int32_t K, float* centres_inout, int32_t* ids_out,
+                       uint64_t reseed_key, float tol, int32_t iter_limit, int32_t n_steps, int32_t* state, void* ws,
+                       size_t ws_bytes, int32_t device, trase_stream_t stream);
+int trase_segment_mask_sizes(int32_t N, int32_t D, int32_t S, size_t* ws_bytes);
+int trase_segment_mask(const float* X, int32_t N, int32_t D, const int32_t* ids, const int32_t* sel, int32_t S, float threshold,
+                       uint8_t* mask_out, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
