@@ -2,11 +2,11 @@
 
     python -m tests.mlp_forms_child OUT.npz infer|train|both
 
-The kernel form is chosen by the TRASE_MLP_* switches of trase_amd/csrc/mlp.hip, which the library reads ONCE per process, so
-the test starts this module as a fresh child process per form (the default form runs in the test's own process through
-``run``).  Inputs and parameters are rebuilt here from fixed seeds on the CPU (``case_inputs``, ``make_params``), so parent and
-child see bit-identical data without shipping it.  Every case runs twice; the second run's bit-equality is recorded.
-Not a test module (no ``test_`` prefix)."""
+"infer" runs the inference entry point (register-chained kernel), "train" the training pair (block forward + backward) under
+every row order of the case.  The test calls ``run`` in its own process; the command line writes the same .npz from a
+library of the caller's choosing (TRASE_RAST_LIB), so the results of two builds can be compared bit for bit.  Inputs and
+parameters are rebuilt from fixed seeds on the CPU (``case_inputs``, ``make_params``), so every process sees bit-identical
+data.  Every case runs twice; the second run's bit-equality is recorded.  Not a test module (no ``test_`` prefix)."""
 from __future__ import annotations
 
 import sys

@@ -1,15 +1,9 @@
-"""Every selectable form of the deformation MLP (trase_amd/csrc/mlp.hip) at full size against the float64 reference of
-tests/mlp_reference.py (bf16 operands, float64 arithmetic).
-
-Forms -- the TRASE_MLP_* switches are read once per process, so each non-default form runs in a fresh child process
-(tests/mlp_forms_child.py) that writes the kernels' outputs and gradients to an .npz; this process builds the reference and
-asserts:
-  default      inference: register-chained kernel, two 32-row groups per wave (mlp_fwd_rc_kernel); training: block kernel
-  rc_g1        TRASE_MLP_RC_G=1: eight-wave inference kernel (mlp_fwd_rc1_kernel)
-  block        TRASE_MLP_RC=0: block inference kernel (mlp_fwd_kernel_blk)
-  rc_train     TRASE_MLP_RC_TRAIN=1: register-chained training forward (mlp_fwd_train_rc_kernel, FULL and tail workgroups)
-  rc_train_g1  TRASE_MLP_RC_TRAIN=1 TRASE_MLP_RC_G=1: eight-wave training forward (mlp_fwd_train_rc1_kernel)
-A form whose switches change nothing for an entry point (e.g. rc_g1's training forward) runs only the other one.
+"""Both kernel forms of the deformation MLP (trase_amd/csrc/mlp.hip) at full size against the float64 reference of
+tests/mlp_reference.py (bf16 operands, float64 arithmetic):
+  inference  register-chained kernel, two 32-row groups per wave (mlp_fwd_rc_kernel)
+  training   block kernel (mlp_fwd_train_kernel_blk, FULL and tail workgroups) + the backward kernels
+tests/mlp_forms_child.py runs them over the cases and writes outputs and gradients to an .npz; this module builds the
+reference and asserts.
 
 Cases (tests/mlp_forms_child.py:cases): 255 .. 300 000 rows, the tails 256 k + r of every wave position of the last RC
 workgroup, 1 000 000 training rows; time as a stride-0 expand and as distinct per-row values; is_blender and is_6dof at
@@ -17,8 +11,6 @@ workgroup, 1 000 000 training rows; time as a stride-0 expand and as distinct pe
 Morton and index row order.  Every bar below is checked separately on the unit-cube rows and on the scene rows.
 """
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -29,59 +21,35 @@ from tests import mlp_reference as R
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FORMS = {            # form -> (environment, entry points run)
-    "default": ({}, "both"),
-    "rc_g1": ({"TRASE_MLP_RC_G": "1"}, "infer"),
-    "block": ({"TRASE_MLP_RC": "0"}, "infer"),
-    "rc_train": ({"TRASE_MLP_RC_TRAIN": "1"}, "train"),
-    "rc_train_g1": ({"TRASE_MLP_RC_TRAIN": "1", "TRASE_MLP_RC_G": "1"}, "train"),
-}
-CHILD_TIMEOUT = 300
-
 # Outputs against the bf16 float64 reference, per row group (elementwise of the group's output scale, relative L2 per output).
-# The 2e-3 elementwise bar of the 20 011-row test (test_gpu_parity.py) does not hold at full size for ANY of the five forms: an
+# The 2e-3 elementwise bar of the 20 011-row test (test_gpu_parity.py) does not hold at full size for either form: an
 # activation whose fp32 sum lands within accumulation noise of a bf16 rounding boundary rounds to the neighbouring bf16 value
 # (0.4 % of it), which moves an output by ~2e-3 of its scale; with 300 k rows x 2048 activations such rows always exist.  The
-# forms differ from EACH OTHER by as much (below); the mutated references of the last test miss by 0.25 (rows swapped), 0.63
+# two forms differ from EACH OTHER by as much (below); the mutated references of the last test miss by 0.25 (rows swapped), 0.63
 # (time of the next row) and 5.9 (skip encoding dropped) of scale.
 # Measured worst on MI355X: unit rows 4.71e-3 of scale (blender, 300 000) / rel L2 4.55e-4; scene rows 4.66e-3 / rel L2 8.95e-4
 # (32 scene rows of 257).  Before the encoding's argument reduction (mlp.hip pe_rev) the unit rows' rel L2 was 7.7e-4 and the
 # scene rows' 3.7e-3: __sinf lost up to 1e-3 rad at |x 2^9| = 2e4 rad, a quarter of a bf16 ulp of the encoding.
 OUT_ABS = 1e-5
 OUT_BARS = {"unit": (1e-2, 1.5e-3), "scene": (1e-2, 3e-3)}       # group -> (elementwise of scale, relative L2)
-# Forms against the default inference form, of max(scale, 1): the unit rows keep the bar of the suite's training-vs-inference
-# check (test_gpu_parity.py, 4e-4; measured worst 2.70e-4, block training forward, 6dof 300 000).  Scene-sized rows feed
-# |x| up to 40 into the network, so their activations are large against their outputs and one bf16 flip moves an output
-# further: measured worst 1.17e-3 (block training forward, 1 000 000 rows).  The register-chained training forwards equal the register-chained inference bit for bit.
+# Training forward against the inference forward, of max(scale, 1): the unit rows keep the bar of the suite's training-vs-inference
+# check (test_gpu_parity.py, 4e-4; measured worst 2.70e-4, 6dof 300 000).  Scene-sized rows feed |x| up to 40 into the
+# network, so their activations are large against their outputs and one bf16 flip moves an output further: measured worst
+# 1.17e-3 (1 000 000 rows).
 FORM_TOLS = {"unit": 4e-4, "scene": 2.5e-3}
 # parameter gradients against the bf16 float64 reference, the bars of test_deform_mlp_training_step_matches_bf16_evaluated_autograd
-# (measured worst: rel L2 1.80e-2, linear.0.weight at 769 rows; elementwise 6.43e-2 of scale, rc_train at 832 rows)
+# (measured worst: rel L2 1.80e-2, linear.0.weight at 769 rows; elementwise 4.95e-2 of scale at 769 rows)
 GRAD_REL_L2, GRAD_ELEM = 5e-2, 1e-1
 
 
 @pytest.fixture(scope="module")
 def results(tmp_path_factory):
-    """form -> NpzFile of its outputs.  The default form runs here, the others one after another in child processes; a
-    child that fails (any non-zero status, signals included) fails the module at once and no further child starts."""
-    leaked = sorted(k for k in os.environ if k.startswith("TRASE_MLP_") and k != "TRASE_MLP_ROW_ORDER")
-    if leaked or os.environ.get("TRASE_MLP_ROW_ORDER", "morton") != "morton":
-        pytest.fail(f"the test process must run the default MLP form; found {leaked or 'TRASE_MLP_ROW_ORDER'} in the environment")
-    d = tmp_path_factory.mktemp("mlp_forms")
-    out = {}
-    for form, (env_add, mode) in FORMS.items():
-        path = str(d / f"{form}.npz")
-        if not env_add:
-            child.run(path, mode)
-        else:
-            env = {k: v for k, v in os.environ.items() if not k.startswith("TRASE_MLP_")}
-            env.update(env_add)
-            p = subprocess.run([sys.executable, "-m", "tests.mlp_forms_child", path, mode], cwd=ROOT, env=env,
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-            if p.returncode != 0:
-                pytest.fail(f"form {form} ({env_add}) exited with status {p.returncode}:\n{p.stderr[-4000:]}")
-        out[form] = np.load(path)
-    return out
+    """NpzFile of the inference and training outputs and gradients of every case."""
+    if os.environ.get("TRASE_MLP_ROW_ORDER", "morton") != "morton":
+        pytest.fail("the test process must run the default Morton row order; found TRASE_MLP_ROW_ORDER in the environment")
+    path = str(tmp_path_factory.mktemp("mlp_forms") / "default.npz")
+    child.run(path, "both")
+    return np.load(path)
 
 
 @pytest.fixture(scope="module")
@@ -134,79 +102,71 @@ def _outputs(res, tag):
 
 
 def test_inference_and_training_forwards_match_float64_reference(results, refs):
-    """Every form's inference outputs and every training forward's outputs, every case, against the bf16 float64 reference."""
+    """The inference outputs and the training forward's outputs (every row order), every case, against the bf16 float64
+    reference."""
     misses = []
     for c in child.cases():
         ref, _ = refs(c)
         groups = _groups(c)
-        for form, (_, mode) in FORMS.items():
-            tags = ([f"{c.name}|infer"] if mode in ("infer", "both") else []) + \
-                   ([f"{c.name}|train-{o}" for o in c.orders] if mode in ("train", "both") else [])
-            for tag in tags:
-                worst, miss = compare_outputs(_outputs(results[form], tag), ref, groups)
-                print(f"[measured] {form:12s} {tag:36s} vs float64 ref  {_fmt(worst)}")
-                misses += [f"{form} {tag}: {m}" for m in miss]
+        for tag in [f"{c.name}|infer"] + [f"{c.name}|train-{o}" for o in c.orders]:
+            worst, miss = compare_outputs(_outputs(results, tag), ref, groups)
+            print(f"[measured] {tag:36s} vs float64 ref  {_fmt(worst)}")
+            misses += [f"{tag}: {m}" for m in miss]
     assert not misses, "\n".join(misses)
 
 
 def test_forms_agree_with_default_inference(results):
-    """All inference forms and all training forwards against the default inference form, every case."""
+    """The training forward (every row order) against the inference forward, every case."""
     misses = []
     for c in child.cases():
-        base = _outputs(results["default"], f"{c.name}|infer")
+        base = _outputs(results, f"{c.name}|infer")
         groups = _groups(c)
-        for form, (_, mode) in FORMS.items():
-            tags = ([f"{c.name}|infer"] if mode == "infer" else []) + \
-                   ([f"{c.name}|train-{o}" for o in c.orders] if mode in ("train", "both") else [])
-            for tag in tags:
-                worst = {}
-                for gname, rows in groups:
-                    if not bool(rows.any()):
-                        continue
-                    worst[gname] = 0.0
-                    for j, (a, b) in enumerate(zip(_outputs(results[form], tag), base)):
-                        a, b = a[rows.numpy()], b[rows.numpy()]
-                        d, scale = float(np.abs(a - b).max()), max(float(np.abs(b).max()), 1.0)
-                        worst[gname] = max(worst[gname], d / scale)
-                        if d > FORM_TOLS[gname] * scale:
-                            misses.append(f"{form} {tag} {gname} output {j}: {d:.3e} vs default (scale {scale:.3e})")
-                print(f"[measured] {form:12s} {tag:36s} vs default inference  "
-                      + "  ".join(f"{g}: {v:.2e}" for g, v in worst.items()) + " of max(scale, 1)")
+        for tag in [f"{c.name}|train-{o}" for o in c.orders]:
+            worst = {}
+            for gname, rows in groups:
+                if not bool(rows.any()):
+                    continue
+                worst[gname] = 0.0
+                for j, (a, b) in enumerate(zip(_outputs(results, tag), base)):
+                    a, b = a[rows.numpy()], b[rows.numpy()]
+                    d, scale = float(np.abs(a - b).max()), max(float(np.abs(b).max()), 1.0)
+                    worst[gname] = max(worst[gname], d / scale)
+                    if d > FORM_TOLS[gname] * scale:
+                        misses.append(f"{tag} {gname} output {j}: {d:.3e} vs inference (scale {scale:.3e})")
+            print(f"[measured] {tag:36s} vs inference  "
+                  + "  ".join(f"{g}: {v:.2e}" for g, v in worst.items()) + " of max(scale, 1)")
     assert not misses, "\n".join(misses)
 
 
 def test_training_gradients_match_float64_reference(results, refs):
-    """Every training form (block = default, rc_train, rc_train_g1), every case and row order, every parameter gradient
-    against the float64 reference's (straight-through bf16 rounding; dead slab of zero cotangents included)."""
+    """Every case and row order, every parameter gradient against the float64 reference's (straight-through bf16
+    rounding; dead slab of zero cotangents included)."""
     misses = []
     for c in child.cases():
         _, want = refs(c)
-        for form, (_, mode) in FORMS.items():
-            if mode == "infer":
-                continue
-            for o in c.orders:
-                tag = f"{c.name}|train-{o}"
-                wr, we, wk = 0.0, 0.0, ""
-                for k, w in want.items():
-                    g = torch.as_tensor(results[form][f"{tag}|grad|{k}"]).cuda().double()
-                    scale = float(w.abs().max())
-                    if scale == 0.0:
-                        if float(g.abs().max()) != 0.0:
-                            misses.append(f"{form} {tag} grad {k}: nonzero where the reference is zero")
-                        continue
-                    err, rel = float((g - w).abs().max()), float((g - w).norm() / w.norm())
-                    if rel > wr:
-                        wk = k
-                    wr, we = max(wr, rel), max(we, err / scale)
-                    if not (rel < GRAD_REL_L2 and err < GRAD_ELEM * scale + 1e-6):
-                        misses.append(f"{form} {tag} grad {k}: rel L2 {rel:.3e}, max {err:.3e} vs scale {scale:.3e}")
-                print(f"[measured] {form:12s} {tag:36s} grads vs float64 ref: worst rel L2 {wr:.2e} ({wk}), worst max {we:.2e} of scale")
+        for o in c.orders:
+            tag = f"{c.name}|train-{o}"
+            wr, we, wk = 0.0, 0.0, ""
+            for k, w in want.items():
+                g = torch.as_tensor(results[f"{tag}|grad|{k}"]).cuda().double()
+                scale = float(w.abs().max())
+                if scale == 0.0:
+                    if float(g.abs().max()) != 0.0:
+                        misses.append(f"{tag} grad {k}: nonzero where the reference is zero")
+                    continue
+                err, rel = float((g - w).abs().max()), float((g - w).norm() / w.norm())
+                if rel > wr:
+                    wk = k
+                wr, we = max(wr, rel), max(we, err / scale)
+                if not (rel < GRAD_REL_L2 and err < GRAD_ELEM * scale + 1e-6):
+                    misses.append(f"{tag} grad {k}: rel L2 {rel:.3e}, max {err:.3e} vs scale {scale:.3e}")
+            print(f"[measured] {tag:36s} grads vs float64 ref: worst rel L2 {wr:.2e} ({wk}), worst max {we:.2e} of scale")
     assert not misses, "\n".join(misses)
 
 
 def test_forms_are_bit_reproducible(results):
-    """Each form, run twice in its process, gives bit-identical outputs (and gradients)."""
-    bad = [f"{form}: {k}" for form, res in results.items() for k in res.files if k.endswith("|repro") and not bool(res[k])]
+    """Every case, run twice, gives bit-identical outputs (and gradients)."""
+    bad = [k for k in results.files if k.endswith("|repro") and not bool(results[k])]
     assert not bad, bad
 
 
@@ -215,7 +175,7 @@ def test_bars_reject_mutated_references(results, refs):
     time: two adjacent rows swapped in the last full 256-row workgroup, every row's time taken from the next row, and the
     skip layer's encoding columns dropped."""
     c = next(c for c in child.cases() if c.name == "default-20011-rows")
-    got = _outputs(results["default"], f"{c.name}|infer")
+    got = _outputs(results, f"{c.name}|infer")
     ref, _ = refs(c)
     groups = _groups(c)
     worst, miss = compare_outputs(got, ref, groups)

@@ -1,17 +1,19 @@
 // mlp.hip -- the per-Gaussian deformation MLP (utils/time_utils.py:60-131 DeformNetwork, called through
-// scene/deform_model.py:34-35 at train.py:202-204, render.py:195, gui.py:965) as ONE fused forward kernel
-// on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, fp32 accumulate).
+// scene/deform_model.py:34-35 at train.py:202-204, render.py:195, gui.py:965) as fused kernels on the bf16
+// matrix cores (v_mfma_f32_32x32x16_bf16, fp32 accumulate).
 //
 // Network (default TRASE config D=8, W=256, multires=10, t_multires=10, not blender, not 6dof):
 //   PE(x) 63 | PE(t) 21  -> 84 -> [Linear 256 + ReLU] x 8, layer 5 sees cat(PE, h) = 340 -> heads 3 | 4 | 3.
-// Fusion: a workgroup of 4 waves owns 128 Gaussians, each wave 32 rows.  Activations never leave the CU:
-// they live in LDS as bf16 (64 KiB, XOR-swizzled 16-byte chunks so that the row-per-lane fragment reads are
-// conflict free), the positional encoding is generated once per wave into six register fragments, weights
-// stream from L2 (1 MB of bf16 for the whole net), bias (as the accumulator's initial value) + ReLU + bf16
-// happen in the MFMA epilogue.  Waves never synchronise with each other; two waves share a SIMD.
-// Training (GAUSSIAN state, train.py:202-204 / :299): the same forward additionally saves the activations as
-// "transposed images" and the ReLU gates as bits; the backward is a fused data chain of the same shape plus
-// split-N MFMA GEMMs for the parameter gradients (see "training backward" below).
+// The fp32 parameters are re-packed to bf16 on every call (they change every optimizer step).  Each forward is ONE
+// kernel for the whole network: the positional encoding is generated in registers, bias (as the accumulator's initial
+// value) + ReLU + bf16 happen in the MFMA epilogue, and activations never leave the CU.
+//   inference (trase_mlp_forward): mlp_fwd_rc_kernel, register-chained -- a wave owns 64 rows and all 256 columns, the
+//     accumulators of a layer ARE the next layer's B fragments, the weights are one stream staged through LDS.
+//   training forward (trase_mlp_forward_train*, GAUSSIAN state, train.py:202-204 / :299): mlp_fwd_train_kernel_blk,
+//     block-GEMM -- a workgroup owns 128 rows in a shared LDS tile and stages every weight slab once; it also saves the
+//     activations as "transposed images" and the ReLU gates as bits.
+//   training backward: a data chain of the block kernel's shape plus split-N MFMA GEMMs for the parameter gradients
+//     (see "training backward" below).
 #include "common.h"
 #include <type_traits>
 
@@ -213,17 +215,11 @@ __device__ __forceinline__ void patch_store(s16x4p v, const PatchLane& pl, __bf1
   }
   typedef unsigned u2v __attribute__((ext_vector_type(2)));
   const u2v o2 = __builtin_bit_cast(u2v, v);
-#ifdef TRASE_MLP_PLAIN_STORES
-  *reinterpret_cast<u2v*>(img_patch + pl.img_elem) = o2;
-#else
   __builtin_nontemporal_store(o2, reinterpret_cast<u2v*>(img_patch + pl.img_elem));
-#endif
 }
 
-// ---- inference forward, block-GEMM organisation ---------------------------------------------------------------------
-// The 32-row chain kernel makes every wave stream every weight slab from L2 on its own (16 MAC per byte through the vector
-// memory path) and hides the round trip with a single K-step of lookahead; PMC shows the matrix pipe busy 36 %.  Here
-// the WORKGROUP owns 128 rows and stages each 256 x 16 weight slab (8 KiB, contiguous in the K-slice-major packing) in
+// ---- training forward, block-GEMM organisation ----------------------------------------------------------------------
+// The WORKGROUP owns 128 rows and stages each 256 x 16 weight slab (8 KiB, contiguous in the K-slice-major packing) in
 // LDS exactly once, double-buffered, one workgroup barrier per K-step.  Wave (wr, wc) owns rows wr*64.. (two 32-row
 // groups) x output columns wc*128.. : 8 MFMAs per K-step from 4 weight + 2 activation fragments out of LDS, 128
 // accumulator registers, two workgroups per CU (80 KiB of LDS each: 64 KiB activations shared by the four waves + two
@@ -262,19 +258,19 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_barrier();
 }
 
-// SAVE: training forward -- additionally writes, per layer, the transposed image of the post-ReLU activations and the
-// ReLU gates (same saved-state layout as the chain kernel, so the backward does not care which forward produced it)
+// Besides the outputs, writes the state the backward reads: per layer the transposed image of the post-ReLU activations and
+// the ReLU gates, and the encoding's image.
 // FULL: every row of the workgroup's 128 exists (all workgroups but the last): the image stores are then unconditional --
 // inside a branch the compiler's wait counts cannot rely on them having been issued, and a wait for an older weight slab then
 // includes them
-template <bool SAVE, bool FULL>
+template <bool FULL>
 __device__ __forceinline__ void mlp_fwd_blk_body(__bf16* __restrict__ act, __bf16 (*s_w)[2][MW * 8], const MlpNet& net,
                                                  const float* __restrict__ x, const float* __restrict__ t, int t_stride, int N,
                                                  float* __restrict__ d_xyz, float* __restrict__ d_rot,
                                                  float* __restrict__ d_scale, __bf16* __restrict__ actsT,
-                                                 uint32_t* __restrict__ gates, const int* __restrict__ ro = nullptr,
-                                                 __bf16* __restrict__ peT = nullptr) {
-  // ro (row order, training only): batch row r evaluates Gaussian ro[r] -- inputs are gathered and the ten outputs scattered
+                                                 uint32_t* __restrict__ gates, const int* __restrict__ ro,
+                                                 __bf16* __restrict__ peT) {
+  // ro (row order, may be null): batch row r evaluates Gaussian ro[r] -- inputs are gathered and the ten outputs scattered
   // through it; everything saved for the backward (images, gates) is in BATCH order (see "dead rows" below)
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m = lane & 31, h = lane >> 5;
@@ -302,7 +298,7 @@ __device__ __forceinline__ void mlp_fwd_blk_body(__bf16* __restrict__ act, __bf1
     sb0 = *reinterpret_cast<const uint4*>(src); sb1 = *reinterpret_cast<const uint4*>(src + 8);
     sa0 = *reinterpret_cast<const uint4*>(src + (size_t)MW * 16); sa1 = *reinterpret_cast<const uint4*>(src + (size_t)MW * 16 + 8);
   }
-  // SAVE: the transposed image of a layer's activations is NOT stored in that layer's epilogue -- loads and stores share
+  // The transposed image of a layer's activations is NOT stored in that layer's epilogue -- loads and stores share
   // vmcnt, in order, so the burst of 32 stores per wave stalled the next layer's second weight slab until it had drained
   // (0.56 ms against 0.33 for inference = exactly the store time).  The tile stays in LDS as the next layer's A operand;
   // the wave re-reads its own 32 pieces from there, four per K-step pair, while the next layer multiplies.
@@ -321,7 +317,7 @@ __device__ __forceinline__ void mlp_fwd_blk_body(__bf16* __restrict__ act, __bf1
     if constexpr (FULL) patch_store(v, pl, patch, 16);
     else if ((growb & ~31) < N) patch_store(v, pl, patch, min(max(N - growb, 0), 16));   // the 32-row image tile exists
   };
-  if constexpr (SAVE) {
+  {
     // The encoding as a transposed image (operand of the weight-gradient GEMMs of layers 0 and 5; a kernel of its own cost 0.04 ms
     // per step for this).  Done HERE, before any accumulator is live (inside layer 0's K-steps the same code spilled): the two
     // waves of a row block share the six K-steps (wc = 0: columns 0..47, wc = 1: 48..95), park their fragments in the idle
@@ -399,7 +395,7 @@ __device__ __forceinline__ void mlp_fwd_blk_body(__bf16* __restrict__ act, __bf1
     auto kpair = [&](int ks, const bf16x8 (&a0)[BRG], const bf16x8 (&a1)[BRG], auto&& between) {
       slab_load(ks + 2, sb0, sb1);
       mma(0, a0);
-      between();                                             // (SAVE: image stores -- early in the pair, so that the slab
+      between();                                             // (image stores -- early in the pair, so that the slab
       slab_park(1, sa0, sa1);                                // loads issued after them have ~1.5 pairs to get past them)
       lds_barrier();
       slab_load(ks + 3, sa0, sa1);
@@ -437,23 +433,19 @@ __device__ __forceinline__ void mlp_fwd_blk_body(__bf16* __restrict__ act, __bf1
       }
       constexpr int DP = BRG * 16 / (MW / 32);             // image pieces of the previous layer per K-step pair (4)
       const int p0 = ((ks - emb_k) >> 1) * DP;
-      s16x4p dv[DP];
-      if constexpr (SAVE) {                                  // (l >= 1 here: layer 0 has no K-steps of this kind)
+      s16x4p dv[DP];                                         // (l >= 1 here: layer 0 has no K-steps of this kind)
 #pragma unroll
-        for (int j = 0; j < DP; ++j) dv[j] = drain_read(p0 + j);
-      }
+      for (int j = 0; j < DP; ++j) dv[j] = drain_read(p0 + j);
       kpair(ks, a0, a1, [&] {
-        if constexpr (SAVE) {
 #pragma unroll
-          for (int j = 0; j < DP; ++j) drain_store(l - 1, p0 + j, dv[j]);
-        }
+        for (int j = 0; j < DP; ++j) drain_store(l - 1, p0 + j, dv[j]);
       });
     }
     // epilogue: ReLU, bf16, this wave's 64 x 128 block of the tile (all reads of the old tile are behind the last barrier)
 #pragma unroll
     for (int g = 0; g < BRG; ++g) {
       const int grow = row0 + 32 * g + m;
-      unsigned gate[2] = {0u, 0u};                           // SAVE: this lane's 64 ReLU gates of the layer
+      unsigned gate[2] = {0u, 0u};                           // this lane's 64 ReLU gates of the layer
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
@@ -461,21 +453,19 @@ __device__ __forceinline__ void mlp_fwd_blk_body(__bf16* __restrict__ act, __bf1
           const int f0 = wc * 128 + nb * 32 + 8 * q + 4 * h;
           const s16x4 pk = relu_bf16x4(acc[g][nb][4 * q], acc[g][nb][4 * q + 1], acc[g][nb][4 * q + 2], acc[g][nb][4 * q + 3]);
           *reinterpret_cast<s16x4*>(act + act_off(lrow0 + 32 * g + m, f0)) = pk;
-          if constexpr (SAVE) gate[nb >> 1] |= gate_bits4(pk) << ((nb & 1) * 16 + q * 4);
+          gate[nb >> 1] |= gate_bits4(pk) << ((nb & 1) * 16 + q * 4);
         }
-      if constexpr (SAVE)      // the row's 256 gate bits are two uint4 (h = 0 / 1); this wave owns words 2 wc, 2 wc + 1 of each
-        if (FULL || grow < N) *reinterpret_cast<uint2*>(gates + (((size_t)l * N + grow) * 2 + h) * 4 + wc * 2) = uint2{gate[0], gate[1]};
+      // the row's 256 gate bits are two uint4 (h = 0 / 1); this wave owns words 2 wc, 2 wc + 1 of each
+      if (FULL || grow < N) *reinterpret_cast<uint2*>(gates + (((size_t)l * N + grow) * 2 + h) * 4 + wc * 2) = uint2{gate[0], gate[1]};
     }
     lds_barrier();             // the tile is complete; the image stores and the next layer's slab loads stay in flight
   }
-  if constexpr (SAVE) {
-    for (int p0 = 0; p0 < BRG * 16; p0 += 8) {
-      s16x4p dv[8];
+  for (int p0 = 0; p0 < BRG * 16; p0 += 8) {
+    s16x4p dv[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) dv[j] = drain_read(p0 + j);
+    for (int j = 0; j < 8; ++j) dv[j] = drain_read(p0 + j);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) drain_store(MD - 1, p0 + j, dv[j]);
-    }
+    for (int j = 0; j < 8; ++j) drain_store(MD - 1, p0 + j, dv[j]);
   }
   if (wc != 0) return;                                       // heads: one wave per 64 rows
   f32x16 hacc[BRG];
@@ -518,24 +508,16 @@ __device__ __forceinline__ void mlp_fwd_blk_body(__bf16* __restrict__ act, __bf1
 }
 
 __global__ __launch_bounds__(MWAVES* WAVE) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void mlp_fwd_kernel_blk(MlpNet net, const float* __restrict__ x, const float* __restrict__ t, int t_stride, int N,
-                        float* __restrict__ d_xyz, float* __restrict__ d_rot, float* __restrict__ d_scale) {
-  __shared__ __attribute__((aligned(16))) __bf16 act[BROWS * MW];                   // 64 KiB
-  __shared__ __attribute__((aligned(16))) __bf16 s_w[2][2][MW * 8];                 // [buffer][k half][n][8]: 16 KiB
-  mlp_fwd_blk_body<false, false>(act, s_w, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, nullptr, nullptr);
-}
-
-__global__ __launch_bounds__(MWAVES* WAVE) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void mlp_fwd_train_kernel_blk(MlpNet net, const float* __restrict__ x, const float* __restrict__ t, int t_stride, int N,
                               float* __restrict__ d_xyz, float* __restrict__ d_rot, float* __restrict__ d_scale,
                               __bf16* __restrict__ actsT, uint4* __restrict__ gates, const int* __restrict__ ro,
                               __bf16* __restrict__ peT) {
-  __shared__ __attribute__((aligned(16))) __bf16 act[BROWS * MW];
-  __shared__ __attribute__((aligned(16))) __bf16 s_w[2][2][MW * 8];
+  __shared__ __attribute__((aligned(16))) __bf16 act[BROWS * MW];                   // 64 KiB
+  __shared__ __attribute__((aligned(16))) __bf16 s_w[2][2][MW * 8];                 // [buffer][k half][n][8]: 16 KiB
   if ((int)(blockIdx.x + 1) * BROWS <= N)
-    mlp_fwd_blk_body<true, true>(act, s_w, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, actsT, reinterpret_cast<uint32_t*>(gates), ro, peT);
+    mlp_fwd_blk_body<true>(act, s_w, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, actsT, reinterpret_cast<uint32_t*>(gates), ro, peT);
   else
-    mlp_fwd_blk_body<true, false>(act, s_w, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, actsT, reinterpret_cast<uint32_t*>(gates), ro, peT);
+    mlp_fwd_blk_body<false>(act, s_w, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, actsT, reinterpret_cast<uint32_t*>(gates), ro, peT);
 }
 
 // ---- training backward ------------------------------------------------------------------------------------
@@ -814,9 +796,7 @@ struct WgradJob {
 constexpr int WG_MAX_JOBS = 8;
 // distance between the partial planes of consecutive row groups, in floats: NOT the bare M * NK -- the reduction reads the
 // same offset of every plane, and planes a power of two apart put all of those reads on the same memory channels
-#ifndef WG_PLANE_PAD
-#define WG_PLANE_PAD 1088
-#endif
+constexpr int WG_PLANE_PAD = 1088;
 __host__ __device__ constexpr size_t wg_plane(int M, int NK) { return (size_t)M * NK + WG_PLANE_PAD; }
 struct WgradJobs { WgradJob j[WG_MAX_JOBS]; };
 
@@ -1048,12 +1028,12 @@ __global__ __launch_bounds__(256) void mlp_wreduce_kernel(WreduceJobs jobs) {
 }
 
 // =====================================================================================================================
-// Round 6: the chain kernels in a register-chained, OUTPUT-stationary organisation ("RC").
+// ---- inference forward, register-chained OUTPUT-stationary organisation ("RC") ---------------------------------------
 //
-// Why: the block kernels above are bound by LDS throughput, not by the matrix pipe.  Per layer and CU they move 768 KB of
-// fragment reads (256 B/clk), 256 KB of weight-slab stores and 128 KB of activation stores (ds_write_b128 / _b64: ~80 B/clk,
+// Why not the block organisation above: it is bound by LDS throughput, not by the matrix pipe.  Per layer and CU it moves 768 KB
+// of fragment reads (256 B/clk), 256 KB of weight-slab stores and 128 KB of activation stores (ds_write_b128 / _b64: ~80 B/clk,
 // MI355X_MICROARCH.md "LDS") = ~7 900 LDS cycles against 8 192 matrix-pipe cycles: every imperfection of the overlap is lost time
-// (measured: 39 % of the bf16 peak).  Here
+// (measured: 39 % of the bf16 peak; 0.300 ms against this kernel's 0.248 at 300k rows).  Here
 //   * a WAVE owns 64 rows (two 32-row groups) and ALL 256 columns of a layer; the workgroup (4 waves, one per SIMD, 256 rows)
 //     shares nothing but the weights;
 //   * activations never touch LDS: the fp32 accumulators of an output block, converted to bf16 in place, ARE two B fragments of
@@ -1067,6 +1047,8 @@ __global__ __launch_bounds__(256) void mlp_wreduce_kernel(WreduceJobs jobs) {
 //     256 rows through a three-slot ring of 16-fragment groups: per group one workgroup barrier, placed in the middle of the
 //     previous group so that the fragment reads run ahead across group boundaries.
 // LDS per layer and CU: 512 KB of reads + 128 KB of stores = ~3 700 cycles against the same 8 192 matrix-pipe cycles.
+// The training forward stays on the block organisation: saving the state adds ~120 single-issue instructions per 32-MFMA block
+// to a kernel that is already at the issue limit.
 constexpr int RC_ROWS = 256;                 // rows per workgroup (4 waves x 64)
 constexpr int RC_G = 16;                     // fragments per staged group (16 KB)
 constexpr int RC_SLOTS = 3;                  // ring slots (groups)
@@ -1090,7 +1072,7 @@ struct RcNet {
   const float* temb;       // is_blender: the 30 shared timenet outputs; else nullptr
 };
 
-// weight packing for the RC kernels: one thread per fragment element
+// weight packing for the RC kernel: one thread per fragment element
 __global__ __launch_bounds__(256) void mlp_pack_rc_kernel(MlpPackArgs a, __bf16* __restrict__ ws, float* __restrict__ bias) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx < MD * MW) bias[idx] = a.b[idx / MW][idx % MW];
@@ -1132,25 +1114,13 @@ struct RcStream {
   uint4 st[4];              // staging registers: this wave's four fragments of the group being fetched
 };
 
-// 8-byte slot permutation of the 64-byte rows of a wave's transposition scratch (SAVE): slot ^ rc_swz(row) makes both the
-// epilogue's ds_write_b64 (16 lanes = 16 rows, one slot) and the transposing reads (32 lanes = 8 rows x 4 slots) conflict-free
-__device__ __forceinline__ int rc_swz(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 1) | (((row >> 2) & 1) << 2); }
-
-// SAVE: training forward -- additionally writes, per layer, the transposed image of the post-ReLU activations, the ReLU gates as
-// bits and the encoding image: the SAME saved state as mlp_fwd_blk_body (the backward does not care which forward produced it).
-// FULL: every row of the workgroup's 256 exists (image stores unconditional).
-// G: 32-row groups per wave -- 2: four waves per workgroup, one per SIMD (a weight fragment read feeds two MFMAs); 1: eight waves, two per
-// SIMD (each wave half the registers; the second wave's VALU / LDS / VMEM instructions issue under the first one's MFMAs)
-template <bool SAVE, bool FULL, int G = 2>
 __device__ __forceinline__ void mlp_fwd_rc_body(unsigned char* __restrict__ ring, float* __restrict__ s_bias, const RcNet& net,
                                                 const float* __restrict__ x, const float* __restrict__ t, int t_stride, int N,
                                                 float* __restrict__ d_xyz, float* __restrict__ d_rot, float* __restrict__ d_scale,
-                                                const int* __restrict__ ro, unsigned char* __restrict__ pe_store,
-                                                unsigned char* __restrict__ scratch = nullptr,
-                                                __bf16* __restrict__ actsT = nullptr, uint32_t* __restrict__ gates = nullptr,
-                                                __bf16* __restrict__ peT = nullptr) {
+                                                unsigned char* __restrict__ pe_store) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int m = lane & 31, h = lane >> 5;
+  constexpr int G = 2;                         // 32-row groups per wave: a weight fragment read feeds two MFMAs
   constexpr int WROWS = 32 * G, NWV = RC_ROWS / WROWS, FPW = RC_G / NWV, NP = 2 * G;   // rows per wave, waves, staged fragments per wave and group, epilogue pieces
   const int row0 = blockIdx.x * RC_ROWS + wave * WROWS;
   // ---- biases into LDS (8.1 KB), inputs into registers --------------------------------------------------------------
@@ -1158,8 +1128,7 @@ __device__ __forceinline__ void mlp_fwd_rc_body(unsigned char* __restrict__ ring
   float px[G][4];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    int gm = min(row0 + 32 * g + m, N - 1);
-    if (ro) gm = ro[gm];
+    const int gm = min(row0 + 32 * g + m, N - 1);
     px[g][0] = x[3 * gm]; px[g][1] = x[3 * gm + 1]; px[g][2] = x[3 * gm + 2]; px[g][3] = t[(size_t)gm * t_stride];
   }
   const bool blender = net.temb != nullptr;
@@ -1178,12 +1147,12 @@ __device__ __forceinline__ void mlp_fwd_rc_body(unsigned char* __restrict__ ring
   auto stage_load = [&](int grp) {
     const __bf16* p = gsrc + (size_t)grp * RC_G * 512;
     st0 = *reinterpret_cast<const uint4*>(p); st1 = *reinterpret_cast<const uint4*>(p + 512);
-    if constexpr (FPW == 4) { st2 = *reinterpret_cast<const uint4*>(p + 1024); st3 = *reinterpret_cast<const uint4*>(p + 1536); }
+    st2 = *reinterpret_cast<const uint4*>(p + 1024); st3 = *reinterpret_cast<const uint4*>(p + 1536);
   };
   auto stage_park = [&](int grp) {
     unsigned char* q = wr + (grp % RC_SLOTS) * (RC_G * 1024);
     *reinterpret_cast<uint4*>(q) = st0; *reinterpret_cast<uint4*>(q + 1024) = st1;
-    if constexpr (FPW == 4) { *reinterpret_cast<uint4*>(q + 2048) = st2; *reinterpret_cast<uint4*>(q + 3072) = st3; }
+    *reinterpret_cast<uint4*>(q + 2048) = st2; *reinterpret_cast<uint4*>(q + 3072) = st3;
   };
   auto frag_read = [&](int f) -> bf16x8 {
     return *reinterpret_cast<const bf16x8*>(rd + ((f / RC_G) % RC_SLOTS) * (RC_G * 1024) + (f % RC_G) * 1024);
@@ -1202,13 +1171,8 @@ __device__ __forceinline__ void mlp_fwd_rc_body(unsigned char* __restrict__ ring
   auto advance = [&](int f) {
     if (f % RC_G == 0) {                       // start of group f/16: park group +1 (fetched during the previous group), fetch group +2
       const int grp = f / RC_G;
-#ifndef RC_DBG_NOSTAGE
       if (grp + 1 < NGRP) stage_park(grp + 1);
       if (grp + 2 < NGRP) stage_load(grp + 2);
-#else
-      if (grp == 0) { stage_park(1); stage_load(2); }
-      if (grp == 1) stage_park(2);
-#endif
     }
     if (f % RC_G == RC_G / 2) lds_barrier();   // everybody has parked group +1 (and finished reading group -1): +1 is readable
     if (f + LA < RC_FWD_FRAGS) wf[(f + LA) % (LA + 1)] = frag_read(f + LA);
@@ -1232,73 +1196,6 @@ __device__ __forceinline__ void mlp_fwd_rc_body(unsigned char* __restrict__ ring
     for (int k = 0; k < RC_PE_KS; ++k) *reinterpret_cast<bf16x8*>(pe_lds + (g * RC_PE_KS + k) * 1024) = pe[g][k];
   }
   auto pe_frag = [&](int g, int k) -> bf16x8 { return *reinterpret_cast<const bf16x8*>(pe_lds + (g * RC_PE_KS + k) * 1024); };
-  // ---- SAVE: the wave's transposition scratch (64 rows x 64 bytes, slots permuted by rc_swz) ----------------------------
-  unsigned char* const scr = SAVE ? scratch + wave * (WROWS * 64) : nullptr;
-  const int tiles = (N + 31) >> 5;
-  const int u_row0 = __builtin_amdgcn_readfirstlane(row0);
-  PatchLane pl;                                     // (only img_elem / row4 are used: patch_store)
-  int tr_off = 0;                                   // this lane's byte offset for a transposing read of patch (r0 = 0, c0 = 0)
-  int tr_sw = 0;
-  if constexpr (SAVE) {
-    const int grp = lane >> 4, i = lane & 15, jj = i >> 2, cc = i & 3;
-    pl.img_elem = i * 16 + 4 * grp; pl.row4 = 4 * grp; pl.lds_elem = 0; pl.sw = 0; pl.cch = 0;
-    tr_off = (4 * grp + jj) * 64; tr_sw = rc_swz(4 * grp + jj);
-    tr_off += 0 * cc;
-  }
-  // 16-row x 16-column patch (r0 multiple of 16, c0 in {0, 16}) of the scratch, transposed: lane (grp, i) <- column c0 + i, rows r0 + 4 grp ..
-  auto scr_patch_read = [&](int r0, int c0) -> s16x4p {
-    typedef __attribute__((address_space(3))) s16x4p lds_s16x4;
-    const int cc = lane & 3;
-    const int slot = ((c0 >> 2) + cc) ^ tr_sw;      // (r0 is a multiple of 16: rc_swz(row) does not depend on it)
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(scr + r0 * 64 + tr_off + slot * 8));
-  };
-  // four bf16 (columns col4 .. col4 + 3 of the scratch block, col4 a multiple of 4) of row `r` (= 32 g + m)
-  auto scr_write4 = [&](int r, int col4, s16x4 v) {
-    *reinterpret_cast<s16x4*>(scr + r * 64 + (((col4 >> 2) ^ rc_swz(r)) * 8)) = v;
-  };
-  // the image patches of the block sitting in the scratch: `which` = 0..3 -> row patch `which` (16 rows), both column patches
-  auto image_store = [&](__bf16* __restrict__ img, int img_cols, int col0, int which) {
-#ifdef RC_DBG_NOIMG
-    return;
-#endif
-    const s16x4p v0 = scr_patch_read(16 * which, 0), v1 = scr_patch_read(16 * which, 16);
-#ifdef RC_DBG_NOSTORE
-    asm volatile("" :: "v"(v0), "v"(v1));
-    return;
-#endif
-    const int growb = u_row0 + 16 * which;
-    __bf16* const base = img + (size_t)(growb >> 5) * ((size_t)img_cols * 32) + (size_t)((growb >> 4) & 1) * ((size_t)img_cols * 16) + (size_t)col0 * 16;
-    if constexpr (FULL) { patch_store(v0, pl, base, 16); patch_store(v1, pl, base + 256, 16); }
-    else if ((growb & ~31) < N) {
-      const int rv = min(max(N - growb, 0), 16);
-      patch_store(v0, pl, base, rv); patch_store(v1, pl, base + 256, rv);
-    }
-  };
-  if constexpr (SAVE) {
-    // the encoding as a transposed image [tile][half][96 columns][16 rows]: three passes of 32 columns through the scratch
-#pragma unroll
-    for (int pass = 0; pass < 3; ++pass) {
-#pragma unroll
-      for (int g = 0; g < G; ++g)
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-          typedef short s16x8 __attribute__((ext_vector_type(8)));
-          const s16x8 f8 = __builtin_bit_cast(s16x8, pe[g][2 * pass + k2]);       // lane (m, h): columns 16 (2 pass + k2) + 8 h + 0..7
-          const s16x4 a4 = {f8[0], f8[1], f8[2], f8[3]}, b4 = {f8[4], f8[5], f8[6], f8[7]};
-          scr_write4(32 * g + m, 16 * k2 + 8 * h, a4);
-          scr_write4(32 * g + m, 16 * k2 + 8 * h + 4, b4);
-        }
-#pragma unroll
-      for (int which = 0; which < NP; ++which) image_store(peT, EMBP, 32 * pass, which);
-    }
-  }
-  uint32_t gw[G][4];                                 // SAVE: this lane's ReLU gates of the layer, [row group][word]
-#ifdef RC_L2
-  int l2_off[4];                                     // element offset of this lane's 8-byte piece of column group q inside a 16-row image tile
-  __bf16* const actsT_l2 = actsT;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) l2_off[q] = (m >> 4) * 4096 + h * 64 + (((m & 15) + 4 * q) & 15) * 4;
-#endif
   typedef float f32x4v __attribute__((ext_vector_type(4)));
   auto to_acc_file = [](bf16x8 v) -> bf16x8 {
     typedef int i32x4v __attribute__((ext_vector_type(4)));
@@ -1317,73 +1214,19 @@ __device__ __forceinline__ void mlp_fwd_rc_body(unsigned char* __restrict__ ring
   // layer finishes inside the first block of the next layer (its fragments are K-steps 14 / 15 there: needed last).
   f32x16 acc[2][G];
   // piece p = 2 g + s2 of the epilogue of the block in acc[slot]: fragment (g, K-step 2 nb + s2) of `out`
-  auto epi_piece = [&](auto out_acc_c, bf16x8 (&out)[G][16], int slot, int nb, int p, int l) {
+  auto epi_piece = [&](auto out_acc_c, bf16x8 (&out)[G][16], int slot, int nb, int p) {
     constexpr bool OUT_ACC = decltype(out_acc_c)::value;
     const int g = p >> 1, s2 = p & 1;
     const f32x16& a = acc[slot][g];
     const s16x4 lo = relu_bf16x4(a[8 * s2], a[8 * s2 + 1], a[8 * s2 + 2], a[8 * s2 + 3]);
     const s16x4 hi = relu_bf16x4(a[8 * s2 + 4], a[8 * s2 + 5], a[8 * s2 + 6], a[8 * s2 + 7]);
-#ifdef RC_L2
-    if constexpr (SAVE) {
-      // TIMING EXPERIMENT (profiles/r6_ab_experiments.txt): image layout [row/16][col/4][rotated row%16][col%4] written straight from the
-      // registers (two 8-byte stores per piece), gate bits by four packed minima + shifts
-      typedef unsigned u2v_ __attribute__((ext_vector_type(2)));
-      const u2v_ ul = __builtin_bit_cast(u2v_, lo), uh = __builtin_bit_cast(u2v_, hi);
-      unsigned t0, t1, t2, t3;
-      asm("v_pk_min_u16 %0, %1, %2" : "=v"(t0) : "v"(ul.x), "s"(0x00010001u));
-      asm("v_pk_min_u16 %0, %1, %2" : "=v"(t1) : "v"(ul.y), "s"(0x00010001u));
-      asm("v_pk_min_u16 %0, %1, %2" : "=v"(t2) : "v"(uh.x), "s"(0x00010001u));
-      asm("v_pk_min_u16 %0, %1, %2" : "=v"(t3) : "v"(uh.y), "s"(0x00010001u));
-      const uint32_t w8 = t0 | (t1 << 1) | (t2 << 2) | (t3 << 3);
-      const int pp = 2 * (nb & 1) + s2;
-      if (pp == 0) gw[g][nb >> 1] = w8; else gw[g][nb >> 1] |= w8 << (4 * pp);
-      __bf16* const img = actsT_l2 + (size_t)l * tiles * (MW * 32) + (size_t)((u_row0 >> 4) + 2 * g) * 4096 + (size_t)(8 * nb + 4 * s2) * 64;
-#if defined(RC_DBG_L2_NOSTORE)
-      asm volatile("" :: "v"(ul), "v"(uh), "v"(img));
-#elif defined(RC_DBG_L2_PLAIN)
-      *reinterpret_cast<u2v_*>(img + l2_off[2 * s2]) = ul;
-      *reinterpret_cast<u2v_*>(img + 128 + l2_off[2 * s2 + 1]) = uh;
-#else
-      __builtin_nontemporal_store(ul, reinterpret_cast<u2v_*>(img + l2_off[2 * s2]));
-      __builtin_nontemporal_store(uh, reinterpret_cast<u2v_*>(img + 128 + l2_off[2 * s2 + 1]));
-#endif
-    }
-#else
-    if constexpr (SAVE) {
-      // registers 4 q + j (q = 2 s2, 2 s2 + 1) <-> columns 32 nb + 8 q + 4 h + j: gate bits as in mlp_fwd_blk_body (word nb / 2, bit
-      // (nb & 1) 16 + 4 q + j of the (row, h) record), and the block's [row][column] image for the transposing reads
-      const uint32_t b8 = gate_bits4(lo) | (gate_bits4(hi) << 4);
-      const uint32_t sh = b8 << ((nb & 1) * 16 + 8 * s2);
-      if ((nb & 1) == 0 && s2 == 0) gw[g][nb >> 1] = sh; else gw[g][nb >> 1] |= sh;
-      scr_write4(32 * g + m, 16 * s2 + 4 * h, lo);
-      scr_write4(32 * g + m, 16 * s2 + 8 + 4 * h, hi);
-    }
-#endif
     typedef short s16x8 __attribute__((ext_vector_type(8)));
     const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     if constexpr (OUT_ACC) out[g][2 * nb + s2] = to_acc_file(__builtin_bit_cast(bf16x8, v));
     else out[g][2 * nb + s2] = __builtin_bit_cast(bf16x8, v);
   };
-  // SAVE: what follows the four pieces of a block -- `w` = 0..3: the image patches of row patch w (the block is in the scratch);
-  // after the last block of a layer also the layer's gate words
-  auto epi_image = [&](int l, int nb, int w) {
-    if constexpr (SAVE) {
-#ifndef RC_L2
-      image_store(actsT + (size_t)l * tiles * (MW * 32), MW, 32 * nb, w);
-#endif
-      if (nb == 7 && w == NP - 1) {
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-          const int grow = row0 + 32 * g + m;
-          if (FULL || grow < N)
-            *reinterpret_cast<uint4*>(gates + (((size_t)l * N + grow) * 2 + h) * 4) = make_uint4(gw[g][0], gw[g][1], gw[g][2], gw[g][3]);
-        }
-      }
-    }
-  };
   // one layer: IN -> OUT.  PE_KS encoding K-steps first (layers 0 and 5), then HID hidden K-steps out of `in`.
-  // `pending(step)`: the previous layer's last block (its output bank is THIS layer's input: K-steps 14, 15) -- steps 0..3 its
-  // epilogue pieces, 4..7 (SAVE) its image patches
+  // `pending(step)`: epilogue piece `step` of the previous layer's last block (its output bank is THIS layer's input: K-steps 14, 15)
   auto layer = [&](auto l_c, auto out_acc_c, bf16x8 (&in)[G][16], bf16x8 (&out)[G][16], auto&& pending) {
     constexpr int L = decltype(l_c)::value;
     constexpr int PE_KS = (L == 0 || L == SKIP) ? RC_PE_KS : 0, HID = L == 0 ? 0 : 16, KS = PE_KS + HID;
@@ -1400,8 +1243,7 @@ __device__ __forceinline__ void mlp_fwd_rc_body(unsigned char* __restrict__ ring
       const int slot = nb & 1;
       auto prev = [&](int step) {                 // the block before this one
         if (nb == 0) pending(step);
-        else if (step < NP) epi_piece(out_acc_c, out, slot ^ 1, nb - 1, step, L);
-        else epi_image(L, nb - 1, step - NP);
+        else epi_piece(out_acc_c, out, slot ^ 1, nb - 1, step);
       };
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
@@ -1413,37 +1255,30 @@ __device__ __forceinline__ void mlp_fwd_rc_body(unsigned char* __restrict__ ring
           const bf16x8 a = ks < PE_KS ? pe_frag(g, ks < PE_KS ? ks : 0) : in[g][ks >= PE_KS ? ks - PE_KS : 0];
           acc[slot][g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, a, ks == 0 ? binit : acc[slot][g], 0, 0, 0);
         }
-        // the previous block's epilogue: one piece per K-step 1..4; SAVE: its image patches behind K-steps 6..9 (a short
-        // block -- layer 0: six K-steps -- takes all four behind its last one)
-        if (ks >= 1 && ks <= NP) prev(ks - 1);
-        if (SAVE && KS >= 10 && ks >= 6 && ks < 6 + NP) prev(NP + ks - 6);
-        if (SAVE && KS < 10 && ks == KS - 1) {
-          prev(NP); prev(NP + 1);
-          if constexpr (G == 2) { prev(NP + 2); prev(NP + 3); }
-        }
+        if (ks >= 1 && ks <= NP) prev(ks - 1);    // the previous block's epilogue: one piece per K-step 1..4
       }
     }
   };
   auto none = [](int) {};
   constexpr std::true_type ACC{};
   constexpr std::false_type ARCH{};
-  // the last block (7, in acc[1]) of layer l, whose output bank is `out`
-  auto last_of = [&](auto out_acc_c, bf16x8 (&out)[G][16], int l) {
-    return [&, l, out_acc_c](int step) { if (step < NP) epi_piece(out_acc_c, out, 1, 7, step, l); else epi_image(l, 7, step - NP); };
+  // the last block (7, in acc[1]) of a layer whose output bank is `out`
+  auto last_of = [&](auto out_acc_c, bf16x8 (&out)[G][16]) {
+    return [&, out_acc_c](int step) { epi_piece(out_acc_c, out, 1, 7, step); };
   };
   // bankA: accumulation file, bankB: architectural file
   layer(std::integral_constant<int, 0>{}, ACC, bankB, bankA, none);
-  layer(std::integral_constant<int, 1>{}, ARCH, bankA, bankB, last_of(ACC, bankA, 0));
-  layer(std::integral_constant<int, 2>{}, ACC, bankB, bankA, last_of(ARCH, bankB, 1));
-  layer(std::integral_constant<int, 3>{}, ARCH, bankA, bankB, last_of(ACC, bankA, 2));
-  layer(std::integral_constant<int, 4>{}, ACC, bankB, bankA, last_of(ARCH, bankB, 3));
-  layer(std::integral_constant<int, 5>{}, ARCH, bankA, bankB, last_of(ACC, bankA, 4));
-  layer(std::integral_constant<int, 6>{}, ACC, bankB, bankA, last_of(ARCH, bankB, 5));
-  layer(std::integral_constant<int, 7>{}, ARCH, bankA, bankB, last_of(ACC, bankA, 6));
+  layer(std::integral_constant<int, 1>{}, ARCH, bankA, bankB, last_of(ACC, bankA));
+  layer(std::integral_constant<int, 2>{}, ACC, bankB, bankA, last_of(ARCH, bankB));
+  layer(std::integral_constant<int, 3>{}, ARCH, bankA, bankB, last_of(ACC, bankA));
+  layer(std::integral_constant<int, 4>{}, ACC, bankB, bankA, last_of(ARCH, bankB));
+  layer(std::integral_constant<int, 5>{}, ARCH, bankA, bankB, last_of(ACC, bankA));
+  layer(std::integral_constant<int, 6>{}, ACC, bankB, bankA, last_of(ARCH, bankB));
+  layer(std::integral_constant<int, 7>{}, ARCH, bankA, bankB, last_of(ACC, bankA));
   {
-    auto fin = last_of(ARCH, bankB, 7);             // (the last layer's last block: nothing left to hide it behind)
+    auto fin = last_of(ARCH, bankB);                // (the last layer's last block: nothing left to hide it behind)
 #pragma unroll
-    for (int st_ = 0; st_ < (SAVE ? 2 * NP : NP); ++st_) fin(st_);
+    for (int st_ = 0; st_ < NP; ++st_) fin(st_);
   }
   // heads: one 32-wide output block (10 used) out of bankB
   f32x16 hacc[G];
@@ -1466,9 +1301,8 @@ __device__ __forceinline__ void mlp_fwd_rc_body(unsigned char* __restrict__ ring
   // the ten outputs of a row sit in two lanes (h = 0: outputs 0-3, 8, 9; h = 1: 4-7): see mlp_fwd_blk_body
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    int grow = row0 + 32 * g + m;
+    const int grow = row0 + 32 * g + m;
     const bool ok = grow < N;
-    if (ok && ro) grow = ro[grow];
     float o[6];
 #pragma unroll
     for (int r = 0; r < 6; ++r) o[r] = hacc[g][r];
@@ -1493,47 +1327,7 @@ void mlp_fwd_rc_kernel(RcNet net, const float* __restrict__ x, const float* __re
   __shared__ __attribute__((aligned(1024))) unsigned char ring[RC_SLOTS * RC_G * 1024];      // 48 KiB
   __shared__ __attribute__((aligned(16))) float s_bias[MD * MW + HEADP];
   __shared__ __attribute__((aligned(1024))) unsigned char pe_store[4 * 2 * RC_PE_KS * 1024];  // per wave: 12 encoding fragments
-  mlp_fwd_rc_body<false, false>(ring, s_bias, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, nullptr, pe_store);
-}
-
-
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void mlp_fwd_train_rc_kernel(RcNet net, const float* __restrict__ x, const float* __restrict__ t, int t_stride, int N,
-                             float* __restrict__ d_xyz, float* __restrict__ d_rot, float* __restrict__ d_scale,
-                             __bf16* __restrict__ actsT, uint4* __restrict__ gates, const int* __restrict__ ro, __bf16* __restrict__ peT) {
-  __shared__ __attribute__((aligned(1024))) unsigned char ring[RC_SLOTS * RC_G * 1024];      // 48 KiB
-  __shared__ __attribute__((aligned(16))) float s_bias[MD * MW + HEADP];
-  __shared__ __attribute__((aligned(64))) unsigned char scratch[4 * 4096];                   // per wave: 64 rows x 64 bytes
-  __shared__ __attribute__((aligned(1024))) unsigned char pe_store[4 * 2 * RC_PE_KS * 1024];
-  if ((int)(blockIdx.x + 1) * RC_ROWS <= N)
-    mlp_fwd_rc_body<true, true>(ring, s_bias, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, ro, pe_store, scratch, actsT, reinterpret_cast<uint32_t*>(gates), peT);
-  else
-    mlp_fwd_rc_body<true, false>(ring, s_bias, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, ro, pe_store, scratch, actsT, reinterpret_cast<uint32_t*>(gates), peT);
-}
-
-
-// G = 1: eight waves of 32 rows, two per SIMD
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void mlp_fwd_rc1_kernel(RcNet net, const float* __restrict__ x, const float* __restrict__ t, int t_stride, int N,
-                        float* __restrict__ d_xyz, float* __restrict__ d_rot, float* __restrict__ d_scale) {
-  __shared__ __attribute__((aligned(1024))) unsigned char ring[RC_SLOTS * RC_G * 1024];
-  __shared__ __attribute__((aligned(16))) float s_bias[MD * MW + HEADP];
-  __shared__ __attribute__((aligned(1024))) unsigned char pe_store[8 * RC_PE_KS * 1024];
-  mlp_fwd_rc_body<false, false, 1>(ring, s_bias, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, nullptr, pe_store);
-}
-
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void mlp_fwd_train_rc1_kernel(RcNet net, const float* __restrict__ x, const float* __restrict__ t, int t_stride, int N,
-                              float* __restrict__ d_xyz, float* __restrict__ d_rot, float* __restrict__ d_scale,
-                              __bf16* __restrict__ actsT, uint4* __restrict__ gates, const int* __restrict__ ro, __bf16* __restrict__ peT) {
-  __shared__ __attribute__((aligned(1024))) unsigned char ring[RC_SLOTS * RC_G * 1024];
-  __shared__ __attribute__((aligned(16))) float s_bias[MD * MW + HEADP];
-  __shared__ __attribute__((aligned(64))) unsigned char scratch[8 * 2048];                   // per wave: 32 rows x 64 bytes
-  __shared__ __attribute__((aligned(1024))) unsigned char pe_store[8 * RC_PE_KS * 1024];
-  if ((int)(blockIdx.x + 1) * RC_ROWS <= N)
-    mlp_fwd_rc_body<true, true, 1>(ring, s_bias, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, ro, pe_store, scratch, actsT, reinterpret_cast<uint32_t*>(gates), peT);
-  else
-    mlp_fwd_rc_body<true, false, 1>(ring, s_bias, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, ro, pe_store, scratch, actsT, reinterpret_cast<uint32_t*>(gates), peT);
+  mlp_fwd_rc_body(ring, s_bias, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, pe_store);
 }
 
 static size_t mlp_rc_ws_bytes() {
@@ -1548,17 +1342,8 @@ static size_t mlp_ws_bytes_blk() {
   b += align_up(sizeof(__bf16) * (size_t)HEADP * MW) + align_up(sizeof(float) * HEADP);
   return b;
 }
-// both organisations' packed weights fit (the block kernels' first, the RC stream behind them): TRASE_MLP_RC switches per call
+// one forward workspace for both entry points: the training forward's block packing first, the inference RC stream behind it
 static size_t mlp_ws_bytes() { return mlp_ws_bytes_blk() + mlp_rc_ws_bytes(); }
-// TRASE_MLP_RC: 1 (default) = the register-chained INFERENCE kernel of round 6 (0.248 against 0.300 ms at 300k rows), 0 = the block
-// kernel (cross-check / A/B baseline).  TRASE_MLP_RC_TRAIN: 1 = the register-chained TRAINING forward; default 0 -- with the saved
-// state's extra issue slots (scratch stores, gate bits, transposing reads, image stores: ~250 single-issue instructions per 32
-// MFMAs where ~160 hide) it measures 0.50 ms against the block kernel's 0.44 (profiles/r6_ab_experiments.txt)
-static bool mlp_use_rc() { static const bool on = [] { const char* e = getenv("TRASE_MLP_RC"); return !e || atoi(e) != 0; }(); return on; }
-// TRASE_MLP_RC_G: 32-row groups per wave of the RC kernels (2 = four waves, one per SIMD: the default; 1 = eight waves, two per SIMD:
-// inference -1.6 %, training forward 0.51 -> 0.43 ms = the block kernel's time -- profiles/r6_ab_experiments.txt)
-static int mlp_rc_groups() { static const int g = [] { const char* e = getenv("TRASE_MLP_RC_G"); return e ? atoi(e) : 2; }(); return g; }
-static bool mlp_use_rc_train() { static const bool on = [] { const char* e = getenv("TRASE_MLP_RC_TRAIN"); return e && atoi(e) != 0; }(); return on; }
 
 // ---- buffer plans of the training pair ---------------------------------------------------------------------
 struct MlpSaved {            // written by the training forward, read by the backward
@@ -1700,29 +1485,12 @@ int trase_mlp_forward(const TraseMlpWeights* w, const float* x, const float* t, 
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   if (w->is_blender && t_stride != 0) { set_error("trase_mlp_forward: is_blender takes the timenet output (30 floats) with t_stride 0"); return TRASE_ERR_INVALID; }
-  if (mlp_use_rc()) {
-    RcNet rnet;
-    if (int rc = mlp_pack_rc(w, ws, rnet, stream)) return rc;
-    if (w->is_blender) rnet.temb = t;
-    {
-      ProfScope ps("mlp_fwd", stream);
-      if (mlp_rc_groups() == 1)
-        hipLaunchKernelGGL(mlp_fwd_rc1_kernel, dim3((N + RC_ROWS - 1) / RC_ROWS), dim3(512), 0, stream, rnet, x, t, t_stride, N, d_xyz, d_rotation, d_scaling);
-      else
-        hipLaunchKernelGGL(mlp_fwd_rc_kernel, dim3((N + RC_ROWS - 1) / RC_ROWS), dim3(256), 0, stream, rnet, x, t, t_stride, N, d_xyz, d_rotation, d_scaling);
-    }
-    TRASE_POST_LAUNCH("mlp_fwd", stream, 0);
-    return TRASE_OK;
-  }
-  MlpNet net;
-  if (int rc = mlp_pack_forward(w, ws, net, stream)) return rc;
-  if (w->is_blender) net.temb = t;                         // t = the 30 timenet outputs shared by all rows
+  RcNet rnet;
+  if (int rc = mlp_pack_rc(w, ws, rnet, stream)) return rc;
+  if (w->is_blender) rnet.temb = t;                        // t = the 30 timenet outputs shared by all rows
   {
     ProfScope ps("mlp_fwd", stream);
-    const dim3 block(MWAVES * WAVE);
-    // block-GEMM organisation: weight slabs staged in LDS once per 128-row workgroup
-    hipLaunchKernelGGL(mlp_fwd_kernel_blk, dim3((N + BROWS - 1) / BROWS), block, 0, stream, net, x, t, t_stride, N, d_xyz,
-                       d_rotation, d_scaling);
+    hipLaunchKernelGGL(mlp_fwd_rc_kernel, dim3((N + RC_ROWS - 1) / RC_ROWS), dim3(256), 0, stream, rnet, x, t, t_stride, N, d_xyz, d_rotation, d_scaling);
   }
   TRASE_POST_LAUNCH("mlp_fwd", stream, 0);
   return TRASE_OK;
@@ -1748,22 +1516,6 @@ int trase_mlp_forward_train_rows(const TraseMlpWeights* w, const float* x, const
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   if (w->is_blender && t_stride != 0) { set_error("trase_mlp_forward_train: is_blender takes the timenet output (30 floats) with t_stride 0"); return TRASE_ERR_INVALID; }
-  if (mlp_use_rc_train()) {
-    RcNet rnet;
-    if (int rc = mlp_pack_rc(w, ws, rnet, stream)) return rc;
-    if (w->is_blender) rnet.temb = t;
-    {
-      ProfScope ps("mlp_fwd_train", stream);
-      if (mlp_rc_groups() == 1)
-        hipLaunchKernelGGL(mlp_fwd_train_rc1_kernel, dim3((N + RC_ROWS - 1) / RC_ROWS), dim3(512), 0, stream, rnet, x, t, t_stride, N,
-                           d_xyz, d_rotation, d_scaling, sv.actsT, sv.gates, (const int*)row_order, sv.peT);
-      else
-        hipLaunchKernelGGL(mlp_fwd_train_rc_kernel, dim3((N + RC_ROWS - 1) / RC_ROWS), dim3(256), 0, stream, rnet, x, t, t_stride, N,
-                           d_xyz, d_rotation, d_scaling, sv.actsT, sv.gates, (const int*)row_order, sv.peT);
-    }
-    TRASE_POST_LAUNCH("mlp_fwd_train", stream, 0);
-    return TRASE_OK;
-  }
   MlpNet net;
   if (int rc = mlp_pack_forward(w, ws, net, stream)) return rc;
   if (w->is_blender) net.temb = t;
