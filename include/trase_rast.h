@@ -602,6 +602,28 @@ int trase_segment_mask_sizes(int32_t N, int32_t D, int32_t S, size_t* ws_bytes);
 int trase_segment_mask(const float* X, int32_t N, int32_t D, const int32_t* ids, const int32_t* sel, int32_t S, float threshold,
                        uint8_t* mask_out, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
 
+/* ---- prompt lift: a 2D prompt to cluster votes (render.py:208-229, gui.py:1039-1064; a clicked pixel: gui.py:786-800) -----
+ * For every prompted pixel (row r, column c, depth d = depth[r * W + c]; depth is the (H, W) fp32 map the rasterizer wrote):
+ *     z = zfar / (zfar - znear) * d - zfar * znear / (zfar - znear)
+ *     p = ([((c - 0.5) / W * 2 - 1) * d, ((r - 0.5) / H * 2 - 1) * d, z, d] @ inv_proj)[:3]     (no homogeneous division)
+ *   inv_proj is a HOST pointer to the 16 doubles (row-major, row-vector convention) of inverse(full_proj_transform), inverted
+ *   in float64 by the caller.  z is folded into rows 2 and 3 of it in float64 before the kernel's coefficients are rounded to
+ *   fp32 (the two rows cancel by a factor of about d / znear), and the kernel evaluates p in float64 and rounds it.  The nearest of the N `points` (fp32
+ *   (N, 3), exact, ties to the lowest index) gives j; votes_out[cluster_ids[j]] += 1 for 0 <= cluster_ids[j] < bins (int32
+ *   ids; a negative id casts no vote).  A pixel of depth 0 still votes; a pixel whose point is not finite finds nothing.
+ *   Prompt, one of: prompt_mask (H * W bytes, non-zero = prompted; pixels must be NULL), or pixels (M (col, row) int32 pairs;
+ *   prompt_mask NULL; a pair outside the image finds nothing).
+ *   Outputs: votes_out (bins int32, zeroed here; integer atomics, so bitwise reproducible); optional index_out (int32, H * W
+ *   for a mask -- -1 where not prompted -- or M for a pixel list) and points_out (fp32, 3 per entry of index_out, 0 where
+ *   not prompted).  bins = 0 with cluster_ids = votes_out = NULL only looks the indices up.  N = 0: no hash is built, every
+ *   index is -1 and no vote is cast; M = 0: nothing is launched but the zeroing of votes_out.
+ *   Limits: 0 <= bins <= 4096 (the per-block LDS histogram), W * H < 2^31.  Workspace: trase_lift_sizes(N, bins). */
+int trase_lift_sizes(int32_t N, int32_t bins, size_t* ws_bytes);
+int trase_lift_votes(const float* depth, int32_t W, int32_t H, const double* inv_proj, double znear, double zfar,
+                     const uint8_t* prompt_mask, const int32_t* pixels, int32_t M, const float* points, int32_t N,
+                     const int32_t* cluster_ids, int32_t bins, int32_t* votes_out, int32_t* index_out, float* points_out,
+                     void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

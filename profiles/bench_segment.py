@@ -3,9 +3,13 @@
 N = 300k Gaussians with D = 32 features -- the HIP Lloyd loop of trase_amd/segment.py against the float64-checked torch
 restatement of kmeans_pytorch 0.3's loop (tests/segment_reference.py: an N x K x D broadcast and K nonzero host syncs per
 iteration), both on the same GPU in the same process, alternating, with a fixed iteration count (iter_limit = 30,
-tol = 0) so both do equal work; and segment_mask at S = 3 against the render.py per-id composition.
+tol = 0) so both do equal work; segment_mask at S = 3 against the render.py per-id composition; and the prompt lift
+(``lift_votes``: one fused pass over the hash of the points) against the composition of render.py:208-231 around this
+repository's ``knn_points`` shim at K = 1, at 300k points and 1080p for prompt masks of 1 %, 10 % and 100 % of the image
+(the scene of tests/test_gpu_lift.py), alternating the two.
 
     python profiles/bench_segment.py                          # one JSON line
+    python profiles/bench_segment.py --lift-only              # only the "lift" rows
     python profiles/bench_segment.py --profile-k 16           # only the HIP steps at K = 16 (run under rocprofv3)
     python profiles/bench_segment.py --kernel-stats 16=a.csv --kernel-stats 64=b.csv
         # adds bytes per step over the step kernels' time from `rocprofv3 --kernel-trace --stats` runs of --profile-k
@@ -80,13 +84,63 @@ def kernel_us_per_step(path):
     return (total_ns / steps / 1e3 if steps else None), steps
 
 
+def lift_composition(depth, text_mask, view, xyz, cluster_ids_x, threshold):
+    """render.py:208-231 as torch ops on the device around the knn_points shim: what a user composed before lift_votes."""
+    from pytorch3d.ops import knn_points
+    depth = depth.squeeze()
+    h, w = depth.shape
+    grid_index = torch.stack(torch.meshgrid([torch.arange(h), torch.arange(w)], indexing="ij"), dim=-1).to(depth.device)
+    z = view.zfar / (view.zfar - view.znear) * depth[text_mask] - view.zfar * view.znear / (view.zfar - view.znear)
+    uvz = torch.cat(((((grid_index[text_mask, :][:, 1] - 0.5) / view.image_width * 2 - 1) * depth[text_mask]).unsqueeze(-1),
+                     (((grid_index[text_mask, :][:, 0] - 0.5) / view.image_height * 2 - 1) * depth[text_mask]).unsqueeze(-1),
+                     z.unsqueeze(-1), depth[text_mask].unsqueeze(-1)), 1)
+    points = uvz @ (torch.inverse(view.full_proj_transform))[:, :3]
+    ijs = knn_points(points.unsqueeze(0), xyz.unsqueeze(0), K=1).idx.squeeze(0).squeeze(-1)
+    votes = torch.bincount(cluster_ids_x[ijs].int())
+    return votes, torch.where(votes > threshold, 1, 0).nonzero()
+
+
+def lift_rows(dev, reps):
+    from tests.test_gpu_lift import K_FULL, _blob, _full_scene
+    cam, depth, points, ids, (rr, cc) = _full_scene()
+    cam, depth, points, ids = cam.to(dev), depth.to(dev), points.to(dev), ids.to(dev)
+    rows = {"n": int(points.shape[0]), "image": [cam.image_width, cam.image_height], "bins": K_FULL}
+    for share in (0.01, 0.10, 1.0):
+        mask = torch.from_numpy(_blob(rr, cc, share)).to(dev)
+        threshold = int(mask.sum()) // (2 * K_FULL)
+        fused = lambda: segment.prompt_clusters(depth, mask, cam, points, ids, threshold, num_clusters=K_FULL)   # noqa: E731
+        composed = lambda: lift_composition(depth, mask, cam, points, ids.float(), threshold)                    # noqa: E731
+        a, (v, b) = fused(), composed()
+        torch.cuda.synchronize()
+        hip, ref = [], []
+        for _ in range(reps):       # alternating
+            for fn, out in ((fused, hip), (composed, ref)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                out.append((time.perf_counter() - t0) * 1e3)
+        hip_ms, ref_ms = sorted(hip)[len(hip) // 2], sorted(ref)[len(ref) // 2]
+        votes = segment.lift_votes(depth, mask, cam, points, ids, num_clusters=K_FULL)
+        rows[f"mask_{int(round(share * 100))}pct"] = {
+            "prompted_pixels": int(mask.sum()), "lift_votes_ms": round(hip_ms, 4), "torch_render_py_knn_shim_ms": round(ref_ms, 4),
+            "speedup": round(ref_ms / hip_ms, 1), "min_ms": [round(min(hip), 4), round(min(ref), 4)],
+            "votes_differing_from_composition": int((votes[:v.numel()] != v).sum()),
+            "chosen_ids_equal": bool(torch.equal(a, b.flatten()))}
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--lift-only", action="store_true")
     ap.add_argument("--profile-k", type=int, default=0)
     ap.add_argument("--kernel-stats", action="append", default=[])
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.lift_only:
+        print(json.dumps({"lift": lift_rows(dev, max(a.reps, 11))}))
+        return
     X = features(dev)
     if a.profile_k:
         run = step_loop(X, a.profile_k)
@@ -130,6 +184,7 @@ def main():
     t_ref = timed(lambda: sr.render_masks_torch(X, ids16, sel, thr), 20)
     res["segment_mask_s3"] = {"score_threshold": thr, "hip_ms": round(t_hip, 4), "torch_render_py_ms": round(t_ref, 4), "speedup": round(t_ref / t_hip, 1),
                               "selected": int(m_hip.sum()), "mask_bits_differing": int((m_hip != m_ref).sum())}
+    res["lift"] = lift_rows(dev, max(a.reps, 11))
     print(json.dumps(res))
 
 

@@ -221,6 +221,10 @@ SYMBOLS = [
     ("trase_segment_mask_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     ("trase_segment_mask", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p,
                                      C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_lift_sizes", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    ("trase_lift_votes", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double * 16), C.c_double, C.c_double,
+                                   C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     ("trase_adam_step", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_int32, C.c_void_p]),
     ("trase_adam_step_guarded", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -5,6 +5,8 @@
 // bucketed by hash(cell) with the stable radix sort of binning.hip, a query walks cube shells of
 // cells outwards until the 3rd-best distance is provably final.  Hash collisions only add
 // candidates that are filtered by their true cell, so the result is exact for any cell size.
+// The same hash serves pytorch3d.ops.knn_points (knn_points_kernel) and the prompt lift (lift_kernel: 2D prompt ->
+// nearest Gaussian -> cluster votes; trase_lift_votes).
 #include "common.h"
 
 namespace trase {
@@ -168,23 +170,18 @@ __global__ __launch_bounds__(256) void knn_query_kernel(const float* __restrict_
   out[self] = cnt ? sum / 3.0f : 0.f;
 }
 
-// top-KT nearest points of the hashed cloud `pts` for every query point; ascending, squared distance
+// The shell walk of one query (x, y, z) over the hashed cloud `pts`: on return bd / bi hold the KT nearest points,
+// ascending, squared distances (3.0e38f where the cloud has fewer).  `out2` is a lower bound of the squared distance from
+// the query to the cloud's bounding box (0 for a query inside it; 0 is always valid): a cell outside shell r is at least
+// r*h away along one axis and the box at least its own distance along the others, so the walk of a query outside the box
+// may end as soon as bd[KT - 1] <= (r*h)^2 + out2 instead of crossing the whole grid.
 template <int KT>
-__global__ __launch_bounds__(256) void knn_points_kernel(const float* __restrict__ qpts, int nq,
-                                                         const float* __restrict__ pts, int n, int K,
-                                                         const KnnParams* pp, uint32_t mask,
-                                                         const uint32_t* __restrict__ sorted_ids,
-                                                         const uint2* __restrict__ buckets,
-                                                         int64_t* __restrict__ idx_out, float* __restrict__ dist_out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nq) return;
-  const KnnParams p = *pp;
-  const float x = qpts[3 * i], y = qpts[3 * i + 1], z = qpts[3 * i + 2];
+__device__ __forceinline__ void knn_walk(const KnnParams& p, float x, float y, float z, float out2,
+                                         const float* __restrict__ pts, uint32_t mask,
+                                         const uint32_t* __restrict__ sorted_ids, const uint2* __restrict__ buckets,
+                                         float (&bd)[KT], uint32_t (&bi)[KT]) {
   int cx, cy, cz;
   cell_of(p, x, y, z, cx, cy, cz);
-  // distance from the query to its (clamped) cell: queries outside the cloud's box start farther away
-  float bd[KT];
-  uint32_t bi[KT];
 #pragma unroll
   for (int k = 0; k < KT; ++k) { bd[k] = 3.0e38f; bi[k] = 0u; }
   const int rmax = max(p.dims[0], max(p.dims[1], p.dims[2]));
@@ -222,9 +219,25 @@ __global__ __launch_bounds__(256) void knn_points_kernel(const float* __restrict
         }
       }
     const float bound = (float)r * p.h;
-    if (bd[KT - 1] <= bound * bound && r > 0) break;
+    if (bd[KT - 1] <= bound * bound + out2 && r > 0) break;
     if (KT == 1 && bd[0] == 0.0f) break;
   }
+}
+
+// top-KT nearest points of the hashed cloud `pts` for every query point; ascending, squared distance
+template <int KT>
+__global__ __launch_bounds__(256) void knn_points_kernel(const float* __restrict__ qpts, int nq,
+                                                         const float* __restrict__ pts, int n, int K,
+                                                         const KnnParams* pp, uint32_t mask,
+                                                         const uint32_t* __restrict__ sorted_ids,
+                                                         const uint2* __restrict__ buckets,
+                                                         int64_t* __restrict__ idx_out, float* __restrict__ dist_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nq) return;
+  const KnnParams p = *pp;
+  float bd[KT];
+  uint32_t bi[KT];
+  knn_walk<KT>(p, qpts[3 * i], qpts[3 * i + 1], qpts[3 * i + 2], 0.0f, pts, mask, sorted_ids, buckets, bd, bi);
 #pragma unroll
   for (int k = 0; k < KT; ++k) {
     if (k < K) {
@@ -232,6 +245,101 @@ __global__ __launch_bounds__(256) void knn_points_kernel(const float* __restrict
       idx_out[(size_t)i * K + k] = have ? (int64_t)bi[k] : 0;
       dist_out[(size_t)i * K + k] = have ? bd[k] : 0.0f;
     }
+  }
+}
+
+// ---- prompt lift: 2D prompts to cluster votes (render.py:208-229, gui.py:1039-1064; one clicked pixel: gui.py:786-800) ----
+// One thread per pixel of a 16 x 16 tile (mask form) or per listed pixel (click form): read the mask and the depth,
+// un-project, walk the hash for the nearest point (knn_walk<1>, everything in registers), read its cluster id, vote.
+// Votes are integer atomics into a per-block LDS histogram, flushed once per block with integer atomics on the non-zero
+// bins: integer sums do not depend on the order, so the result is bitwise reproducible.
+constexpr int LIFT_MAX_BINS = 4096;     // the LDS histogram: 16 KiB of int32
+constexpr int LIFT_TILE = 16;           // a block's unit of work is 16 x 16 pixels: a wave covers 16 x 4 neighbours
+constexpr int LIFT_BLOCK = LIFT_TILE * LIFT_TILE;
+constexpr int LIFT_MAX_BLOCKS = 2048;   // blocks stride over the tiles: one histogram flush per block, not per tile
+
+// p = u * m[0] + v * m[1] + d * m[2] - m[3] with u = ((c - 0.5) * sx - 1) * d, v = ((r - 0.5) * sy - 1) * d, where the host folds
+// z = za * d - zb into rows 2 and 3 of the float64 inverse I before rounding to fp32: m[2] = za * I[2] + I[3], m[3] = zb * I[2].
+// (z * I[2] + d * I[3] cancels about (zfar - znear) / (zfar * znear) * d down to the size of the point: with the rows rounded
+// to fp32 separately their rounding alone moves the point by 2e-4 at d = 6, half of what the reference's fp32 inverse does.)
+struct LiftCam { float m[12]; double sx, sy; };
+
+template <bool CLICK>
+__global__ __launch_bounds__(LIFT_BLOCK) void lift_kernel(const float* __restrict__ depth, const uint8_t* __restrict__ pmask,
+                                                          const int32_t* __restrict__ pixels, int M, int W, int H, LiftCam cam,
+                                                          const float* __restrict__ pts, int n, const KnnParams* pp,
+                                                          uint32_t mask, const uint32_t* __restrict__ sorted_ids,
+                                                          const uint2* __restrict__ buckets, const int32_t* __restrict__ ids,
+                                                          int bins, int* __restrict__ votes, int32_t* __restrict__ idx_out,
+                                                          float* __restrict__ pts_out) {
+  __shared__ int hist[LIFT_MAX_BINS];
+  const int tid = threadIdx.x;
+  for (int b = tid; b < bins; b += LIFT_BLOCK) hist[b] = 0;
+  __syncthreads();
+  KnnParams p = {};
+  float bbmax[3] = {0.f, 0.f, 0.f};
+  if (n > 0) {
+    p = *pp;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) bbmax[k] = ord2f(p.bb[3 + k]);
+  }
+  const int tiles_x = (W + LIFT_TILE - 1) / LIFT_TILE, tiles_y = (H + LIFT_TILE - 1) / LIFT_TILE;
+  const int units = CLICK ? (M + LIFT_BLOCK - 1) / LIFT_BLOCK : tiles_x * tiles_y;
+  for (int unit = blockIdx.x; unit < units; unit += gridDim.x) {
+    int col, row;
+    size_t out;
+    bool listed, on;     // listed: the thread has an output slot;  on: it has a prompted pixel inside the image
+    if (CLICK) {
+      const int q = unit * LIFT_BLOCK + tid;
+      listed = q < M;
+      col = listed ? pixels[2 * q] : 0;
+      row = listed ? pixels[2 * q + 1] : 0;
+      on = listed && col >= 0 && col < W && row >= 0 && row < H;
+      out = (size_t)q;
+    } else {
+      const int ty = unit / tiles_x;
+      col = (unit - ty * tiles_x) * LIFT_TILE + (tid & (LIFT_TILE - 1));
+      row = ty * LIFT_TILE + tid / LIFT_TILE;
+      listed = col < W && row < H;
+      out = (size_t)row * W + col;
+      on = listed && pmask[out] != 0;
+    }
+    int best = -1;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (on) {
+      const double d = (double)depth[(size_t)row * W + col];
+      const double u = (((double)col - 0.5) * cam.sx - 1.0) * d, v = (((double)row - 0.5) * cam.sy - 1.0) * d;
+      x = (float)(u * cam.m[0] + v * cam.m[3] + d * cam.m[6] - cam.m[9]);
+      y = (float)(u * cam.m[1] + v * cam.m[4] + d * cam.m[7] - cam.m[10]);
+      z = (float)(u * cam.m[2] + v * cam.m[5] + d * cam.m[8] - cam.m[11]);
+      if (n > 0 && fabsf(x) < 3.0e38f && fabsf(y) < 3.0e38f && fabsf(z) < 3.0e38f) {   // a NaN / inf depth finds nothing
+        const float q3[3] = {x, y, z};
+        float out2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const float o = fmaxf(fmaxf(p.origin[k] - q3[k], q3[k] - bbmax[k]), 0.f);
+          out2 = fmaf(o, o, out2);
+        }
+        out2 *= 0.9999f;                // the bound must not exceed the true distance to the box: keep it below its rounding
+        float bd[1];
+        uint32_t bi[1];
+        knn_walk<1>(p, x, y, z, out2, pts, mask, sorted_ids, buckets, bd, bi);
+        if (bd[0] < 3.0e38f) best = (int)bi[0];
+      }
+      if (best >= 0 && bins > 0) {
+        const int id = ids[best];
+        if (id >= 0 && id < bins) atomicAdd(&hist[id], 1);     // a negative id (HDBSCAN noise) casts no vote
+      }
+    }
+    if (listed) {
+      if (idx_out) idx_out[out] = best;
+      if (pts_out) { pts_out[3 * out] = x; pts_out[3 * out + 1] = y; pts_out[3 * out + 2] = z; }
+    }
+  }
+  __syncthreads();
+  for (int b = tid; b < bins; b += LIFT_BLOCK) {
+    const int v = hist[b];
+    if (v) atomicAdd(&votes[b], v);
   }
 }
 
@@ -348,6 +456,74 @@ int trase_knn_points(const float* p1, int32_t N1, const float* p2, int32_t N2, i
 #undef TRASE_KQ
   }
   TRASE_POST_LAUNCH("knn_points_query", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_lift_sizes(int32_t N, int32_t bins, size_t* ws_bytes) {
+  if (!ws_bytes || N < 0 || bins < 0 || bins > LIFT_MAX_BINS) {
+    set_error("trase_lift_sizes: need N >= 0, 0 <= bins <= %d (got N %d, bins %d)", LIFT_MAX_BINS, N, bins);
+    return TRASE_ERR_INVALID;
+  }
+  *ws_bytes = knn_ws_bytes(N);
+  return TRASE_OK;
+}
+
+int trase_lift_votes(const float* depth, int32_t W, int32_t H, const double* inv_proj, double znear, double zfar,
+                     const uint8_t* prompt_mask, const int32_t* pixels, int32_t M, const float* points, int32_t N,
+                     const int32_t* cluster_ids, int32_t bins, int32_t* votes_out, int32_t* index_out, float* points_out,
+                     void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  if (N < 0 || bins < 0 || bins > LIFT_MAX_BINS) {
+    set_error("trase_lift_votes: need N >= 0, 0 <= bins <= %d (got N %d, bins %d)", LIFT_MAX_BINS, N, bins);
+    return TRASE_ERR_INVALID;
+  }
+  if (W < 1 || H < 1 || (int64_t)W * H > (int64_t)0x7fffffff || M < 0 || !(zfar != znear)) {
+    set_error("trase_lift_votes: bad arguments (W %d, H %d, M %d, znear %g, zfar %g)", W, H, M, znear, zfar);
+    return TRASE_ERR_INVALID;
+  }
+  const bool click = prompt_mask == nullptr;
+  if (!depth || !inv_proj || (!click && pixels) || (click && M > 0 && !pixels) || (N > 0 && !points) ||
+      (bins > 0 && (!votes_out || (N > 0 && !cluster_ids)))) {
+    set_error("trase_lift_votes: null pointer (or both a mask and a pixel list)");
+    return TRASE_ERR_INVALID;
+  }
+  if (N > 0 && (!ws || ws_bytes < knn_ws_bytes(N))) { set_error("trase_lift_votes: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  if (bins > 0) launch_zero_bytes(votes_out, sizeof(int32_t) * (size_t)bins, stream);
+  if (click && M == 0) return TRASE_OK;
+  LiftCam cam;
+  const double za = zfar / (zfar - znear), zb = zfar * znear / (zfar - znear);
+  for (int k = 0; k < 3; ++k) {
+    cam.m[k] = (float)inv_proj[k];
+    cam.m[3 + k] = (float)inv_proj[4 + k];
+    cam.m[6 + k] = (float)(za * inv_proj[8 + k] + inv_proj[12 + k]);
+    cam.m[9 + k] = (float)(zb * inv_proj[8 + k]);
+  }
+  cam.sx = 2.0 / (double)W;
+  cam.sy = 2.0 / (double)H;
+  LaunchCtx c{stream, 0, 0};
+  KnnWs w = {};
+  uint32_t mask = 0u;
+  int idx = 0;
+  if (N > 0) {          // N == 0: nothing to find -- no hash, every index -1, no votes
+    w = knn_carve(ws, N);
+    const int bits = knn_bits(N);
+    mask = (1u << bits) - 1u;
+    int rc = knn_build(c, points, N, w, mask, bits, &idx);
+    if (rc) return rc;
+  }
+  const int units = click ? (M + LIFT_BLOCK - 1) / LIFT_BLOCK
+                          : ((W + LIFT_TILE - 1) / LIFT_TILE) * ((H + LIFT_TILE - 1) / LIFT_TILE);
+  const int blocks = units < LIFT_MAX_BLOCKS ? units : LIFT_MAX_BLOCKS;
+  {
+    ProfScope ps("lift_votes", stream);
+#define TRASE_LIFT(CLICK) hipLaunchKernelGGL((lift_kernel<CLICK>), dim3(blocks), dim3(LIFT_BLOCK), 0, stream, depth, prompt_mask, \
+                                             pixels, M, W, H, cam, points, N, w.prm, mask, N > 0 ? w.sort.vals[idx] : nullptr, \
+                                             w.buckets, cluster_ids, bins, votes_out, index_out, points_out)
+    if (click) TRASE_LIFT(true); else TRASE_LIFT(false);
+#undef TRASE_LIFT
+  }
+  TRASE_POST_LAUNCH("lift_votes", stream, 0);
   return TRASE_OK;
 }
 
