@@ -624,6 +624,43 @@ int trase_lift_votes(const float* depth, int32_t W, int32_t H, const double* inv
                      const int32_t* cluster_ids, int32_t bins, int32_t* votes_out, int32_t* index_out, float* points_out,
                      void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
 
+/* ---- nearest cluster centre by cosine (gui.py:276 + :288-290, gui_standalone.py:721-727) -----------------------------------
+ * trase_assign_clusters: ids_out[n] (int64) = argmax_k <x_n / |x_n|, c_k> for fp32 features X (N,D) and centres (K,D), both on
+ *   the device, the centres used as given.  Ties go to the lowest k.  The raw dot products are compared (the division by |x_n|
+ *   is common to every k); optional scores_out[n] (fp32) = the winning dot product / max(|x_n|, 1e-12), so a zero row gets
+ *   id 0 and score 0.  Fixed-order fmaf chains: bitwise reproducible.  Limits: 1 <= K <= 4096 (the bin limit of
+ *   trase_lift_votes), 1 <= D <= 64.  Workspace: trase_assign_clusters_sizes(N, D, K) (which validates the limits; 0 bytes
+ *   today, ws may then be NULL). */
+int trase_assign_clusters_sizes(int32_t N, int32_t D, int32_t K, size_t* ws_bytes);
+int trase_assign_clusters(const float* X, int32_t N, int32_t D, const float* centres, int32_t K, int64_t* ids_out,
+                          float* scores_out, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+
+/* ---- display stage: point splats and PCA colours (render.py:247-294, :52-59; gui.py:984-1030, :55-62) ----------------------
+ * trase_splat_points: every point i of `points` (fp32 (N,3), the deformed positions) with mask == NULL or mask[i] != 0 is
+ *   projected in float64, p = [x, y, z, 1] @ full_proj (a HOST pointer to the 16 doubles of full_proj_transform, row-major,
+ *   row-vector convention), px = (p.x / p.w + 1) / 2 * W, py = (p.y / p.w + 1) / 2 * H, and lands at column trunc(px), row
+ *   trunc(py) if 0 < px < W and 0 < py < H (no near-plane or w > 0 test; a non-finite coordinate lands nowhere).  The winner
+ *   of a pixel is the HIGHEST index landing there (integer atomicMax: bitwise reproducible).  For each of the L <= 4 layers
+ *   images_out[l] ((3,H,W) fp32, planar) = colors[l][winner] at hit pixels (colors[l] fp32 (N,3); NULL = the dot colour: 1,
+ *   or 0 with white_background) and the background (0, or 1 with white_background) elsewhere.  `colors` and `images_out` are
+ *   HOST arrays of L device pointers.  Optional index_out (H * W int64): the winner, -1 where no point landed.
+ *   Limits: W * H < 2^31.  Workspace: trase_splat_sizes(N, W, H) (the int32 winner map).
+ * trase_feature_gram: gram_mean_out (device, D * D + D fp32) = the centred Gram matrix Xc^T Xc of X (N,D) fp32, Xc = X - mean,
+ *   then the D column means.  fp32 products and sums within a block, block slabs summed in block order in float64: no float
+ *   atomics, bitwise reproducible.  Limits: N >= 2, 1 <= D <= 64.  Workspace: trase_feature_gram_sizes(N, D).
+ * trase_feature_project: colors_out (N,3) fp32 = ((X - mean) @ axes^T - min) / (max - min), axes (3,D) and mean (D) fp32 on
+ *   the device, min and max taken over all 3 N projections (integer atomics on the ordered-int image of the floats);
+ *   max == min gives 0 / 0 = NaN as render.py:58 does.  minmax: 2 int32 words of device scratch. */
+int trase_splat_sizes(int32_t N, int32_t W, int32_t H, size_t* ws_bytes);
+int trase_splat_points(const float* points, int32_t N, const uint8_t* mask, const double* full_proj, int32_t W, int32_t H,
+                       const float* const* colors, int32_t L, int32_t white_background, float* const* images_out,
+                       int64_t* index_out, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+int trase_feature_gram_sizes(int32_t N, int32_t D, size_t* ws_bytes);
+int trase_feature_gram(const float* X, int32_t N, int32_t D, float* gram_mean_out, void* ws, size_t ws_bytes, int32_t device,
+                       trase_stream_t stream);
+int trase_feature_project(const float* X, int32_t N, int32_t D, const float* axes, const float* mean, float* colors_out,
+                          int32_t* minmax, int32_t device, trase_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -225,6 +225,17 @@ SYMBOLS = [
     ("trase_lift_votes", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double * 16), C.c_double, C.c_double,
                                    C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_assign_clusters_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    ("trase_assign_clusters", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_splat_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    ("trase_splat_points", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double * 16), C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_void_p * 4), C.c_int32, C.c_int32, C.POINTER(C.c_void_p * 4), C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_feature_gram_sizes", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    ("trase_feature_gram", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_feature_project", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.c_void_p]),
     ("trase_adam_step", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_int32, C.c_void_p]),
     ("trase_adam_step_guarded", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

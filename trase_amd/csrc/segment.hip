@@ -21,6 +21,9 @@
 // The query mask reuses launches 1 and 2 with the slots taken from the selected ids instead of the nearest centre
 // (seg_assign_accum_kernel<1>), then scores every member point against its cluster's normalised mean in fp16
 // (seg_mask_kernel).
+//
+// seg_assign_cosine_kernel (gui.py:276 + :288-290) is launch 1a alone with the cosine score in place of the distance and up
+// to 4096 centres, chunked through LDS: the ids of clusters that did not come from K-means.
 #include <hip/hip_fp16.h>
 
 #include "common.h"
@@ -30,6 +33,7 @@ namespace trase {
 constexpr int SEG_TILE = 512;                 // points per tile == threads per block of the assign/accumulate kernel
 constexpr int SEG_WAVES = SEG_TILE / WAVE;    // 8
 constexpr int SEG_MAX_K = 128, SEG_MAX_D = 64, SEG_MAX_S = 128;
+constexpr int SEG_MAX_ASSIGN_K = 4096;         // assign_clusters: the bin limit of the prompt lift (knn.hip)
 constexpr int SEG_MAX_BLOCKS = 256;           // about one block per CU
 constexpr int SEG_LDS_FLOATS = 34816;         // 136 KiB: centres + tile slots + wave slabs (one block per CU)
 constexpr int SEG_RUNS = 16;                  // seg_reduce_kernel: block runs per element
@@ -283,6 +287,70 @@ __global__ __launch_bounds__(256) void seg_mask_kernel(const float* __restrict__
   mask[i] = m;
 }
 
+// gui.py:276 + :288-290: id = argmax_k <x / |x|, c_k> for every row, the centres used as given.  One row per lane, held in
+// registers; the centres go through LDS in chunks of ASSIGN_CHUNK_FLOATS / DP.  The dot product of a row with a centre is four
+// fmaf chains over the dimensions d = 0, 1, 2, 3 (mod 4), added as (s0 + s1) + (s2 + s3); the division by |x| is common to
+// all k, so the raw dot products are compared (strictly: ties go to the lowest k) and only the winner's is divided, by
+// max(|x|, 1e-12) as F.normalize does: a zero row gets id 0 and score 0.
+constexpr int ASSIGN_THREADS = 256;
+constexpr int ASSIGN_CHUNK_FLOATS = 16384;    // 64 KiB of centres per chunk
+
+template <int DP>
+__global__ __launch_bounds__(ASSIGN_THREADS) void seg_assign_cosine_kernel(const float* __restrict__ X, int N, int D, int K,
+                                                                           const float* __restrict__ centres,
+                                                                           int64_t* __restrict__ ids_out, float* __restrict__ scores_out) {
+  __shared__ __attribute__((aligned(16))) float c_lds[ASSIGN_CHUNK_FLOATS];
+  constexpr int KC = ASSIGN_CHUNK_FLOATS / DP;
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * ASSIGN_THREADS + tid;
+  const bool live = i < N;
+  const bool vec4 = (D & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  float x[DP];
+  if (live && vec4) {
+#pragma unroll
+    for (int d = 0; d < DP; d += 4) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (d < D) v = *reinterpret_cast<const float4*>(X + (size_t)i * D + d);
+      x[d] = v.x; x[d + 1] = v.y; x[d + 2] = v.z; x[d + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int d = 0; d < DP; ++d) x[d] = (live && d < D) ? X[(size_t)i * D + d] : 0.f;
+  }
+  float n2 = 0.f;
+#pragma unroll
+  for (int d = 0; d < DP; ++d) n2 = fmaf(x[d], x[d], n2);
+  float best = -__builtin_inff();
+  int bk = 0;
+  for (int k0 = 0; k0 < K; k0 += KC) {
+    const int kc = min(KC, K - k0);
+    __syncthreads();
+    for (int e = tid; e < kc * DP; e += ASSIGN_THREADS) {
+      const int k = e / DP, d = e - k * DP;
+      c_lds[e] = d < D ? centres[(size_t)(k0 + k) * D + d] : 0.f;
+    }
+    __syncthreads();
+    for (int k = 0; k < kc; ++k) {
+      const float4* c4 = reinterpret_cast<const float4*>(c_lds + k * DP);
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+      for (int q = 0; q < DP / 4; ++q) {
+        const float4 c = c4[q];
+        s0 = fmaf(x[4 * q], c.x, s0);
+        s1 = fmaf(x[4 * q + 1], c.y, s1);
+        s2 = fmaf(x[4 * q + 2], c.z, s2);
+        s3 = fmaf(x[4 * q + 3], c.w, s3);
+      }
+      const float dot = (s0 + s1) + (s2 + s3);
+      if (dot > best) { best = dot; bk = k0 + k; }
+    }
+  }
+  if (live) {
+    ids_out[i] = bk;
+    if (scores_out) scores_out[i] = best / fmaxf(sqrtf(n2), 1e-12f);
+  }
+}
+
 }  // namespace trase
 
 using namespace trase;
@@ -396,6 +464,39 @@ int trase_segment_mask(const float* X, int32_t N, int32_t D, const int32_t* ids,
     hipLaunchKernelGGL(seg_mask_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, X, N, D, S, total, slot, threshold, mask_out);
   }
   TRASE_POST_LAUNCH("segment_mask", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_assign_clusters_sizes(int32_t N, int32_t D, int32_t K, size_t* ws_bytes) {
+  if (!ws_bytes || N < 0 || K < 1 || K > SEG_MAX_ASSIGN_K || D < 1 || D > SEG_MAX_D) {
+    set_error("trase_assign_clusters_sizes: need 1 <= K <= %d, 1 <= D <= %d (got N %d, D %d, K %d)", SEG_MAX_ASSIGN_K, SEG_MAX_D, N, D, K);
+    return TRASE_ERR_INVALID;
+  }
+  *ws_bytes = 0;        // the centres go from global memory to LDS directly: nothing to stage
+  return TRASE_OK;
+}
+
+int trase_assign_clusters(const float* X, int32_t N, int32_t D, const float* centres, int32_t K, int64_t* ids_out,
+                          float* scores_out, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  if (N < 0 || K < 1 || K > SEG_MAX_ASSIGN_K || D < 1 || D > SEG_MAX_D) {
+    set_error("trase_assign_clusters: need 1 <= K <= %d, 1 <= D <= %d (got N %d, D %d, K %d)", SEG_MAX_ASSIGN_K, SEG_MAX_D, N, D, K);
+    return TRASE_ERR_INVALID;
+  }
+  if (N == 0) return TRASE_OK;
+  if (!X || !centres || !ids_out) { set_error("trase_assign_clusters: null pointer"); return TRASE_ERR_INVALID; }
+  (void)ws; (void)ws_bytes;
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  const int dp = seg_dpad(D);
+  const dim3 grid((N + ASSIGN_THREADS - 1) / ASSIGN_THREADS), block(ASSIGN_THREADS);
+  {
+    ProfScope ps("assign_clusters", stream);
+    if (dp == 8) hipLaunchKernelGGL((seg_assign_cosine_kernel<8>), grid, block, 0, stream, X, N, D, K, centres, ids_out, scores_out);
+    else if (dp == 16) hipLaunchKernelGGL((seg_assign_cosine_kernel<16>), grid, block, 0, stream, X, N, D, K, centres, ids_out, scores_out);
+    else if (dp == 32) hipLaunchKernelGGL((seg_assign_cosine_kernel<32>), grid, block, 0, stream, X, N, D, K, centres, ids_out, scores_out);
+    else hipLaunchKernelGGL((seg_assign_cosine_kernel<64>), grid, block, 0, stream, X, N, D, K, centres, ids_out, scores_out);
+  }
+  TRASE_POST_LAUNCH("assign_clusters", stream, 0);
   return TRASE_OK;
 }
 

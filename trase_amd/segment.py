@@ -22,6 +22,10 @@ float64 and the un-projection evaluated in float64 (the reference's fp32 ``torch
 points by up to 4e-4 and with them the nearest index of a fraction of a percent of the pixels), and a negative cluster id
 casts no vote where ``torch.bincount`` would raise.
 
+``assign_clusters(features, centres)`` gives every Gaussian the id of its nearest cluster centre by cosine, gui.py:276 +
+:288-290 (gui_standalone.py:721-727, the viewer's DBSCAN mode, where the reference copies all features to the host and runs
+an N x K x D einsum on the CPU), for clusters that are not K-means ones.
+
 Only CUDA tensors are accepted: there is no CPU path."""
 from __future__ import annotations
 
@@ -90,6 +94,41 @@ def kmeans(X: torch.Tensor, num_clusters: int, *, tol: float = 1e-4, iter_limit:
         if int(host[1]):
             break
     return ids.to(torch.int64), centres, int(host[0])
+
+
+ASSIGN_MAX_CENTRES = 4096      # == LIFT_MAX_BINS: the ids go to lift_votes unchanged
+
+
+def assign_clusters(features: torch.Tensor, centres: torch.Tensor, *, return_scores: bool = False):
+    """-> int64 (N,) ``argmax_k <f_n / |f_n|, c_k>`` on the features' device: gui.py:276 + :288-290.  ``features`` is (N, D) or
+    (N, 1, D) fp32, ``centres`` (K, D) on the device or the host, 1 <= K <= 4096, 1 <= D <= 64; the centres are used as given
+    (the viewer normalises them at gui.py:286).  Ties go to the lowest k.  A zero feature row gets id 0 (and score 0, its
+    norm clamped at 1e-12 as ``F.normalize`` does).  With ``return_scores`` also the winning score, fp32 (N,).  The ids can
+    be passed unchanged to ``lift_votes``, ``segment_mask`` and ``display.splat_points``.  Inputs are read, never modified."""
+    if not torch.is_tensor(features) or features.device.type != "cuda":
+        raise RuntimeError("assign_clusters runs on the GPU only (there is no CPU path)")
+    dev = features.device
+    if features.dim() == 3 and features.shape[1] == 1:
+        features = features.squeeze(1)
+    if features.dim() != 2:
+        raise ValueError(f"assign_clusters: features must be (N, D) or (N, 1, D), got {tuple(features.shape)}")
+    X = features.detach().float().contiguous()
+    N, D = X.shape
+    centres = torch.as_tensor(centres)
+    if centres.dim() != 2 or centres.shape[1] != D:
+        raise ValueError(f"assign_clusters: centres must be (K, {D}), got {tuple(centres.shape)}")
+    Cn = centres.detach().to(device=dev, dtype=torch.float32).contiguous()
+    K = Cn.shape[0]
+    lib = _lib.load()
+    sz = C.c_size_t()
+    _lib.check(lib.trase_assign_clusters_sizes(N, D, K, C.byref(sz)), "assign_clusters")      # validates K, D first
+    ws = torch.empty(sz.value, dtype=torch.uint8, device=dev)
+    ids = torch.empty(N, dtype=torch.int64, device=dev)
+    scores = torch.empty(N, dtype=torch.float32, device=dev) if return_scores else None
+    _lib.check(lib.trase_assign_clusters(_lib.ptr(X), N, D, _lib.ptr(Cn), K, _lib.ptr(ids), _lib.ptr(scores),
+                                         _lib.ptr(ws) if sz.value else None, ws.numel(), _device_index(dev), _stream(dev)),
+               "assign_clusters")
+    return (ids, scores) if return_scores else ids
 
 
 def segment_mask(features: torch.Tensor, cluster_ids: torch.Tensor, segment_ids, score_threshold: float = 0.8) -> torch.Tensor:
