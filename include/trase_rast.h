@@ -661,6 +661,32 @@ int trase_feature_gram(const float* X, int32_t N, int32_t D, float* gram_mean_ou
 int trase_feature_project(const float* X, int32_t N, int32_t D, const float* axes, const float* mean, float* colors_out,
                           int32_t* minmax, int32_t device, trase_stream_t stream);
 
+/* ---- HDBSCAN over sampled features: the viewer's default clustering mode (gui.py:271-301, gui_standalone.py:721-727) -------
+ * The two dense all-pairs passes of HDBSCAN for fp32 rows X (n,D) on the device; the hierarchy over the n - 1 tree edges is the
+ * caller's (trase_amd/segment.py).  A squared distance is the fmaf chain over (a_d - b_d)^2 in dimension order, symmetric bit
+ * for bit; no n x n buffer is held.  Limits: 2 <= n <= 65536 (16 + 16 index bits in an edge key), 1 <= D <= 64, 1 <= k <= 64,
+ * k < n.  Workspace of both: trase_hdbscan_sizes(n, D, k).
+ * trase_hdbscan_core: core2_out[i] (fp32) = the SQUARED distance from row i to its k-th nearest OTHER row (the hdbscan
+ *   package's min_samples = k; scikit-learn counts the row itself, so its min_samples is k + 1).
+ * trase_hdbscan_mst: the minimum spanning tree of w(i,j) = max(core2[i], core2[j], |x_i - x_j|^2) by Boruvka rounds with
+ *   64-bit integer atomics on the keys (float bits of w) << 32 | min(i,j) << 16 | max(i,j), a total order on the edges (among
+ *   equal weights the lower index pair wins).  edge_keys_out (n uint64): the n - 1 keys of the tree in slots that depend on
+ *   the data only, and one ~0; sorted ascending they are the edge list in canonical order.  counts_out (18 int32): the
+ *   component count after every round, counts_out[0] = n, the last non-zero entry 1.  Nothing is read by the host; bitwise
+ *   reproducible.
+ * trase_label_centres: centres_out (C,D) fp32, row c = normalize(mean of the rows of X (N,D) with labels[n] == c), the norm
+ *   clamped at 1e-12; labels int32, a label outside [0, C) (noise: -1) belongs nowhere; a label without rows gives NaN.  The
+ *   sums are those of K-means and of the query mask (fixed order, no float atomics).  Limits: 1 <= C <= 4096, 1 <= D <= 64.
+ *   Workspace: trase_label_centres_sizes(N, D, C). */
+int trase_hdbscan_sizes(int32_t n, int32_t D, int32_t k, size_t* ws_bytes);
+int trase_hdbscan_core(const float* X, int32_t n, int32_t D, int32_t k, float* core2_out, void* ws, size_t ws_bytes,
+                       int32_t device, trase_stream_t stream);
+int trase_hdbscan_mst(const float* X, int32_t n, int32_t D, const float* core2, uint64_t* edge_keys_out, int32_t* counts_out,
+                      void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+int trase_label_centres_sizes(int32_t N, int32_t D, int32_t C, size_t* ws_bytes);
+int trase_label_centres(const float* X, int32_t N, int32_t D, const int32_t* labels, int32_t C, float* centres_out, void* ws,
+                        size_t ws_bytes, int32_t device, trase_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,14 @@ SYMBOLS = [
     ("trase_assign_clusters_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     ("trase_assign_clusters", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_hdbscan_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    ("trase_hdbscan_core", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
+                                     C.c_void_p]),
+    ("trase_hdbscan_mst", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_int32, C.c_void_p]),
+    ("trase_label_centres_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    ("trase_label_centres", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_int32, C.c_void_p]),
     ("trase_splat_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     ("trase_splat_points", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double * 16), C.c_int32, C.c_int32,
                                      C.POINTER(C.c_void_p * 4), C.c_int32, C.c_int32, C.POINTER(C.c_void_p * 4), C.c_void_p,

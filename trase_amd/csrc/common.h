@@ -405,6 +405,11 @@ int radix_sort_pairs(const LaunchCtx& c, const SortBufs& t, const uint32_t* n_pt
 // (round 5: gradient rows of stale pair flags -- NaN under TRASE_POISON -- on every graph hit after the first; ROCm 7.0.2)
 int launch_zero_bytes(void* p, size_t bytes, hipStream_t stream);
 int launch_fill_u32(uint32_t* p, uint32_t v, hipStream_t stream);
+// per-label sums and counts of the rows of X (segment.hip; at most LABEL_SUMS_MAX labels per call), for hdbscan.hip
+constexpr int LABEL_SUMS_MAX = 128;
+size_t label_sums_ws_bytes(int N, int D, int S);
+int launch_label_sums(const float* X, int N, int D, const int32_t* ids, const int32_t* sel, int S, void* ws, const float** total_out,
+                      hipStream_t stream);
 int launch_split_pair_ids(const LaunchCtx& c, const uint32_t* sorted, int P, uint32_t* ids0, uint32_t* ids1);
 int radix_passes(int bit_lo, int bit_hi, int digit_bits = 8);
 // The depth sort (round 5).  Default: an order-preserving 27-bit key -- the float32 depth bits ABOVE those of the 0.2 near-cull

@@ -376,6 +376,28 @@ static int seg_launch_accum(int mode, const float* X, int32_t N, int32_t D, int3
   return TRASE_OK;
 }
 
+// The per-label sums of the query mask for callers outside this file (hdbscan.hip: the centres of labelled samples): launches
+// 1 and 2 with the slots taken from `sel` (S <= LABEL_SUMS_MAX labels on the device).  *total_out (inside ws) then holds the
+// S x D sums followed by the S counts.  ws: label_sums_ws_bytes(N, D, S).
+namespace trase {
+size_t label_sums_ws_bytes(int N, int D, int S) { return seg_ws_bytes(N, D, S, true); }
+int launch_label_sums(const float* X, int N, int D, const int32_t* ids, const int32_t* sel, int S, void* ws, const float** total_out,
+                      hipStream_t stream) {
+  static_assert(LABEL_SUMS_MAX == SEG_MAX_S, "label sums go through the query mask's accumulate kernel");
+  const int G = seg_blocks(N), E = seg_slab_floats(S, D);
+  float* slabs = static_cast<float*>(ws);
+  char* p = static_cast<char*>(ws) + align_up(sizeof(float) * (size_t)E * G);
+  float* total = reinterpret_cast<float*>(p);
+  int32_t* slot = reinterpret_cast<int32_t*>(p + align_up(sizeof(float) * (size_t)E));
+  seg_launch_accum(1, X, N, D, S, nullptr, ids, sel, slot, slabs, nullptr, stream);
+  TRASE_POST_LAUNCH("label_sums_accum", stream, 0);
+  hipLaunchKernelGGL(seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, stream, slabs, G, E, total, nullptr);
+  TRASE_POST_LAUNCH("label_sums_reduce", stream, 0);
+  *total_out = total;
+  return TRASE_OK;
+}
+}  // namespace trase
+
 extern "C" {
 
 int trase_kmeans_sizes(int32_t N, int32_t D, int32_t K, size_t* ws_bytes) {

@@ -26,6 +26,12 @@ casts no vote where ``torch.bincount`` would raise.
 :288-290 (gui_standalone.py:721-727, the viewer's DBSCAN mode, where the reference copies all features to the host and runs
 an N x K x D einsum on the CPU), for clusters that are not K-means ones.
 
+``hdbscan(X, ...)`` / ``density_clusters(features)`` are the viewer's default clustering mode, gui.py:271-301: the core
+distances and the minimum spanning tree of the mutual-reachability graph on the device (trase_amd/csrc/hdbscan.hip), the
+hierarchy over the n - 1 edges on the host from one read-back (``hdbscan_hierarchy``, plain numpy).  Deliberate deviations:
+the centres belong to labels 0..C-1 (the reference's loop is off by one), and among exactly equal weights the spanning tree
+follows our edge order.
+
 Only CUDA tensors are accepted: there is no CPU path."""
 from __future__ import annotations
 
@@ -280,3 +286,310 @@ def pick(depth: torch.Tensor, pixels, viewpoint_camera, points: torch.Tensor, *,
     _, index, pts = _lift_call("pick", depth, viewpoint_camera, points, pixels=pixels, want_index=True, want_points=return_points)
     index = index.to(torch.int64)
     return (index, pts) if return_points else index
+
+
+# ---- HDBSCAN: the viewer's default clustering mode (gui.py:271-301, gui_standalone.py:721-727) --------------------------------
+
+HDBSCAN_MAX_POINTS = 65536      # 16 + 16 index bits in an edge key (trase_amd/csrc/hdbscan.hip)
+
+
+def hdbscan_hierarchy(edges, n_points: int, *, min_cluster_size: int = 10, cluster_selection_epsilon: float = 0.0,
+                      allow_single_cluster: bool = False) -> np.ndarray:
+    """Labels, int64 (n_points,), from the n_points - 1 edges ``(i, j, weight)`` of a minimum spanning tree of the
+    mutual-reachability graph: the host half of ``hdbscan``, plain numpy, no GPU.  Noise is -1; the clusters are numbered
+    0..C-1 by their smallest member index.
+
+    Steps, with the behaviour of the ``hdbscan`` package and of scikit-learn's port: (1) the edges are sorted by weight
+    (stably: equal weights keep the order given) and merged into the single-linkage tree by union-find; (2) the tree is
+    condensed at ``min_cluster_size``: a split with both sides that large makes two new clusters, otherwise the small side's
+    points fall out of the cluster at lambda = 1 / distance; (3) stability of a cluster = sum over what leaves it of
+    (lambda - lambda_birth) x size; (4) excess of mass, children before parents: a cluster is kept when its stability is
+    at least the sum of its kept descendants'; (5) the root takes no part unless ``allow_single_cluster``; (6) with an
+    epsilon, a kept cluster born at a distance below it is replaced by its first ancestor born above it (under the root: the
+    last one below it, or the root when a single cluster is allowed); (7) every point takes its nearest kept ancestor."""
+    n = int(n_points)
+    E = np.asarray(edges, dtype=np.float64).reshape(-1, 3)
+    if n < 2 or E.shape[0] != n - 1:
+        raise ValueError(f"hdbscan_hierarchy: {n} points need {n - 1} edges, got {E.shape[0]}")
+    mcs = int(min_cluster_size)
+    if mcs < 2:
+        raise ValueError(f"hdbscan_hierarchy: min_cluster_size must be at least 2, got {mcs}")
+    eps = float(cluster_selection_epsilon)
+    order = np.argsort(E[:, 2], kind="stable")
+    ea = E[order, 0].astype(np.int64).tolist()
+    eb = E[order, 1].astype(np.int64).tolist()
+    ew = E[order, 2].tolist()
+
+    # (1) single linkage: leaves 0..n-1, the k-th merge makes node n + k
+    up = list(range(2 * n - 1))
+    left = [0] * (n - 1)
+    right = [0] * (n - 1)
+    size = [1] * n + [0] * (n - 1)
+
+    def find(x):
+        r = x
+        while up[r] != r:
+            r = up[r]
+        while up[x] != r:
+            up[x], x = r, up[x]
+        return r
+
+    for k in range(n - 1):
+        ra, rb = find(ea[k]), find(eb[k])
+        if ra == rb:
+            raise ValueError("hdbscan_hierarchy: the edges do not form a spanning tree")
+        node = n + k
+        up[ra] = up[rb] = node
+        left[k], right[k] = ra, rb
+        size[node] = size[ra] + size[rb]
+
+    # the leaves below a node as one slice of `leaves`
+    start = [0] * (2 * n - 1)
+    for k in range(n - 2, -1, -1):
+        node = n + k
+        start[left[k]] = start[node]
+        start[right[k]] = start[node] + size[left[k]]
+    leaves = np.empty(n, dtype=np.int64)
+    leaves[np.asarray(start[:n])] = np.arange(n)
+
+    # (2) condensed tree: cluster 0 is the root; a child's id is larger than its parent's
+    c_parent, c_birth, c_size = [-1], [0.0], [n]
+    p_cluster = np.zeros(n, dtype=np.int64)          # the cluster a point falls out of, and at which lambda
+    p_lambda = np.zeros(n, dtype=np.float64)
+    todo = [(2 * n - 2, 0)]
+    while todo:
+        node, c = todo.pop()
+        while node >= n:
+            k = node - n
+            lam = 1.0 / ew[k] if ew[k] > 0.0 else np.inf
+            a, b = left[k], right[k]
+            big_a, big_b = size[a] >= mcs, size[b] >= mcs
+            if big_a and big_b:
+                for child in (a, b):
+                    c_parent.append(c); c_birth.append(lam); c_size.append(size[child])
+                    todo.append((child, len(c_parent) - 1))
+                break
+            for child, big in ((a, big_a), (b, big_b)):
+                if not big:
+                    pts = leaves[start[child]:start[child] + size[child]]
+                    p_cluster[pts] = c
+                    p_lambda[pts] = lam
+            if big_a:
+                node = a
+            elif big_b:
+                node = b
+            else:
+                break
+    nc = len(c_parent)
+    c_parent = np.asarray(c_parent, dtype=np.int64)
+    c_birth = np.asarray(c_birth, dtype=np.float64)
+    c_size = np.asarray(c_size, dtype=np.float64)
+
+    # (3) stabilities
+    stab = np.zeros(nc, dtype=np.float64)
+    np.add.at(stab, p_cluster, p_lambda - c_birth[p_cluster])
+    if nc > 1:
+        np.add.at(stab, c_parent[1:], (c_birth[1:] - c_birth[c_parent[1:]]) * c_size[1:])
+    children = [[] for _ in range(nc)]
+    for c in range(1, nc):
+        children[c_parent[c]].append(c)
+
+    # (4), (5) excess of mass, children first
+    stab = stab.tolist()
+    keep = [False] * nc
+    for c in range(nc - 1, -1 if allow_single_cluster else 0, -1):
+        below = sum(stab[ch] for ch in children[c])
+        if below > stab[c]:
+            stab[c] = below
+        else:
+            keep[c] = True
+    selected = set()
+    stack = [0]
+    while stack:                                     # the topmost kept cluster of every branch
+        c = stack.pop()
+        if keep[c]:
+            selected.add(c)
+        else:
+            stack.extend(children[c])
+
+    # (6) the epsilon rule
+    if eps != 0.0 and nc > 1 and selected != {0}:
+        merged, done = set(), set()
+        for c in sorted(selected):
+            if 1.0 / c_birth[c] >= eps:
+                merged.add(c)
+                continue
+            if c in done:
+                continue
+            top = c
+            while True:
+                parent = int(c_parent[top])
+                if parent == 0:
+                    if allow_single_cluster:
+                        top = 0
+                    break
+                top = parent
+                if 1.0 / c_birth[top] > eps:
+                    break
+            merged.add(top)
+            stack = list(children[top])
+            while stack:
+                d = stack.pop()
+                done.add(d)
+                stack.extend(children[d])
+        selected = merged
+
+    # (7) labels: the nearest selected ancestor of the cluster a point fell out of
+    owner = np.full(nc, -1, dtype=np.int64)
+    for c in range(nc):
+        owner[c] = c if c in selected else (owner[c_parent[c]] if c > 0 else -1)
+    own = owner[p_cluster]
+    if 0 in selected:
+        # a single cluster: only the points that stay to the threshold belong to it
+        if eps != 0.0:
+            threshold = 1.0 / eps
+        else:
+            from_root = p_lambda[p_cluster == 0]
+            threshold = max(from_root.max() if from_root.size else 0.0,
+                            max((c_birth[ch] for ch in children[0]), default=0.0))
+        own = np.where((own == 0) & (p_lambda < threshold), -1, own)
+    labels = np.full(n, -1, dtype=np.int64)
+    members = np.nonzero(own >= 0)[0]
+    if members.size:
+        first = np.full(nc, n, dtype=np.int64)
+        np.minimum.at(first, own[members], members)
+        ids = np.nonzero(first < n)[0]
+        rank = np.empty(nc, dtype=np.int64)
+        rank[ids[np.argsort(first[ids], kind="stable")]] = np.arange(ids.size)
+        labels[members] = rank[own[members]]
+    return labels
+
+
+def _hdbscan_device(X: torch.Tensor, k: int):
+    """The two device passes -> (squared core distances fp32 (n,), int64 (n + 9,): the n edge keys, then the 18 int32
+    component counts), on X's device, nothing read back."""
+    n, D = X.shape
+    lib = _lib.load()
+    sz = C.c_size_t()
+    _lib.check(lib.trase_hdbscan_sizes(n, D, k, C.byref(sz)), "hdbscan")          # validates n, D, k first
+    dev = X.device
+    ws = torch.empty(sz.value, dtype=torch.uint8, device=dev)
+    core2 = torch.empty(n, dtype=torch.float32, device=dev)
+    out = torch.empty(n + 9, dtype=torch.int64, device=dev)                        # n keys, then the 18 counts
+    _lib.check(lib.trase_hdbscan_core(_lib.ptr(X), n, D, k, _lib.ptr(core2), _lib.ptr(ws), ws.numel(), _device_index(dev),
+                                      _stream(dev)), "hdbscan")
+    _lib.check(lib.trase_hdbscan_mst(_lib.ptr(X), n, D, _lib.ptr(core2), _lib.ptr(out), _lib.ptr(out[n:]), _lib.ptr(ws),
+                                     ws.numel(), _device_index(dev), _stream(dev)), "hdbscan")
+    return core2, out
+
+
+def _mst_edges(out_host: np.ndarray, n: int) -> np.ndarray:
+    """The one read-back of ``_hdbscan_device`` (int64 (n + 9,)) -> float64 (n - 1, 3) rows (i, j, weight), ascending in
+    (weight, i, j), i < j."""
+    counts = out_host[n:].view(np.int32)
+    live = counts[counts > 0]
+    if live.size == 0 or live[-1] != 1:
+        raise RuntimeError(f"hdbscan: the spanning tree did not close (components per round: {live.tolist()})")
+    keys = np.sort(out_host[:n].view(np.uint64))[:n - 1]
+    w2 = (keys >> np.uint64(32)).astype(np.uint32).view(np.float32).astype(np.float64)
+    if not np.isfinite(w2).all():
+        raise ValueError("hdbscan: X has rows that are not finite")
+    edges = np.empty((n - 1, 3), dtype=np.float64)
+    edges[:, 0] = ((keys >> np.uint64(16)) & np.uint64(0xffff)).astype(np.float64)
+    edges[:, 1] = (keys & np.uint64(0xffff)).astype(np.float64)
+    edges[:, 2] = np.sqrt(w2)
+    return edges
+
+
+def hdbscan(X: torch.Tensor, *, min_cluster_size: int = 10, min_samples: int | None = None,
+            cluster_selection_epsilon: float = 0.0, allow_single_cluster: bool = False, return_mst: bool = False):
+    """``hdbscan.HDBSCAN(min_cluster_size, min_samples, cluster_selection_epsilon, allow_single_cluster).fit_predict(X)``
+    for the euclidean metric and excess-of-mass selection -> labels int64 (n,) on X's device; noise is -1, the clusters are
+    numbered 0..C-1 by their smallest member index.
+
+    ``min_samples`` (None: ``min_cluster_size``) is the package's: the core distance of a row is the distance to its
+    ``min_samples``-th nearest OTHER row (scikit-learn counts the row itself: its ``min_samples`` is ours + 1).  The core
+    distances and the minimum spanning tree of the mutual-reachability graph are computed on the device in fp32 squared
+    distances, ``sum (a_d - b_d)^2`` in dimension order; the n - 1 edges come back in one copy and ``hdbscan_hierarchy`` runs
+    on the host.  Among equal weights the tree takes the edge with the lower (min index, max index), where the libraries
+    follow their own scan order: partitions can differ from theirs only where distances tie exactly.
+
+    With ``return_mst`` also the (n - 1, 3) float64 edge list ``(i, j, weight)``, i < j, ascending in (weight, i, j), and the
+    core distances, float64 (n,), both on X's device: the float64 square roots of the fp32 squared values.
+    Limits: 2 <= n <= 65536, 1 <= D <= 64, 1 <= min_samples <= 64, min_samples < n.  Bitwise reproducible."""
+    if not torch.is_tensor(X) or X.device.type != "cuda":
+        raise RuntimeError("hdbscan runs on the GPU only (there is no CPU path)")
+    if X.dim() != 2:
+        raise ValueError(f"hdbscan: X must be (n, D), got {tuple(X.shape)}")
+    if int(min_cluster_size) < 2:
+        raise ValueError(f"hdbscan: min_cluster_size must be at least 2, got {min_cluster_size}")
+    X = X.detach().float().contiguous()
+    n = X.shape[0]
+    k = int(min_cluster_size if min_samples is None else min_samples)
+    core2, out = _hdbscan_device(X, k)
+    host = torch.empty(n + 9, dtype=torch.int64, pin_memory=True)
+    host.copy_(out, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(X.device))
+    ev.synchronize()
+    edges = _mst_edges(host.numpy(), n)
+    labels = hdbscan_hierarchy(edges, n, min_cluster_size=int(min_cluster_size),
+                               cluster_selection_epsilon=float(cluster_selection_epsilon),
+                               allow_single_cluster=bool(allow_single_cluster))
+    labels = torch.from_numpy(labels).to(X.device)
+    if return_mst:
+        return labels, torch.from_numpy(edges).to(X.device), core2.double().sqrt()
+    return labels
+
+
+def label_centres(X: torch.Tensor, labels: torch.Tensor, num_clusters: int) -> torch.Tensor:
+    """-> fp32 (C, D): row c = normalize(mean of the rows of X with label c), gui.py:284-286 without its off-by-one.  A
+    label outside [0, C) (noise: -1) belongs to no centre.  1 <= C <= 4096, 1 <= D <= 64."""
+    if not torch.is_tensor(X) or X.device.type != "cuda":
+        raise RuntimeError("label_centres runs on the GPU only (there is no CPU path)")
+    dev = X.device
+    X = X.detach().float().contiguous()
+    N, D = X.shape
+    ids = labels.detach().reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    if ids.numel() != N:
+        raise ValueError(f"label_centres: {ids.numel()} labels for {N} rows")
+    Cn = int(num_clusters)
+    lib = _lib.load()
+    sz = C.c_size_t()
+    _lib.check(lib.trase_label_centres_sizes(N, D, Cn, C.byref(sz)), "label_centres")
+    ws = torch.empty(sz.value, dtype=torch.uint8, device=dev)
+    centres = torch.empty(Cn, D, dtype=torch.float32, device=dev)
+    _lib.check(lib.trase_label_centres(_lib.ptr(X), N, D, _lib.ptr(ids), Cn, _lib.ptr(centres), _lib.ptr(ws), ws.numel(),
+                                       _device_index(dev), _stream(dev)), "label_centres")
+    return centres
+
+
+def density_clusters(features: torch.Tensor, *, percent: float = 0.02, min_cluster_size: int = 10,
+                     cluster_selection_epsilon: float = 0.01, return_sample: bool = False):
+    """The viewer's DBSCAN mode, gui.py:274-290, end to end on the device -> (ids int64 (N,), centres fp32 (C, D)).
+
+    The sample is drawn as the reference draws it, ``torch.rand(N) > 1 - percent`` on torch's default CPU generator (so
+    ``torch.manual_seed`` reproduces its draw), normalised, clustered by ``hdbscan``; the centres are the normalised means
+    of the labelled samples and every Gaussian takes the nearest centre by cosine (``assign_clusters``).  ``features`` is
+    (N, D) or (N, 1, D) and is only read.  Deliberate deviation: the reference's centre loop is off by one
+    (``cluster_labels == i - 1``: row 0 is the centre of the noise points -- NaN when there are none -- and the last cluster
+    gets none); here the centres belong to labels 0..C-1 and noise samples to none.  With ``return_sample`` also the sample's
+    indices, int64 (n,), and its labels, int64 (n,).  No cluster found: ValueError."""
+    if not torch.is_tensor(features) or features.device.type != "cuda":
+        raise RuntimeError("density_clusters runs on the GPU only (there is no CPU path)")
+    if features.dim() == 3 and features.shape[1] == 1:
+        features = features.squeeze(1)
+    if features.dim() != 2:
+        raise ValueError(f"density_clusters: features must be (N, D) or (N, 1, D), got {tuple(features.shape)}")
+    dev = features.device
+    X = features.detach().float()
+    index = torch.nonzero(torch.rand(X.shape[0]) > 1 - percent).flatten().to(dev)
+    sample = X[index]
+    sample = (sample / torch.norm(sample, dim=-1, keepdim=True)).contiguous()
+    labels = hdbscan(sample, min_cluster_size=min_cluster_size, cluster_selection_epsilon=cluster_selection_epsilon)
+    n_clusters = int(labels.max()) + 1 if labels.numel() else 0
+    if n_clusters < 1:
+        raise ValueError(f"density_clusters: no cluster among the {sample.shape[0]} sampled rows")
+    centres = label_centres(sample, labels, n_clusters)
+    ids = assign_clusters(X, centres)
+    return (ids, centres, index, labels) if return_sample else (ids, centres)
