@@ -687,6 +687,48 @@ int trase_label_centres_sizes(int32_t N, int32_t D, int32_t C, size_t* ws_bytes)
 int trase_label_centres(const float* X, int32_t N, int32_t D, const int32_t* labels, int32_t C, float* centres_out, void* ws,
                         size_t ws_bytes, int32_t device, trase_stream_t stream);
 
+/* ---- composited scenes: render_composite and its rigid edits (gaussian_renderer/__init__.py:158-331) ----------------------
+ * One part of a composited scene: a model's RAW parameters (n rows), optionally gathered through `rows`, deformed, and moved
+ * by a rigid edit.  Per output row i, with r = rows ? rows[i] : i, in fp32 and in the reference's statement order:
+ *   means = xyz[r] + d_xyz[r]; scales = exp(scaling[r]) + d_scaling[r]; rot = normalize(rotation[r]) + d_rotation[r];
+ *   opacity = sigmoid(opacity[r]); shs = cat(features_dc[r], features_rest[r]); sh_objs = gaussian_features[r] (as stored);
+ *   edit_mode >= 1: means *= scale_factor, scales *= scale_factor;
+ *   edit_mode == 2: means = R means, rot = normalize(q_edit (x) rot)   (Hamilton product, components (r,x,y,z));
+ *   edit_mode >= 1: means += offset.
+ * edit_mode 1 is the reference's early return for angles that are all exactly zero: rot stays the un-renormalised sum.
+ * Rescale and rotation are about the world origin; SH coefficients are not rotated.  A rows[] entry outside [0, n) is never
+ * dereferenced: its output row is all zeros.  exp is the library expf (<= 1 ulp). */
+typedef struct TraseComposePart {
+  int32_t n;                        /* rows of the model */
+  int32_t m;                        /* output rows: entries of `rows`, or n when rows is NULL */
+  int32_t F;                        /* feature channels, 0 <= F <= 64 */
+  int32_t edit_mode;                /* 0 none, 1 rescale + translate, 2 rescale + rotate + translate */
+  const float* xyz;                 /* (n,3)    */
+  const float* scaling;             /* (n,3)    */
+  const float* rotation;            /* (n,4), 16-byte aligned */
+  const float* opacity;             /* (n,1)    */
+  const float* features_dc;         /* (n,1,3)  */
+  const float* features_rest;       /* (n,15,3) */
+  const float* gaussian_features;   /* (n,1,F), 16-byte aligned; NULL when F == 0 */
+  const int64_t* rows;              /* (m) device, ascending by convention, or NULL: all rows */
+  const float* d_xyz;               /* (n,3) or NULL: indexed by SOURCE row (the reference adds first, masks afterwards) */
+  const float* d_rotation;          /* (n,4) or NULL, 16-byte aligned */
+  const float* d_scaling;           /* (n,3) or NULL */
+  float scale_factor;
+  float R[9];                       /* row-major */
+  float q_edit[4];                  /* (r,x,y,z), r >= 0 */
+  float offset[3];
+} TraseComposePart;
+
+/* trase_compose_sizes: validates the part count (1..8), the row counts and F; offsets_out (HOST, n_parts + 1 int64) = the
+ *   first output row of every part and the total P (< 2^25).  No workspace is needed.
+ * trase_compose_part: one launch; writes rows [row_offset, row_offset + m) of means3D (P,3), scales (P,3), rotations (P,4),
+ *   opacities (P,1), shs (P,16,3), sh_objs (P,1,F) -- fp32, contiguous, 16-byte aligned.  Bitwise reproducible; the inputs
+ *   are read only. */
+int trase_compose_sizes(const int32_t* counts, int32_t n_parts, int32_t F, int64_t* offsets_out);
+int trase_compose_part(const TraseComposePart* part, int64_t row_offset, int64_t P_total, float* means3D, float* scales,
+                       float* rotations, float* opacities, float* shs, float* sh_objs, int32_t device, trase_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

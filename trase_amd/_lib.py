@@ -109,6 +109,16 @@ class MlpGrads(C.Structure):
     ]
 
 
+class ComposePart(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("m", C.c_int32), ("F", C.c_int32), ("edit_mode", C.c_int32),
+        ("xyz", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p), ("opacity", C.c_void_p),
+        ("features_dc", C.c_void_p), ("features_rest", C.c_void_p), ("gaussian_features", C.c_void_p),
+        ("rows", C.c_void_p), ("d_xyz", C.c_void_p), ("d_rotation", C.c_void_p), ("d_scaling", C.c_void_p),
+        ("scale_factor", C.c_float), ("R", C.c_float * 9), ("q_edit", C.c_float * 4), ("offset", C.c_float * 3),
+    ]
+
+
 # every symbol include/trase_rast.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("trase_rast_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(RastSizes)]),
@@ -244,6 +254,9 @@ SYMBOLS = [
     ("trase_feature_gram", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     ("trase_feature_project", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int32, C.c_void_p]),
+    ("trase_compose_sizes", C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("trase_compose_part", C.c_int, [C.POINTER(ComposePart), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("trase_adam_step", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_int32, C.c_void_p]),
     ("trase_adam_step_guarded", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
