@@ -56,54 +56,72 @@ ProfScope::~ProfScope() {
   g_prof_recs.push_back(r);
 }
 
-// ---- workspace layout ---------------------------------------------------------------------------------
-#ifndef TRASE_RS_ITEMS
-#define TRASE_RS_ITEMS 8
-#endif
-static inline int rs_blocks(size_t n) { return (int)((n + 256 * TRASE_RS_ITEMS - 1) / (256 * TRASE_RS_ITEMS)); }   // binning.hip RS_TILE
+// ---- workspace layouts (one walk per workspace, common.h WsCursor; ws == nullptr measures) -----------------
+static size_t geom_layout(void* ws, int P, GeomBuf& g) {
+  const size_t p = (size_t)P;
+  WsCursor w(ws);
+  g.hdr = w.take<uint32_t>(HDR_WORDS);
+  g.xy = w.take<float2>(p);
+  g.conic_o = w.take<float4>(p);
+  g.rgbd = w.take<float4>(p);
+  g.tiles = w.take<uint32_t>(p);
+  g.clamped = w.take<uint32_t>(p);
+  g.geo = w.take<float4>(4 * p);
+  g.ftab = w.take<uint32_t>(32 * p);
+  return w.bytes();
+}
+static size_t bin_layout(void* ws, int64_t cap, int T, BinBuf& b) {
+  WsCursor w(ws);
+  b.point_list = w.take<uint32_t>((size_t)cap);
+  b.pair_slot = w.take<uint32_t>((size_t)cap);
+  b.ranges = w.take<uint2>((size_t)T + 1);       // T sub-tiles + 1 sentinel ("trash") entry
+  return w.bytes();
+}
+static size_t img_layout(void* ws, int W, int H, ImgBuf& im) {
+  WsCursor w(ws);
+  im.final_T = w.take<float>((size_t)W * H);
+  im.n_contrib = w.take<uint32_t>((size_t)W * H);
+  return w.bytes();
+}
+static size_t pre_layout(void* ws, int P, PreBuf& t) {
+  const size_t p = (size_t)(P > 0 ? P : 1), partials = p / 1024 + 2;
+  WsCursor w(ws);
+  sort_layout(w, t.sort, p, SORT_KEYS | SORT_VALS);
+  t.offsets = w.take<uint32_t>(p);
+  t.id_end = w.take<uint32_t>(p);
+  t.live_ids = w.take<uint32_t>(p);
+  t.block_sums = w.take<uint32_t>(3 * partials);
+  t.block_R = t.block_sums + partials;
+  t.block_max = t.block_R + partials;
+  sort_layout(w, t.sort, p, SORT_HIST, DEPTH_MAX_DIGIT_BITS);
+  return w.bytes();
+}
+static size_t tmp_layout(void* ws, int64_t cap, PairBuf& t) {
+  const size_t n = (size_t)cap;
+  WsCursor w(ws);
+  sort_layout(w, t.sort, n, SORT_KEYS);
+  t.sort.vals[0] = t.sort.vals[1] = nullptr;     // arranged by the caller: {spare_vals, BinBuf::pair_slot}
+  t.spare_vals = w.take<uint32_t>(n);
+  t.pair_gauss = w.take<uint32_t>(n);
+  sort_layout(w, t.sort, n, SORT_HIST);
+  return w.bytes();
+}
+static size_t bwd_layout(void* ws, int P, int F, int64_t cap, BwdBuf& b) {
+  WsCursor w(ws);
+  b.acc = w.take<float>(BWD_ACC * (size_t)P);
+  const size_t flags_at = w.bytes();
+  b.row_flags = w.take<uint8_t>((size_t)cap);
+  b.flags_bytes = w.bytes() - flags_at;          // the MFMA backward clears the padded array
+  b.rows = w.take<float>(bwd_row_stride(F) * (size_t)cap);
+  return w.bytes();
+}
+static size_t geom_bytes(int P) { GeomBuf g; return geom_layout(nullptr, P, g); }
+static size_t bin_bytes(int64_t cap, int T) { BinBuf b; return bin_layout(nullptr, cap, T, b); }
+static size_t img_bytes(int W, int H) { ImgBuf im; return img_layout(nullptr, W, H, im); }
+static size_t pre_bytes(int P) { PreBuf t; return pre_layout(nullptr, P, t); }
+static size_t tmp_bytes(int64_t cap) { PairBuf t; return tmp_layout(nullptr, cap, t); }
+static size_t bwd_tmp_bytes(int P, int F, int64_t cap) { BwdBuf b; return bwd_layout(nullptr, P, F, cap, b); }
 
-size_t geom_bytes(int P) {
-  const size_t p = (size_t)P;
-  return align_up(sizeof(uint32_t) * HDR_WORDS) + align_up(sizeof(float2) * p) + align_up(sizeof(float4) * p) * 2 +
-         align_up(sizeof(uint32_t) * p) * 2 + align_up(sizeof(float4) * 4 * p) + align_up(sizeof(uint32_t) * 32 * p);
-}
-GeomBuf carve_geom(void* ptr, int P) {
-  const size_t p = (size_t)P;
-  char* c = (char*)ptr;
-  GeomBuf g;
-  g.hdr = (uint32_t*)c; c += align_up(sizeof(uint32_t) * HDR_WORDS);
-  g.xy = (float2*)c; c += align_up(sizeof(float2) * p);
-  g.conic_o = (float4*)c; c += align_up(sizeof(float4) * p);
-  g.rgbd = (float4*)c; c += align_up(sizeof(float4) * p);
-  g.tiles = (uint32_t*)c; c += align_up(sizeof(uint32_t) * p);
-  g.clamped = (uint32_t*)c; c += align_up(sizeof(uint32_t) * p);
-  g.geo = (float4*)c; c += align_up(sizeof(float4) * 4 * p);
-  g.ftab = (uint32_t*)c;
-  return g;
-}
-// ranges holds T sub-tiles + 1 sentinel ("trash") entry
-size_t bin_bytes(int64_t cap, int T) { return align_up(sizeof(uint32_t) * (size_t)cap) * 2 + align_up(sizeof(uint2) * ((size_t)T + 1)); }
-BinBuf carve_bin(void* ptr, int64_t cap, int T) {
-  char* c = (char*)ptr;
-  BinBuf b;
-  b.point_list = (uint32_t*)c; c += align_up(sizeof(uint32_t) * (size_t)cap);
-  b.pair_slot = (uint32_t*)c; c += align_up(sizeof(uint32_t) * (size_t)cap);
-  b.ranges = (uint2*)c;
-  (void)T;
-  return b;
-}
-size_t img_bytes(int W, int H) { return align_up(sizeof(float) * (size_t)W * H) * 2; }
-ImgBuf carve_img(void* ptr, int W, int H) {
-  char* c = (char*)ptr;
-  ImgBuf i;
-  i.final_T = (float*)c; c += align_up(sizeof(float) * (size_t)W * H);
-  i.n_contrib = (uint32_t*)c;
-  return i;
-}
-static size_t sort_bytes_common(size_t n, int digit_bits = 8) {   // hist + digit_total
-  const size_t nd = (size_t)1 << digit_bits;
-  return align_up(sizeof(uint32_t) * nd * (size_t)rs_blocks(n) * rs_hist_copies(rs_blocks(n))) + align_up(sizeof(uint32_t) * nd * 8);
-}
 // bits of a packed list value left for the pair index (HDR_PACK); 0 = the variant's kernels need emit-order slots
 static int list_pack_bits(const TraseRastSettings* s, int P) {
   if (s->variant & TRASE_VARIANT_SLOT_LISTS) return 0;
@@ -111,47 +129,6 @@ static int list_pack_bits(const TraseRastSettings* s, int P) {
   while ((1ll << lg) < (long long)P) ++lg;
   if (lg >= 28) return 0;
   return lg < 1 ? 31 : 32 - lg;       // never 32: the kernels evaluate (1u << jb) and v >> jb
-}
-size_t pre_bytes(int P) {
-  const size_t p = (size_t)(P > 0 ? P : 1);
-  return align_up(sizeof(uint32_t) * p) * 7 + align_up(sizeof(uint32_t) * (p / 1024 + 2) * 3) + sort_bytes_common(p, DEPTH_MAX_DIGIT_BITS);
-}
-PreBuf carve_pre(void* ptr, int P) {
-  const size_t p = (size_t)(P > 0 ? P : 1);
-  char* c = (char*)ptr;
-  PreBuf t;
-  for (int i = 0; i < 2; ++i) { t.sort.keys[i] = (uint32_t*)c; c += align_up(sizeof(uint32_t) * p); }
-  for (int i = 0; i < 2; ++i) { t.sort.vals[i] = (uint32_t*)c; c += align_up(sizeof(uint32_t) * p); }
-  t.offsets = (uint32_t*)c; c += align_up(sizeof(uint32_t) * p);
-  t.id_end = (uint32_t*)c; c += align_up(sizeof(uint32_t) * p);
-  t.live_ids = (uint32_t*)c; c += align_up(sizeof(uint32_t) * p);
-  t.block_sums = (uint32_t*)c; c += align_up(sizeof(uint32_t) * (p / 1024 + 2) * 3);
-  t.sort.hist = (uint32_t*)c; c += align_up(sizeof(uint32_t) * ((size_t)1 << DEPTH_MAX_DIGIT_BITS) * (size_t)rs_blocks(p) * rs_hist_copies(rs_blocks(p)));
-  t.sort.digit_total = (uint32_t*)c;
-  t.sort.nb_max = rs_blocks(p);
-  t.sort.hist_copies = rs_hist_copies(rs_blocks(p));
-  return t;
-}
-size_t tmp_bytes(int64_t cap) {
-  const size_t n = (size_t)cap;
-  return align_up(sizeof(uint32_t) * n) * 4 + sort_bytes_common(n);
-}
-PairBuf carve_tmp(void* ptr, int64_t cap) {
-  const size_t n = (size_t)cap;
-  char* c = (char*)ptr;
-  PairBuf t;
-  for (int i = 0; i < 2; ++i) { t.sort.keys[i] = (uint32_t*)c; c += align_up(sizeof(uint32_t) * n); }
-  t.spare_vals = (uint32_t*)c; c += align_up(sizeof(uint32_t) * n);
-  t.pair_gauss = (uint32_t*)c; c += align_up(sizeof(uint32_t) * n);
-  t.sort.vals[0] = t.sort.vals[1] = nullptr;
-  t.sort.hist = (uint32_t*)c; c += align_up(sizeof(uint32_t) * 256 * (size_t)rs_blocks(n) * rs_hist_copies(rs_blocks(n)));
-  t.sort.digit_total = (uint32_t*)c;
-  t.sort.nb_max = rs_blocks(n);
-  t.sort.hist_copies = rs_hist_copies(rs_blocks(n));
-  return t;
-}
-size_t bwd_tmp_bytes(int P, int F, int64_t cap) {
-  return align_up(sizeof(float) * BWD_ACC * (size_t)P) + align_up((size_t)cap) + align_up(sizeof(float) * bwd_row_stride(F) * (size_t)cap);
 }
 
 static int validate(const TraseRastSettings* s, const TraseRastInputs* in) {
@@ -327,10 +304,12 @@ int trase_rast_sizes(int32_t P, int32_t W, int32_t H, int32_t F, int64_t capacit
 
 int trase_rast_geom_layout(int32_t P, int64_t off[6]) {
   if (P < 0 || !off) { set_error("trase_rast_geom_layout: bad arguments"); return TRASE_ERR_INVALID; }
-  const GeomBuf g = carve_geom(nullptr, P);
-  off[0] = (int64_t)((char*)g.hdr - (char*)nullptr); off[1] = (int64_t)((char*)g.xy - (char*)nullptr);
-  off[2] = (int64_t)((char*)g.conic_o - (char*)nullptr); off[3] = (int64_t)((char*)g.rgbd - (char*)nullptr);
-  off[4] = (int64_t)((char*)g.tiles - (char*)nullptr); off[5] = (int64_t)((char*)g.clamped - (char*)nullptr);
+  // laid out at an arbitrary non-null address that is never dereferenced; the offsets are differences of integers
+  const uintptr_t base = 256;
+  GeomBuf g;
+  geom_layout((void*)base, P, g);
+  const void* const field[6] = {g.hdr, g.xy, g.conic_o, g.rgbd, g.tiles, g.clamped};
+  for (int i = 0; i < 6; ++i) off[i] = (int64_t)((uintptr_t)field[i] - base);
   return TRASE_OK;
 }
 
@@ -344,8 +323,8 @@ int trase_rast_preprocess(const TraseRastSettings* s, const TraseRastInputs* in,
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(s->device));
   LaunchCtx c{stream, s->debug, s->variant};
-  GeomBuf g = carve_geom(ws->geom, in->P);
-  PreBuf t = carve_pre(ws->pre, in->P);
+  GeomBuf g; geom_layout(ws->geom, in->P, g);
+  PreBuf t; pre_layout(ws->pre, in->P, t);
   if (in->P == 0) return launch_zero_bytes(g.hdr, sizeof(uint32_t) * HDR_WORDS, stream);   // (P > 0: the preprocess kernel clears it; a kernel, not a memset node: common.h)
   const DepthSortCfg cfg = depth_sort_cfg(s->variant);
   rc = launch_preprocess_fwd(c, *s, *in, out->radii, g, t.sort.keys[strip_mode(s) ? 1 - cfg.start : cfg.start], cfg.key_bits == 27);
@@ -379,12 +358,12 @@ int trase_rast_render(const TraseRastSettings* s, const TraseRastInputs* in, con
   LaunchCtx c{stream, s->debug, s->variant};
   const int gx = (s->image_width + SUB - 1) / SUB, gy = (s->image_height + SUB - 1) / SUB;
   const int T = gx * gy;
-  GeomBuf g = carve_geom(ws->geom, in->P);
-  BinBuf b = carve_bin(ws->bin, ws->capacity, T);
-  ImgBuf im = carve_img(ws->img, s->image_width, s->image_height);
-  PreBuf pre = carve_pre(ws->pre, in->P);
+  GeomBuf g; geom_layout(ws->geom, in->P, g);
+  BinBuf b; bin_layout(ws->bin, ws->capacity, T, b);
+  ImgBuf im; img_layout(ws->img, s->image_width, s->image_height, im);
+  PreBuf pre; pre_layout(ws->pre, in->P, pre);
   b.id_end = pre.id_end;       // the forward turns packed list values into row slots (HDR_PACK)
-  PairBuf t = carve_tmp(ws->tmp, ws->capacity);
+  PairBuf t; tmp_layout(ws->tmp, ws->capacity, t);
   const uint32_t cap = (uint32_t)ws->capacity;
   if (in->P > 0) {
     int bits = 1;
@@ -460,13 +439,11 @@ static int backward_impl(const TraseRastSettings* s, const TraseRastInputs* in, 
   TRASE_CHECK(hipSetDevice(s->device));
   LaunchCtx c{stream, s->debug, s->variant};
   const int gx = (s->image_width + SUB - 1) / SUB, gy = (s->image_height + SUB - 1) / SUB;
-  GeomBuf g = carve_geom(ws->geom, in->P);
-  BinBuf b = carve_bin(ws->bin, ws->capacity, gx * gy);
-  ImgBuf im = carve_img(ws->img, s->image_width, s->image_height);
-  PreBuf pre = carve_pre(ws->pre, in->P);
-  float* acc = (float*)ws->tmp;
-  uint8_t* row_flags = (uint8_t*)ws->tmp + align_up(sizeof(float) * BWD_ACC * (size_t)in->P);
-  float* rows = (float*)(row_flags + align_up((size_t)ws->capacity));
+  GeomBuf g; geom_layout(ws->geom, in->P, g);
+  BinBuf b; bin_layout(ws->bin, ws->capacity, gx * gy, b);
+  ImgBuf im; img_layout(ws->img, s->image_width, s->image_height, im);
+  PreBuf pre; pre_layout(ws->pre, in->P, pre);
+  BwdBuf bw; bwd_layout(ws->tmp, in->P, in->F, ws->capacity, bw);
   if (in->P == 0) return TRASE_OK;
   TraseRastGrads g2 = *gr;
   if (!(s->variant & TRASE_VARIANT_DEPTH_GRAD)) g2.dL_ddepth = nullptr;   // lineage: depth carries no gradient
@@ -483,10 +460,10 @@ static int backward_impl(const TraseRastSettings* s, const TraseRastInputs* in, 
   // phase 2: every Gaussian sums its contiguous rows.  No atomics, bit-reproducible.
   // F == 0 here also means "no feature cotangent" (GAUSSIAN-state iterations): the MFMA kernel's image-only scope
   if ((in2.F == 32 || in2.F == 0) && !valu_backward(s)) {
-    rc = launch_render_bwd_hw(c, *s, in2, g, b, im, g2, rows, row_flags, align_up((size_t)ws->capacity), out->depth);
+    rc = launch_render_bwd_hw(c, *s, in2, g, b, im, g2, bw.rows, bw.row_flags, bw.flags_bytes, out->depth);
   } else {
-    launch_zero_bytes(row_flags, (size_t)ws->capacity, stream);
-    rc = launch_render_bwd_gs(c, *s, in2, g, b, im, g2, rows, row_flags, out->depth);
+    launch_zero_bytes(bw.row_flags, (size_t)ws->capacity, stream);
+    rc = launch_render_bwd_gs(c, *s, in2, g, b, im, g2, bw.rows, bw.row_flags, out->depth);
   }
   if (rc) return rc;
   // a tile-row strip: the forward compacted the ids of the Gaussians with a pair in the strip in front of the depth order and
@@ -495,12 +472,12 @@ static int backward_impl(const TraseRastSettings* s, const TraseRastInputs* in, 
   // always did this); the rows it does not write -- Gaussians without a pair: zero gradient -- start at zero.
   const int live_only = strip_mode(s) ? 1 : 0;
   if (live_only) {
-    launch_zero_bytes(acc, sizeof(float) * BWD_ACC * (size_t)in->P, stream);
+    launch_zero_bytes(bw.acc, sizeof(float) * BWD_ACC * (size_t)in->P, stream);
     if (g2.dL_dsh_objs) launch_zero_bytes(g2.dL_dsh_objs, sizeof(float) * (size_t)in2.F * in->P, stream);
   }
-  rc = launch_reduce_rows(c, g, pre, in->P, in2.F, rows, row_flags, acc, g2.dL_dsh_objs, nullptr, 0, -1, -1, live_only);
+  rc = launch_reduce_rows(c, g, pre, in->P, in2.F, bw.rows, bw.row_flags, bw.acc, g2.dL_dsh_objs, nullptr, 0, -1, -1, live_only);
   if (rc) return rc;
-  return launch_preprocess_bwd(c, *s, *in, out->radii, g, acc, *gr);
+  return launch_preprocess_bwd(c, *s, *in, out->radii, g, bw.acc, *gr);
 }
 
 // ---- render() with A1 fused in (raw parameters) ---------------------------------------------------------
@@ -538,8 +515,8 @@ int trase_rast_preprocess_raw(const TraseRastSettings* s, const TraseRastRawInpu
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(s->device));
   LaunchCtx c{stream, s->debug, s->variant};
-  GeomBuf g = carve_geom(ws->geom, in.P);
-  PreBuf t = carve_pre(ws->pre, in.P);
+  GeomBuf g; geom_layout(ws->geom, in.P, g);
+  PreBuf t; pre_layout(ws->pre, in.P, t);
   if (in.P == 0) return launch_zero_bytes(g.hdr, sizeof(uint32_t) * HDR_WORDS, stream);   // (P > 0: the preprocess kernel clears it; a kernel, not a memset node: common.h)
   const DepthSortCfg cfg = depth_sort_cfg(s->variant);
   rc = launch_preprocess_fwd_raw(c, *s, *raw, out->radii, g, t.sort.keys[strip_mode(s) ? 1 - cfg.start : cfg.start], cfg.key_bits == 27, 0u,
@@ -554,10 +531,14 @@ int trase_rast_preprocess_raw(const TraseRastSettings* s, const TraseRastRawInpu
 // index -- view 0's keys sort in front of view 1's, each in its own depth order, ties by ascending id as before.  Everything after
 // the sort (scan, emit, sub-tile sort, compositing) and the whole backward run per view, unchanged, on the per-view workspaces; the
 // forward results are bit-identical to two single-view calls.
-static size_t pair_ws_bytes(int P) {
-  const size_t n = 2 * (size_t)(P > 0 ? P : 1);
-  return align_up(sizeof(uint32_t) * n) * 4 + sort_bytes_common(n) + align_up(sizeof(uint32_t) * 4);
+struct PairSortWs { SortBufs sort; uint32_t* n_word; };      // the joint depth sort of 2 P keys and its item count
+static size_t pair_ws_layout(void* ws, int P, PairSortWs& t) {
+  WsCursor w(ws);
+  sort_layout(w, t.sort, 2 * (size_t)(P > 0 ? P : 1));
+  t.n_word = w.take<uint32_t>(4);
+  return w.bytes();
 }
+static size_t pair_ws_bytes(int P) { PairSortWs t; return pair_ws_layout(nullptr, P, t); }
 int trase_rast_pair_sizes(int32_t P, size_t* bytes) {
   if (!bytes || P < 0) { set_error("trase_rast_pair_sizes: bad arguments"); return TRASE_ERR_INVALID; }
   *bytes = pair_ws_bytes(P);
@@ -568,23 +549,17 @@ static int forward_raw_pair_impl(const TraseRastSettings* const s[2], const Tras
                                  const TraseRastWorkspace* const ws[2], void* pair_ws, hipStream_t stream) {
   const int P = raw[0]->P;
   TRASE_CHECK(hipSetDevice(s[0]->device));
-  char* cp = (char*)pair_ws;
   const size_t n = 2 * (size_t)P;
-  SortBufs cs;
-  for (int i = 0; i < 2; ++i) { cs.keys[i] = (uint32_t*)cp; cp += align_up(sizeof(uint32_t) * n); }
-  for (int i = 0; i < 2; ++i) { cs.vals[i] = (uint32_t*)cp; cp += align_up(sizeof(uint32_t) * n); }
-  cs.hist = (uint32_t*)cp; cp += align_up(sizeof(uint32_t) * 256 * (size_t)rs_blocks(n) * rs_hist_copies(rs_blocks(n)));
-  cs.hist_copies = rs_hist_copies(rs_blocks(n));
-  cs.digit_total = (uint32_t*)cp; cp += align_up(sizeof(uint32_t) * 256 * 8);
-  cs.nb_max = rs_blocks(n);
-  uint32_t* n_word = (uint32_t*)cp;
+  PairSortWs pw; pair_ws_layout(pair_ws, P, pw);
+  const SortBufs& cs = pw.sort;
+  uint32_t* const n_word = pw.n_word;
   launch_fill_u32(n_word, (uint32_t)n, stream);
   GeomBuf g[2];
   PreBuf t[2];
   for (int v = 0; v < 2; ++v) {
     LaunchCtx c{stream, s[v]->debug, s[v]->variant};
-    g[v] = carve_geom(ws[v]->geom, P);
-    t[v] = carve_pre(ws[v]->pre, P);
+    geom_layout(ws[v]->geom, P, g[v]);
+    pre_layout(ws[v]->pre, P, t[v]);
     const int rc = launch_preprocess_fwd_raw(c, *s[v], *raw[v], out[v]->radii, g[v], cs.keys[0] + (size_t)v * P, false,
                                              v ? 0x80000000u : 0u, v ? 0xffffffffu : 0x7fffffffu);
     if (rc) return rc;
@@ -673,13 +648,11 @@ static int backward_raw_phases(const TraseRastSettings* s, const TraseRastRawInp
   TRASE_CHECK(hipSetDevice(s->device));
   LaunchCtx c{stream, s->debug, s->variant};
   const int gx = (s->image_width + SUB - 1) / SUB, gy = (s->image_height + SUB - 1) / SUB;
-  GeomBuf g = carve_geom(ws->geom, in.P);
-  BinBuf b = carve_bin(ws->bin, ws->capacity, gx * gy);
-  ImgBuf im = carve_img(ws->img, s->image_width, s->image_height);
-  PreBuf pre = carve_pre(ws->pre, in.P);
-  float* acc = (float*)ws->tmp;
-  uint8_t* row_flags = (uint8_t*)ws->tmp + align_up(sizeof(float) * BWD_ACC * (size_t)in.P);
-  float* rows = (float*)(row_flags + align_up((size_t)ws->capacity));
+  GeomBuf g; geom_layout(ws->geom, in.P, g);
+  BinBuf b; bin_layout(ws->bin, ws->capacity, gx * gy, b);
+  ImgBuf im; img_layout(ws->img, s->image_width, s->image_height, im);
+  PreBuf pre; pre_layout(ws->pre, in.P, pre);
+  BwdBuf bw; bwd_layout(ws->tmp, in.P, in.F, ws->capacity, bw);
   if (in.P == 0) return TRASE_OK;
   TraseRastGrads g2;
   memset(&g2, 0, sizeof(g2));
@@ -697,10 +670,10 @@ static int backward_raw_phases(const TraseRastSettings* s, const TraseRastRawInp
     if (no_feat_cotangent && gr->dL_dgaussian_features && raw->F > 0 && !sparse)
       launch_zero_bytes(gr->dL_dgaussian_features, sizeof(float) * (size_t)raw->F * raw->P, stream);
     if ((in.F == 32 || in.F == 0) && !valu_backward(s)) {
-      rc = launch_render_bwd_hw(c, *s, in, g, b, im, g2, rows, row_flags, align_up((size_t)ws->capacity), out->depth);
+      rc = launch_render_bwd_hw(c, *s, in, g, b, im, g2, bw.rows, bw.row_flags, bw.flags_bytes, out->depth);
     } else {
-      launch_zero_bytes(row_flags, (size_t)ws->capacity, stream);
-      rc = launch_render_bwd_gs(c, *s, in, g, b, im, g2, rows, row_flags, out->depth);
+      launch_zero_bytes(bw.row_flags, (size_t)ws->capacity, stream);
+      rc = launch_render_bwd_gs(c, *s, in, g, b, im, g2, bw.rows, bw.row_flags, out->depth);
     }
     if (rc) return rc;
   }
@@ -709,10 +682,10 @@ static int backward_raw_phases(const TraseRastSettings* s, const TraseRastRawInp
     // depth order); the feature-gradient rows of the others are zeroed by the per-Gaussian kernel, which writes their other
     // gradients as zeros anyway
     const int live_only = (strip_mode(s) && !ranged) ? 1 : 0;
-    rc = launch_reduce_rows(c, g, pre, in.P, in.F, rows, row_flags, acc, d_feats, raw->gaussian_features, raw->norm_features,
+    rc = launch_reduce_rows(c, g, pre, in.P, in.F, bw.rows, bw.row_flags, bw.acc, d_feats, raw->gaussian_features, raw->norm_features,
                             ranged ? p_begin : -1, ranged ? p_end : -1, live_only);
     if (rc) return rc;
-    rc = launch_preprocess_bwd_raw(c, *s, *raw, out->radii, g, acc, *gr, ranged ? p_begin : 0, ranged ? p_end : raw->P,
+    rc = launch_preprocess_bwd_raw(c, *s, *raw, out->radii, g, bw.acc, *gr, ranged ? p_begin : 0, ranged ? p_end : raw->P,
                                    (live_only && d_feats && !sparse) ? 1 : 0, sparse ? pre.live_ids : nullptr);
   }
   return rc;
@@ -746,7 +719,9 @@ int trase_rast_zero_live_rows(const TraseRastSettings* s, const TraseRastRawInpu
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(s->device));
   LaunchCtx c{stream, s->debug, s->variant};
-  return launch_zero_live_rows(c, carve_geom(ws->geom, raw->P), carve_pre(ws->pre, raw->P), raw->P, raw->F, *gr);
+  GeomBuf g; geom_layout(ws->geom, raw->P, g);
+  PreBuf pre; pre_layout(ws->pre, raw->P, pre);
+  return launch_zero_live_rows(c, g, pre, raw->P, raw->F, *gr);
 }
 
 int trase_rast_backward_raw_compose(const TraseRastSettings* s, const TraseRastRawInputs* raw, const TraseRastOutputs* out,

@@ -17,13 +17,8 @@
 
 namespace trase {
 
-constexpr int RS_THREADS = 256;
-#ifndef TRASE_RS_ITEMS
-#define TRASE_RS_ITEMS 8
-#endif
-constexpr int RS_ITEMS = TRASE_RS_ITEMS;
+// RS_THREADS, RS_ITEMS, RS_TILE: common.h, beside the layout of the sort's buffers
 constexpr int RS_WAVES = RS_THREADS / WAVE;
-constexpr int RS_TILE = RS_THREADS * RS_ITEMS;   // 2048 items per workgroup
 constexpr int RS_SEG = WAVE * RS_ITEMS;          // 512 contiguous items per wave
 
 __device__ __forceinline__ uint32_t dev_n(const uint32_t* n_ptr, uint32_t cap) {
@@ -352,7 +347,7 @@ int launch_split_pair_ids(const LaunchCtx& c, const uint32_t* sorted, int P, uin
 
 int radix_passes(int bit_lo, int bit_hi, int digit_bits) { return (bit_hi - bit_lo + digit_bits - 1) / digit_bits; }
 
-// digit_bits 8 or 9 (SortBufs::hist / digit_total must be sized for it: (1 << digit_bits) * nb_max and (1 << digit_bits) * passes);
+// digit_bits 8 or 9 (SortBufs::hist / digit_total must be laid out for it: sort_layout in common.h);
 // `start`: which of the ping-pong buffers holds the input
 template <int DB>
 static int radix_sort_pairs_t(const LaunchCtx& c, const SortBufs& t, const uint32_t* n_ptr, uint32_t n_cap, int bit_lo, int bit_hi,
@@ -362,7 +357,7 @@ static int radix_sort_pairs_t(const LaunchCtx& c, const SortBufs& t, const uint3
   const int nb = (int)((n_cap + RS_TILE - 1) / RS_TILE);
   if (nb > t.nb_max) { set_error("radix_sort_pairs: nb %d > nb_max %d", nb, t.nb_max); return TRASE_ERR_WORKSPACE; }
   const int passes = radix_passes(bit_lo, bit_hi, DB);
-  if (passes > 8) return TRASE_ERR_INVALID;
+  if (passes > RS_MAX_PASSES) return TRASE_ERR_INVALID;
   static const bool small_off = [] { const char* e = getenv("TRASE_SORT_SMALL"); return e && atoi(e) == 0; }();
   if (nb <= RS_SMALL_NB && t.hist_copies >= passes && !small_off) {
     // short sort: 1 + passes launches (see RS_SMALL_NB in common.h)
@@ -660,14 +655,12 @@ __global__ __launch_bounds__(SC_THREADS) void scan_sums_kernel(uint32_t* __restr
 int launch_scan_tiles(const LaunchCtx& c, const GeomBuf& g, const uint32_t* sorted_ids, int P, const PreBuf& t, uint32_t cap,
                       const int32_t* radii, int gx, int gy, int pack_bits) {
   const int nblocks = (P + SC_TILE - 1) / SC_TILE;
-  uint32_t* const block_R = t.block_sums + ((size_t)P / 1024 + 2);
-  uint32_t* const block_max = t.block_sums + 2 * ((size_t)P / 1024 + 2);
   {
     ProfScope ps("scan_tiles", c.stream);
     hipLaunchKernelGGL(scan_partial_kernel, dim3(nblocks), dim3(SC_THREADS), 0, c.stream, g.tiles, sorted_ids, P,
-                       t.offsets, t.block_sums, radii, g.xy, gx, gy, block_R, block_max, g.hdr + (HDR_WORDS - 1));
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SC_THREADS), 0, c.stream, t.block_sums, nblocks, g.hdr, cap, block_R,
-                       block_max, pack_bits);
+                       t.offsets, t.block_sums, radii, g.xy, gx, gy, t.block_R, t.block_max, g.hdr + (HDR_WORDS - 1));
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SC_THREADS), 0, c.stream, t.block_sums, nblocks, g.hdr, cap, t.block_R,
+                       t.block_max, pack_bits);
   }
   TRASE_POST_LAUNCH("scan_tiles", c.stream, c.debug);
   return TRASE_OK;

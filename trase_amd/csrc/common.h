@@ -265,8 +265,28 @@ static inline void strip_subtile_rows(const TraseRastSettings& s, int& lo, int& 
 }
 
 // ----------------------------------------------------------------------------------------------
-// workspace carving (must match trase_rast_sizes)
+// workspace layouts: every workspace is described by ONE function that walks it with a WsCursor, fills the buffer struct
+// and returns the byte count -- with a null base the same walk only measures, so a size and its carving cannot disagree
 // ----------------------------------------------------------------------------------------------
+struct WsCursor {
+  explicit WsCursor(void* ws) : base((uintptr_t)ws) {}
+  // the next n elements of T, 256-byte aligned (null when measuring)
+  template <class T> T* take(size_t n) {
+    const size_t o = off;
+    off += align_up(sizeof(T) * n);
+    return base ? (T*)(base + o) : nullptr;
+  }
+  size_t bytes() const { return off; }
+  uintptr_t base;      // an integer: the walk never does arithmetic on a null pointer
+  size_t off = 0;
+};
+// the layout of a workspace that is one array
+template <class T> size_t array_layout(void* ws, size_t n, T*& p) {
+  WsCursor w(ws);
+  p = w.take<T>(n);
+  return w.bytes();
+}
+
 enum { HDR_R = 0, HDR_OVERFLOW = 1, HDR_R_EFF = 2, HDR_PACK = 3, HDR_WORDS = 64 };
 // HDR_PACK: 0 = list values are emit-order slots (ids through pair_gauss / point_list); jb > 0 = list values are
 // (Gaussian id << jb) | (index of the pair among the Gaussian's own pairs): decided on the device (every Gaussian must have
@@ -302,11 +322,19 @@ struct ImgBuf {            // saved between forward and backward
 struct SortBufs {          // ping-pong storage of one radix sort
   uint32_t* keys[2];
   uint32_t* vals[2];
-  uint32_t* hist;          // (digits * nb_max), digits = 256 (2048 for the depth sort)
-  uint32_t* digit_total;   // (digits * passes) one row per radix pass
+  uint32_t* hist;          // (digits * nb_max * hist_copies), digits = 1 << digit_bits
+  uint32_t* digit_total;   // (digits * RS_MAX_PASSES) one row per radix pass
   int nb_max;
   int hist_copies;         // how many (digits * nb_max) histograms `hist` holds: >= the number of passes enables the short sorts' fused passes
 };
+// the radix sort's workgroup tile (kernels in binning.hip): what the histograms are sized by
+#ifndef TRASE_RS_ITEMS
+#define TRASE_RS_ITEMS 8
+#endif
+constexpr int RS_THREADS = 256, RS_ITEMS = TRASE_RS_ITEMS;
+constexpr int RS_TILE = RS_THREADS * RS_ITEMS;   // 2048 items per workgroup
+constexpr int RS_MAX_PASSES = 8;                 // rows of digit_total: radix_sort_pairs refuses more passes
+inline int rs_blocks(size_t n) { return (int)((n + RS_TILE - 1) / RS_TILE); }
 // Short sorts (at most RS_SMALL_NB workgroups of 2048 items = 32k items: BASELINE config 1, small test scenes): a pass is ONE launch --
 // the scatter workgroups scan the per-workgroup histograms themselves and count the NEXT pass's digits at the destinations with
 // global integer atomics (deterministic; one per run of equal words inside a wave), so a sort of p passes is 1 + p launches instead
@@ -316,11 +344,27 @@ struct SortBufs {          // ping-pong storage of one radix sort
 constexpr int RS_SMALL_NB = 16;
 constexpr int RS_SMALL_COPIES = 4;
 inline int rs_hist_copies(int nb) { return nb <= RS_SMALL_NB ? RS_SMALL_COPIES : 1; }
+// The one layout of a sort of up to n items: keys[2] | vals[2] | hist | digit_total.  `parts` selects what this call takes, so a
+// workspace that keeps buffers of its own between the items and the histograms calls it twice, and one whose caller arranges
+// the values itself (PairBuf) leaves SORT_VALS out.  hist_copies 0 = what the short sorts' fused passes want (rs_hist_copies).
+enum { SORT_KEYS = 1, SORT_VALS = 2, SORT_HIST = 4, SORT_ALL = 7 };
+inline void sort_layout(WsCursor& w, SortBufs& s, size_t n, int parts = SORT_ALL, int digit_bits = 8, int hist_copies = 0) {
+  if (parts & SORT_KEYS) for (int i = 0; i < 2; ++i) s.keys[i] = w.take<uint32_t>(n);
+  if (parts & SORT_VALS) for (int i = 0; i < 2; ++i) s.vals[i] = w.take<uint32_t>(n);
+  if (!(parts & SORT_HIST)) return;
+  const size_t digits = (size_t)1 << digit_bits;
+  s.nb_max = rs_blocks(n);
+  s.hist_copies = hist_copies ? hist_copies : rs_hist_copies(s.nb_max);
+  s.hist = w.take<uint32_t>(digits * s.nb_max * s.hist_copies);
+  s.digit_total = w.take<uint32_t>(digits * RS_MAX_PASSES);
+}
 struct PreBuf {            // stage-1 scratch (P-sized), read again by stage 2
   SortBufs sort;           // depth sort; sorted ids end in sort.vals[0]
   uint32_t* offsets;       // (P) inclusive scan of tiles in depth-rank order
   uint32_t* id_end;        // (P) the same, indexed by Gaussian id: the pairs of Gaussian i are [id_end[i] - tiles[i], id_end[i])
-  uint32_t* block_sums;    // scan partials: (P/1024 + 2) of the live sub-tile counts, then as many of the rect areas
+  uint32_t* block_sums;    // scan partials, one array of 3 x (P/1024 + 2): the live sub-tile counts,
+  uint32_t* block_R;       // the rect areas
+  uint32_t* block_max;     // and the largest pair count of one Gaussian
   uint32_t* live_ids;      // (P) tile-row strips: the ids of the Gaussians with a pair in the strip, ASCENDING (the sorted list in
                            // sort.vals[0] visits memory in depth order: scattered rows; this one walks it monotonically)
 };
@@ -333,12 +377,12 @@ struct PairBuf {           // stage-2 scratch (capacity-sized)
 constexpr int BWD_ACC = 12;
 enum { ACC_NDCX = 0, ACC_NDCY = 1, ACC_CA = 2, ACC_CB = 3, ACC_CC = 4, ACC_OP = 5, ACC_R = 6, ACC_G = 7, ACC_B = 8, ACC_D = 9 };
 
-size_t geom_bytes(int P);
-size_t bin_bytes(int64_t cap, int T);
-size_t img_bytes(int W, int H);
-size_t pre_bytes(int P);
-size_t tmp_bytes(int64_t cap);
-size_t bwd_tmp_bytes(int P, int F, int64_t cap);
+struct BwdBuf {            // backward scratch (the tmp workspace again)
+  float* acc;              // (P, BWD_ACC)
+  uint8_t* row_flags;      // (flags_bytes) one per pair slot
+  float* rows;             // (capacity, bwd_row_stride(F)) one gradient row per pair
+  size_t flags_bytes;
+};
 static inline int bwd_row_floats(int F) { return F + 12; }
 // distance between the rows of consecutive slots, in floats (experiment knob: 64 puts every F = 32 row on its own pair of
 // 128-byte lines)
@@ -346,11 +390,6 @@ static inline int bwd_row_floats(int F) { return F + 12; }
 #define TRASE_ROW_STRIDE32 44
 #endif
 constexpr int bwd_row_stride(int F) { return F == 32 ? TRASE_ROW_STRIDE32 : F + 12; }
-GeomBuf carve_geom(void* p, int P);
-BinBuf carve_bin(void* p, int64_t cap, int T);
-ImgBuf carve_img(void* p, int W, int H);
-PreBuf carve_pre(void* p, int P);
-PairBuf carve_tmp(void* p, int64_t cap);
 
 // ----------------------------------------------------------------------------------------------
 // kernel launchers (one per .hip file)
@@ -407,9 +446,9 @@ int launch_zero_bytes(void* p, size_t bytes, hipStream_t stream);
 int launch_fill_u32(uint32_t* p, uint32_t v, hipStream_t stream);
 // per-label sums and counts of the rows of X (segment.hip; at most LABEL_SUMS_MAX labels per call), for hdbscan.hip
 constexpr int LABEL_SUMS_MAX = 128;
-size_t label_sums_ws_bytes(int N, int D, int S);
-int launch_label_sums(const float* X, int N, int D, const int32_t* ids, const int32_t* sel, int S, void* ws, const float** total_out,
-                      hipStream_t stream);
+struct LabelSumsWs { float* slabs; float* total; int32_t* slot; };     // total: the S x D sums followed by the S counts
+size_t label_sums_layout(void* ws, int N, int D, int S, LabelSumsWs& w);
+int launch_label_sums(const float* X, int N, int D, const int32_t* ids, const int32_t* sel, int S, const LabelSumsWs& w, hipStream_t stream);
 int launch_split_pair_ids(const LaunchCtx& c, const uint32_t* sorted, int P, uint32_t* ids0, uint32_t* ids1);
 int radix_passes(int bit_lo, int bit_hi, int digit_bits = 8);
 // The depth sort (round 5).  Default: an order-preserving 27-bit key -- the float32 depth bits ABOVE those of the 0.2 near-cull

@@ -105,10 +105,14 @@ __global__ __launch_bounds__(256) void contrastive_bwd_kernel(const float* __res
   }
 }
 
-static size_t contrastive_ws_bytes(int S, int* nblocks) {
+struct ContrastiveWs { int* col; float* partial; int nblocks; };      // per-column flags | two partial sums per block
+static size_t contrastive_layout(void* ws, int S, ContrastiveWs& w) {
   const int bx = (S + 255) / 256, by = (S + CT_ROWS - 1) / CT_ROWS;
-  if (nblocks) *nblocks = bx * by;
-  return align_up(sizeof(int) * (size_t)S) + align_up(2 * sizeof(float) * (size_t)bx * by);
+  WsCursor c(ws);
+  w.nblocks = bx * by;
+  w.col = c.take<int>((size_t)S);
+  w.partial = c.take<float>(2 * (size_t)bx * by);
+  return c.bytes();
 }
 
 }  // namespace trase
@@ -119,7 +123,8 @@ extern "C" {
 
 int trase_contrastive_sizes(int32_t S, size_t* ws_bytes) {
   if (!ws_bytes || S < 1) { set_error("trase_contrastive_sizes: bad arguments"); return TRASE_ERR_INVALID; }
-  *ws_bytes = contrastive_ws_bytes(S, nullptr);
+  ContrastiveWs w;
+  *ws_bytes = contrastive_layout(nullptr, S, w);
   return TRASE_OK;
 }
 
@@ -127,20 +132,18 @@ int trase_contrastive_forward(const float* C, const float* C_F, const float* wei
                               int32_t kind, float* out2, void* ws, size_t ws_bytes, int32_t device,
                               trase_stream_t stream_) {
   if (!C || !C_F || !out2 || S < 1 || kind < 0 || kind > 5) { set_error("trase_contrastive_forward: bad arguments"); return TRASE_ERR_INVALID; }
-  int nblocks = 0;
-  if (!ws || ws_bytes < contrastive_ws_bytes(S, &nblocks)) { set_error("trase_contrastive_forward: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  ContrastiveWs w;
+  if (!ws || ws_bytes < contrastive_layout(ws, S, w)) { set_error("trase_contrastive_forward: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  int* col = (int*)ws;
-  float* partial = (float*)((char*)ws + align_up(sizeof(int) * (size_t)S));
-  launch_zero_bytes(col, sizeof(int) * (size_t)S, stream);
+  launch_zero_bytes(w.col, sizeof(int) * (size_t)S, stream);
   const dim3 grid((S + 255) / 256, (S + CT_ROWS - 1) / CT_ROWS);
   {
     ProfScope ps("contrastive_fwd", stream);
     if ((kind >> 1) != 2)
-      hipLaunchKernelGGL(contrastive_flags_kernel, grid, dim3(256), 0, stream, C, C_F, S, threshold, kind, col);
-    hipLaunchKernelGGL(contrastive_sum_kernel, grid, dim3(256), 0, stream, C, C_F, weights, S, threshold, kind, col, partial);
-    hipLaunchKernelGGL(contrastive_final_kernel, dim3(1), dim3(256), 0, stream, partial, nblocks, col, S, kind, out2);
+      hipLaunchKernelGGL(contrastive_flags_kernel, grid, dim3(256), 0, stream, C, C_F, S, threshold, kind, w.col);
+    hipLaunchKernelGGL(contrastive_sum_kernel, grid, dim3(256), 0, stream, C, C_F, weights, S, threshold, kind, w.col, w.partial);
+    hipLaunchKernelGGL(contrastive_final_kernel, dim3(1), dim3(256), 0, stream, w.partial, w.nblocks, w.col, S, kind, out2);
   }
   TRASE_POST_LAUNCH("contrastive_fwd", stream, 0);
   return TRASE_OK;
@@ -150,13 +153,14 @@ int trase_contrastive_backward(const float* C, const float* C_F, const float* we
                                int32_t kind, const float* out2, const float* g, const void* ws, size_t ws_bytes, float* dL_dC_F,
                                int32_t device, trase_stream_t stream_) {
   if (!C || !C_F || !out2 || !g || !dL_dC_F || S < 1 || kind < 0 || kind > 5) { set_error("trase_contrastive_backward: bad arguments"); return TRASE_ERR_INVALID; }
-  if (!ws || ws_bytes < contrastive_ws_bytes(S, nullptr)) { set_error("trase_contrastive_backward: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  ContrastiveWs w;
+  if (!ws || ws_bytes < contrastive_layout(const_cast<void*>(ws), S, w)) { set_error("trase_contrastive_backward: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const dim3 grid((S + 255) / 256, (S + CT_ROWS - 1) / CT_ROWS);
   {
     ProfScope ps("contrastive_bwd", stream);
-    hipLaunchKernelGGL(contrastive_bwd_kernel, grid, dim3(256), 0, stream, C, C_F, weights, S, threshold, kind, (const int*)ws, out2,
+    hipLaunchKernelGGL(contrastive_bwd_kernel, grid, dim3(256), 0, stream, C, C_F, weights, S, threshold, kind, w.col, out2,
                        g,
                        dL_dC_F);
   }

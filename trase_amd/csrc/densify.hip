@@ -35,18 +35,14 @@ struct DensifyWs {                    // carved from the caller's workspace
   uint32_t* aux;                      // [2P]: children: row of the normal draw
 };
 
-static size_t densify_ws_carve(int P, DensifyWs* w, void* base) {
-  const int nblk = (P + 255) / 256;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
-  const size_t o_flags = take((size_t)P), o_blk = take(sizeof(uint32_t) * 4 * (size_t)nblk), o_tot = take(sizeof(uint32_t) * 8),
-               o_map = take(sizeof(uint32_t) * 2 * (size_t)P), o_aux = take(sizeof(uint32_t) * 2 * (size_t)P);
-  if (w && base) {
-    char* b = (char*)base;
-    w->flags = (uint8_t*)(b + o_flags); w->blk = (uint32_t*)(b + o_blk); w->totals = (uint32_t*)(b + o_tot);
-    w->map = (uint32_t*)(b + o_map); w->aux = (uint32_t*)(b + o_aux);
-  }
-  return off;
+static size_t densify_ws_layout(void* ws, int P, DensifyWs& w) {
+  WsCursor c(ws);
+  w.flags = c.take<uint8_t>((size_t)P);
+  w.blk = c.take<uint32_t>(4 * (size_t)((P + 255) / 256));
+  w.totals = c.take<uint32_t>(8);
+  w.map = c.take<uint32_t>(2 * (size_t)P);
+  w.aux = c.take<uint32_t>(2 * (size_t)P);
+  return c.bytes();
 }
 
 __global__ __launch_bounds__(256) void densify_stats_kernel(const float* __restrict__ vgrad, const int32_t* __restrict__ radii,
@@ -258,7 +254,8 @@ int trase_densify_stats_guarded(const float* viewspace_grad, const int32_t* radi
 
 int trase_densify_sizes(int32_t P, size_t* ws_bytes) {
   if (!ws_bytes || P < 1 || P >= (1 << 29)) { set_error("trase_densify_sizes: bad arguments"); return TRASE_ERR_INVALID; }
-  *ws_bytes = densify_ws_carve(P, nullptr, nullptr);
+  DensifyWs w;
+  *ws_bytes = densify_ws_layout(nullptr, P, w);
   return TRASE_OK;
 }
 
@@ -270,7 +267,7 @@ int trase_densify_plan(const float* xyz_gradient_accum, const float* denom, cons
     set_error("trase_densify_plan: bad arguments"); return TRASE_ERR_INVALID;
   }
   DensifyWs w;
-  if (!ws || ws_bytes < densify_ws_carve(P, &w, ws)) { set_error("trase_densify_plan: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  if (!ws || ws_bytes < densify_ws_layout(ws, P, w)) { set_error("trase_densify_plan: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const int nblk = (P + 255) / 256;
@@ -298,7 +295,7 @@ int trase_densify_apply(int32_t count, const void* const* src, void* const* dst,
     set_error("trase_densify_apply: null pointer"); return TRASE_ERR_INVALID;
   }
   DensifyWs w;
-  if (!ws || ws_bytes < densify_ws_carve(P, &w, const_cast<void*>(ws))) { set_error("trase_densify_apply: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  if (!ws || ws_bytes < densify_ws_layout(const_cast<void*>(ws), P, w)) { set_error("trase_densify_apply: workspace too small"); return TRASE_ERR_WORKSPACE; }
   GatherTensors t;
   int blocks = 0, k = 0;
   for (int i = 0; i < count; ++i) {

@@ -222,7 +222,9 @@ __global__ __launch_bounds__(256) void disp_normalise_kernel(float* __restrict__
 
 using namespace trase;
 
-static size_t gram_ws_bytes(int32_t N, int32_t D) { return align_up(sizeof(float) * (size_t)D * D * disp_blocks(N)); }
+// one-array workspaces: the per-pixel winner of the splat, the per-block Gram slabs
+static size_t splat_layout(void* ws, int32_t W, int32_t H, int32_t*& winner) { return array_layout(ws, (size_t)W * H, winner); }
+static size_t gram_layout(void* ws, int32_t N, int32_t D, float*& slabs) { return array_layout(ws, (size_t)D * D * disp_blocks(N), slabs); }
 
 extern "C" {
 
@@ -231,7 +233,8 @@ int trase_splat_sizes(int32_t N, int32_t W, int32_t H, size_t* ws_bytes) {
     set_error("trase_splat_sizes: need N >= 0, W, H >= 1, W * H < 2^31 (got N %d, W %d, H %d)", N, W, H);
     return TRASE_ERR_INVALID;
   }
-  *ws_bytes = align_up(sizeof(int32_t) * (size_t)W * H);
+  int32_t* winner;
+  *ws_bytes = splat_layout(nullptr, W, H, winner);
   return TRASE_OK;
 }
 
@@ -251,10 +254,10 @@ int trase_splat_points(const float* points, int32_t N, const uint8_t* mask, cons
     S.images[l] = images_out[l];
   }
   const int HW = W * H;
-  if (!ws || ws_bytes < align_up(sizeof(int32_t) * (size_t)HW)) { set_error("trase_splat_points: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  int32_t* winner;
+  if (!ws || ws_bytes < splat_layout(ws, W, H, winner)) { set_error("trase_splat_points: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  int32_t* winner = static_cast<int32_t*>(ws);
   SplatProj P;
   for (int c = 0; c < 3; ++c)
     for (int r = 0; r < 4; ++r) P.m[4 * c + r] = full_proj[4 * r + (c == 2 ? 3 : c)];
@@ -286,7 +289,8 @@ int trase_feature_gram_sizes(int32_t N, int32_t D, size_t* ws_bytes) {
     set_error("trase_feature_gram_sizes: need N >= 2, 1 <= D <= %d (got N %d, D %d)", DISP_MAX_D, N, D);
     return TRASE_ERR_INVALID;
   }
-  *ws_bytes = gram_ws_bytes(N, D);
+  float* slabs;
+  *ws_bytes = gram_layout(nullptr, N, D, slabs);
   return TRASE_OK;
 }
 
@@ -297,11 +301,11 @@ int trase_feature_gram(const float* X, int32_t N, int32_t D, float* gram_mean_ou
     return TRASE_ERR_INVALID;
   }
   if (!X || !gram_mean_out) { set_error("trase_feature_gram: null pointer"); return TRASE_ERR_INVALID; }
-  if (!ws || ws_bytes < gram_ws_bytes(N, D)) { set_error("trase_feature_gram: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  float* slabs;
+  if (!ws || ws_bytes < gram_layout(ws, N, D, slabs)) { set_error("trase_feature_gram: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const int G = disp_blocks(N), chunk = (N + G - 1) / G, dp = disp_dpad(D);
-  float* slabs = static_cast<float*>(ws);
   float* gram = gram_mean_out;
   float* mean = gram_mean_out + (size_t)D * D;
 #define TRASE_DISP_DP(KERNEL, ...)                                                                                  \

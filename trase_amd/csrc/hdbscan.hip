@@ -291,18 +291,23 @@ __global__ __launch_bounds__(64) void hd_centre_kernel(const float* __restrict__
 }
 
 struct HdWs { float* part; int32_t* comp; int32_t* next; unsigned long long* best; };
-static size_t hd_ws_bytes(int n, int k) {
-  return align_up(sizeof(float) * (size_t)n * hd_splits(n) * k) + 2 * align_up(sizeof(int32_t) * (size_t)n) +
-         align_up(sizeof(unsigned long long) * (size_t)n);
+static size_t hd_layout(void* ws, int n, int k, HdWs& w) {
+  WsCursor c(ws);
+  w.part = c.take<float>((size_t)n * hd_splits(n) * k);
+  w.comp = c.take<int32_t>((size_t)n);
+  w.next = c.take<int32_t>((size_t)n);
+  w.best = c.take<unsigned long long>((size_t)n);
+  return c.bytes();
 }
-static HdWs hd_carve(void* ws, int n, int k) {
-  char* p = static_cast<char*>(ws);
-  HdWs w;
-  w.part = reinterpret_cast<float*>(p); p += align_up(sizeof(float) * (size_t)n * hd_splits(n) * k);
-  w.comp = reinterpret_cast<int32_t*>(p); p += align_up(sizeof(int32_t) * (size_t)n);
-  w.next = reinterpret_cast<int32_t*>(p); p += align_up(sizeof(int32_t) * (size_t)n);
-  w.best = reinterpret_cast<unsigned long long*>(p);
-  return w;
+static size_t hd_ws_bytes(int n, int k) { HdWs w; return hd_layout(nullptr, n, k, w); }
+// label centres: the label sums of up to LABEL_SUMS_MAX labels at a time (sums: laid out for a full batch) | the batch's labels
+struct CentresWs { LabelSumsWs sums; int32_t* sel; };
+static size_t centres_layout(void* ws, int N, int D, int C, CentresWs& w) {
+  const int S = C < LABEL_SUMS_MAX ? C : LABEL_SUMS_MAX;
+  WsCursor c(ws);
+  c.take<char>(label_sums_layout(ws, N, D, S, w.sums));      // the sums start at offset 0 and their size is a multiple of the alignment
+  w.sel = c.take<int32_t>((size_t)S);
+  return c.bytes();
 }
 static bool hd_limits_ok(int n, int D, int k) {
   return n >= 2 && n <= HD_MAX_N && D >= 1 && D <= HD_MAX_D && k >= 1 && k <= HD_MAX_K && k < n;
@@ -329,7 +334,7 @@ int trase_hdbscan_core(const float* X, int32_t n, int32_t D, int32_t k, float* c
   if (!ws || ws_bytes < hd_ws_bytes(n, k)) { set_error("trase_hdbscan_core: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  const HdWs w = hd_carve(ws, n, k);
+  HdWs w; hd_layout(ws, n, k, w);
   const int S = hd_splits(n), chunk = hd_chunk(n), dp = hd_dpad(D);
   const dim3 grid(hd_row_blocks(n), S), block(HD_ROWS);
   {
@@ -360,7 +365,7 @@ int trase_hdbscan_mst(const float* X, int32_t n, int32_t D, const float* core2, 
   if (!ws || ws_bytes < hd_ws_bytes(n, k)) { set_error("trase_hdbscan_mst: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  const HdWs w = hd_carve(ws, n, k);
+  HdWs w; hd_layout(ws, n, k, w);
   const int S = hd_splits(n), chunk = hd_chunk(n), dp = hd_dpad(D), rounds = hd_rounds(n);
   const dim3 grid(hd_row_blocks(n), S), block(HD_ROWS), grid1((n + 255) / 256), block1(256);
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(edge_keys_out);
@@ -392,8 +397,8 @@ int trase_label_centres_sizes(int32_t N, int32_t D, int32_t C, size_t* ws_bytes)
     set_error("trase_label_centres_sizes: need 1 <= C <= %d, 1 <= D <= %d (got N %d, D %d, C %d)", HD_MAX_CENTRES, HD_MAX_D, N, D, C);
     return TRASE_ERR_INVALID;
   }
-  const int S = C < LABEL_SUMS_MAX ? C : LABEL_SUMS_MAX;
-  *ws_bytes = label_sums_ws_bytes(N, D, S) + align_up(sizeof(int32_t) * (size_t)S);
+  CentresWs w;
+  *ws_bytes = centres_layout(nullptr, N, D, C, w);
   return TRASE_OK;
 }
 
@@ -404,23 +409,18 @@ int trase_label_centres(const float* X, int32_t N, int32_t D, const int32_t* lab
     return TRASE_ERR_INVALID;
   }
   if (!X || !labels || !centres_out) { set_error("trase_label_centres: null pointer"); return TRASE_ERR_INVALID; }
-  const int SM = C < LABEL_SUMS_MAX ? C : LABEL_SUMS_MAX;
-  const size_t sums_bytes = label_sums_ws_bytes(N, D, SM);
-  if (!ws || ws_bytes < sums_bytes + align_up(sizeof(int32_t) * (size_t)SM)) {
-    set_error("trase_label_centres: workspace too small");
-    return TRASE_ERR_WORKSPACE;
-  }
+  CentresWs w;
+  if (!ws || ws_bytes < centres_layout(ws, N, D, C, w)) { set_error("trase_label_centres: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  int32_t* sel = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + sums_bytes);
   for (int base = 0; base < C; base += LABEL_SUMS_MAX) {          // the per-cluster sums of K-means, 128 labels at a time
     const int S = C - base < LABEL_SUMS_MAX ? C - base : LABEL_SUMS_MAX;
     ProfScope ps("label_centres", stream);
-    hipLaunchKernelGGL(hd_iota_kernel, dim3(1), dim3(256), 0, stream, sel, S, base);
-    const float* total = nullptr;
-    const int rc = launch_label_sums(X, N, D, labels, sel, S, ws, &total, stream);
+    hipLaunchKernelGGL(hd_iota_kernel, dim3(1), dim3(256), 0, stream, w.sel, S, base);
+    if (S < LABEL_SUMS_MAX) label_sums_layout(ws, N, D, S, w.sums);      // a last, shorter batch packs its slabs closer: inside the full batch's bytes
+    const int rc = launch_label_sums(X, N, D, labels, w.sel, S, w.sums, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(hd_centre_kernel, dim3(S), dim3(64), 0, stream, total, S, D, base, centres_out);
+    hipLaunchKernelGGL(hd_centre_kernel, dim3(S), dim3(64), 0, stream, w.sums.total, S, D, base, centres_out);
     TRASE_POST_LAUNCH("label_centres", stream, 0);
   }
   return TRASE_OK;

@@ -351,28 +351,15 @@ static int knn_bits(int N) {
 
 struct KnnWs { KnnParams* prm; SortBufs sort; uint2* buckets; };
 
-static size_t knn_ws_bytes(int N) {
-  const size_t n = (size_t)(N > 0 ? N : 1);
-  const size_t nb = (n + 2047) / 2048;
-  return align_up(sizeof(KnnParams)) + align_up(sizeof(uint32_t) * n) * 4 + align_up(sizeof(uint32_t) * 256 * nb) +
-         align_up(sizeof(uint32_t) * 256 * 8) + align_up(sizeof(uint2) * ((size_t)1 << knn_bits(N)));
+// hist_copies = 1: these sorts take the three-launch passes
+static size_t knn_layout(void* ws, int N, KnnWs& w) {
+  WsCursor c(ws);
+  w.prm = c.take<KnnParams>(1);
+  sort_layout(c, w.sort, (size_t)(N > 0 ? N : 1), SORT_ALL, 8, 1);
+  w.buckets = c.take<uint2>((size_t)1 << knn_bits(N));
+  return c.bytes();
 }
-
-static KnnWs knn_carve(void* ptr, int N) {
-  const size_t n = (size_t)(N > 0 ? N : 1);
-  const size_t nb = (n + 2047) / 2048;
-  char* c = (char*)ptr;
-  KnnWs w;
-  w.prm = (KnnParams*)c; c += align_up(sizeof(KnnParams));
-  for (int i = 0; i < 2; ++i) { w.sort.keys[i] = (uint32_t*)c; c += align_up(sizeof(uint32_t) * n); }
-  for (int i = 0; i < 2; ++i) { w.sort.vals[i] = (uint32_t*)c; c += align_up(sizeof(uint32_t) * n); }
-  w.sort.hist = (uint32_t*)c; c += align_up(sizeof(uint32_t) * 256 * nb);
-  w.sort.digit_total = (uint32_t*)c; c += align_up(sizeof(uint32_t) * 256 * 8);
-  w.sort.nb_max = (int)nb;
-  w.sort.hist_copies = 1;
-  w.buckets = (uint2*)c;
-  return w;
-}
+static size_t knn_ws_bytes(int N) { KnnWs w; return knn_layout(nullptr, N, w); }
 
 }  // namespace trase
 
@@ -410,7 +397,7 @@ int trase_knn_dist2(const float* points, int32_t N, float* out, void* ws, size_t
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   LaunchCtx c{stream, 0, 0};
-  KnnWs w = knn_carve(ws, N);
+  KnnWs w; knn_layout(ws, N, w);
   const int bits = knn_bits(N);
   const uint32_t mask = (1u << bits) - 1u;
   int idx = 0;
@@ -443,7 +430,7 @@ int trase_knn_points(const float* p1, int32_t N1, const float* p2, int32_t N2, i
     launch_zero_bytes(dist_out, sizeof(float) * (size_t)N1 * K, stream);
     return TRASE_OK;
   }
-  KnnWs w = knn_carve(ws, N2);
+  KnnWs w; knn_layout(ws, N2, w);
   const int bits = knn_bits(N2);
   const uint32_t mask = (1u << bits) - 1u;
   int idx = 0;
@@ -506,7 +493,7 @@ int trase_lift_votes(const float* depth, int32_t W, int32_t H, const double* inv
   uint32_t mask = 0u;
   int idx = 0;
   if (N > 0) {          // N == 0: nothing to find -- no hash, every index -1, no votes
-    w = knn_carve(ws, N);
+    knn_layout(ws, N, w);
     const int bits = knn_bits(N);
     mask = (1u << bits) - 1u;
     int rc = knn_build(c, points, N, w, mask, bits, &idx);

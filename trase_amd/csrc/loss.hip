@@ -264,10 +264,14 @@ static LossWin make_window() {
   return w;
 }
 
-static size_t loss_ws_bytes(int C, int H, int W, int* nblocks) {
+struct LossWs { float* dmaps; float* partial; int nblocks; };      // three derivative maps (saved for the backward) | two partial sums per block
+static size_t loss_layout(void* ws, int C, int H, int W, LossWs& w) {
   const int bx = (W + LT - 1) / LT, by = (H + LT - 1) / LT;
-  if (nblocks) *nblocks = bx * by * C;
-  return align_up(sizeof(float) * 3 * (size_t)C * H * W) + align_up(sizeof(float) * 2 * (size_t)bx * by * C);
+  WsCursor c(ws);
+  w.nblocks = bx * by * C;
+  w.dmaps = c.take<float>(3 * (size_t)C * H * W);
+  w.partial = c.take<float>(2 * (size_t)bx * by * C);
+  return c.bytes();
 }
 
 }  // namespace trase
@@ -278,28 +282,27 @@ extern "C" {
 
 int trase_loss_sizes(int32_t C, int32_t H, int32_t W, size_t* ws_bytes) {
   if (!ws_bytes || C < 1 || H < 1 || W < 1) { set_error("trase_loss_sizes: bad arguments"); return TRASE_ERR_INVALID; }
-  *ws_bytes = loss_ws_bytes(C, H, W, nullptr);
+  LossWs w;
+  *ws_bytes = loss_layout(nullptr, C, H, W, w);
   return TRASE_OK;
 }
 
 static int loss_forward(const char* who, const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float* out2, double lambda_dssim,
                         void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
   if (!img || !gt || !out2 || C < 1 || H < 1 || W < 1) { set_error("%s: bad arguments", who); return TRASE_ERR_INVALID; }
-  int nblocks = 0;
-  if (!ws || ws_bytes < loss_ws_bytes(C, H, W, &nblocks)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
+  LossWs w;
+  if (!ws || ws_bytes < loss_layout(ws, C, H, W, w)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  float* dmaps = (float*)ws;
-  float* partial = (float*)((char*)ws + align_up(sizeof(float) * 3 * (size_t)C * H * W));
   const dim3 grid((W + LT - 1) / LT, (H + LT - 1) / LT, C);
   {
     ProfScope ps("ssim_fwd", stream);
-    hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(256), 0, stream, img, gt, H, W, make_window(), dmaps, partial);
+    hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(256), 0, stream, img, gt, H, W, make_window(), w.dmaps, w.partial);
   }
   TRASE_POST_LAUNCH("ssim_fwd", stream, 0);
   {
     ProfScope ps("loss_reduce", stream);
-    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, stream, partial, nblocks, 1.0f / ((float)C * H * W), out2,
+    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, stream, w.partial, w.nblocks, 1.0f / ((float)C * H * W), out2,
                        (float)lambda_dssim, (float)(1.0 - lambda_dssim));
   }
   TRASE_POST_LAUNCH("loss_reduce", stream, 0);
@@ -321,13 +324,14 @@ static int loss_backward(const char* who, const float* img, const float* gt, int
                          float s_l1, float s_ssim, const void* ws, size_t ws_bytes, float* dL_dimg, int32_t device,
                          trase_stream_t stream_) {
   if (!img || !gt || !g2 || !dL_dimg || C < 1 || H < 1 || W < 1) { set_error("%s: bad arguments", who); return TRASE_ERR_INVALID; }
-  if (!ws || ws_bytes < loss_ws_bytes(C, H, W, nullptr)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
+  LossWs w;
+  if (!ws || ws_bytes < loss_layout(const_cast<void*>(ws), C, H, W, w)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const dim3 grid((W + LT - 1) / LT, (H + LT - 1) / LT, C);
   {
     ProfScope ps("ssim_bwd", stream);
-    hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(256), 0, stream, img, gt, H, W, make_window(), (const float*)ws, g2,
+    hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(256), 0, stream, img, gt, H, W, make_window(), w.dmaps, g2,
                        1.0f / ((float)C * H * W), dL_dimg, g_stride, s_l1, s_ssim);
   }
   TRASE_POST_LAUNCH("ssim_bwd", stream, 0);

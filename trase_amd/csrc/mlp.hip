@@ -1330,20 +1330,22 @@ void mlp_fwd_rc_kernel(RcNet net, const float* __restrict__ x, const float* __re
   mlp_fwd_rc_body(ring, s_bias, net, x, t, t_stride, N, d_xyz, d_rot, d_scale, pe_store);
 }
 
-static size_t mlp_rc_ws_bytes() {
-  return align_up(sizeof(__bf16) * (size_t)RC_FWD_FRAGS * 512) + align_up(sizeof(float) * (MD * MW + HEADP));
-}
-static size_t mlp_ws_bytes_blk() {
-  size_t b = 0;
+// one forward workspace for both entry points: the training forward's block packing first, the inference RC stream behind it
+struct MlpFwdWs { __bf16* w[MD]; float* b[MD]; __bf16* w_head; float* b_head; __bf16* rc_stream; float* rc_bias; };
+static size_t mlp_fwd_layout(void* ws, MlpFwdWs& f) {
+  WsCursor c(ws);
   for (int l = 0; l < MD; ++l) {
     const int kp = l == 0 ? EMBP : (l == SKIP ? EMBP + MW : MW);
-    b += align_up(sizeof(__bf16) * (size_t)MW * kp) + align_up(sizeof(float) * MW);
+    f.w[l] = c.take<__bf16>((size_t)MW * kp);
+    f.b[l] = c.take<float>(MW);
   }
-  b += align_up(sizeof(__bf16) * (size_t)HEADP * MW) + align_up(sizeof(float) * HEADP);
-  return b;
+  f.w_head = c.take<__bf16>((size_t)HEADP * MW);
+  f.b_head = c.take<float>(HEADP);
+  f.rc_stream = c.take<__bf16>((size_t)RC_FWD_FRAGS * 512);
+  f.rc_bias = c.take<float>(MD * MW + HEADP);
+  return c.bytes();
 }
-// one forward workspace for both entry points: the training forward's block packing first, the inference RC stream behind it
-static size_t mlp_ws_bytes() { return mlp_ws_bytes_blk() + mlp_rc_ws_bytes(); }
+static size_t mlp_ws_bytes() { MlpFwdWs f; return mlp_fwd_layout(nullptr, f); }
 
 // ---- buffer plans of the training pair ---------------------------------------------------------------------
 struct MlpSaved {            // written by the training forward, read by the backward
@@ -1351,12 +1353,12 @@ struct MlpSaved {            // written by the training forward, read by the bac
 };
 static MlpSaved mlp_saved_plan(void* base, int N) {
   const size_t tiles = (size_t)(N + 31) / 32;
-  char* c = (char*)base;
+  WsCursor c(base);
   MlpSaved p;
-  p.actsT = (__bf16*)c; c += align_up(sizeof(__bf16) * MD * tiles * MW * 32);
-  p.peT = (__bf16*)c;   c += align_up(sizeof(__bf16) * tiles * EMBP * 32);
-  p.gates = (uint4*)c;  c += align_up(sizeof(uint4) * (size_t)MD * N * 2);
-  p.bytes = (size_t)(c - (char*)base);
+  p.actsT = c.take<__bf16>(MD * tiles * MW * 32);
+  p.peT = c.take<__bf16>(tiles * EMBP * 32);
+  p.gates = c.take<uint4>((size_t)MD * N * 2);
+  p.bytes = c.bytes();
   return p;
 }
 
@@ -1370,28 +1372,28 @@ struct MlpBwdPlan {
 };
 static MlpBwdPlan mlp_bwd_plan(void* base, int N) {
   const size_t tiles = (size_t)(N + 31) / 32;
-  char* c = (char*)base;
+  WsCursor c(base);
   MlpBwdPlan p;
   p.wt[0] = nullptr;
-  for (int l = 1; l < MD; ++l) { p.wt[l] = (__bf16*)c; c += align_up(sizeof(__bf16) * (size_t)MW * MW); }
-  p.wt_head = (__bf16*)c; c += align_up(sizeof(__bf16) * (size_t)MW * 16);
-  p.dzT = (__bf16*)c; c += align_up(sizeof(__bf16) * MD * tiles * MW * 32);
-  p.gT = (__bf16*)c;  c += align_up(sizeof(__bf16) * tiles * HEADP * 32);
-  p.tile_flags = (int*)c; c += align_up(sizeof(int) * (tiles + 1));
-  p.live_list = (int*)c;  c += align_up(sizeof(int) * (tiles + 1));
-  p.n_live = (int*)c;     c += align_up(sizeof(int) * 4);
+  for (int l = 1; l < MD; ++l) p.wt[l] = c.take<__bf16>((size_t)MW * MW);
+  p.wt_head = c.take<__bf16>((size_t)MW * 16);
+  p.dzT = c.take<__bf16>(MD * tiles * MW * 32);
+  p.gT = c.take<__bf16>(tiles * HEADP * 32);
+  p.tile_flags = c.take<int>(tiles + 1);
+  p.live_list = c.take<int>(tiles + 1);
+  p.n_live = c.take<int>(4);
   // one workgroup per CU for the big GEMMs (252 = 7 x 36), more and shorter ones for the narrow jobs
   const int gh_max = 36;
   p.Gh = (int)(tiles < (size_t)gh_max ? tiles : gh_max); p.Gp = (int)(tiles < 128 ? tiles : 128);
   p.Gd = p.Gp;
   if (p.Gh < 1) p.Gh = p.Gp = p.Gd = 1;
-  p.part_hidden = (float*)c; c += align_up(sizeof(float) * 7 * (size_t)p.Gh * wg_plane(MW, MW));
-  p.bias_hidden = (float*)c; c += align_up(sizeof(float) * 7 * (size_t)p.Gh * MW);
-  p.part_pe = (float*)c;     c += align_up(sizeof(float) * 2 * (size_t)p.Gp * wg_plane(MW, EMBP));
-  p.bias_pe = (float*)c;     c += align_up(sizeof(float) * (size_t)p.Gp * MW);
-  p.part_head = (float*)c;   c += align_up(sizeof(float) * (size_t)p.Gd * wg_plane(HEADP, MW));
-  p.bias_head = (float*)c;   c += align_up(sizeof(float) * (size_t)p.Gd * HEADP);
-  p.bytes = (size_t)(c - (char*)base);
+  p.part_hidden = c.take<float>(7 * (size_t)p.Gh * wg_plane(MW, MW));
+  p.bias_hidden = c.take<float>(7 * (size_t)p.Gh * MW);
+  p.part_pe = c.take<float>(2 * (size_t)p.Gp * wg_plane(MW, EMBP));
+  p.bias_pe = c.take<float>((size_t)p.Gp * MW);
+  p.part_head = c.take<float>((size_t)p.Gd * wg_plane(HEADP, MW));
+  p.bias_head = c.take<float>((size_t)p.Gd * HEADP);
+  p.bytes = c.bytes();
   return p;
 }
 
@@ -1413,15 +1415,14 @@ static int mlp_check_weights(const TraseMlpWeights* w, const char* who) {
 // pack the fp32 parameters into the forward layout inside `ws`
 static int mlp_pack_forward(const TraseMlpWeights* w, void* ws, MlpNet& net, hipStream_t stream) {
   MlpPackArgs pa;
-  char* c = (char*)ws;
+  MlpFwdWs f; mlp_fwd_layout(ws, f);
   for (int l = 0; l < MD; ++l) {
-    const int kp = l == 0 ? EMBP : (l == SKIP ? EMBP + MW : MW);
     pa.w[l] = w->weight[l]; pa.b[l] = w->bias[l];
-    pa.out_w[l] = (__bf16*)c; net.w[l] = (const __bf16*)c; c += align_up(sizeof(__bf16) * (size_t)MW * kp);
-    pa.out_b[l] = (float*)c; net.b[l] = (const float*)c; c += align_up(sizeof(float) * MW);
+    pa.out_w[l] = f.w[l]; net.w[l] = f.w[l];
+    pa.out_b[l] = f.b[l]; net.b[l] = f.b[l];
   }
-  pa.out_wh = (__bf16*)c; net.w_head = (const __bf16*)c; c += align_up(sizeof(__bf16) * (size_t)HEADP * MW);
-  pa.out_bh = (float*)c; net.b_head = (const float*)c;
+  pa.out_wh = f.w_head; net.w_head = f.w_head;
+  pa.out_bh = f.b_head; net.b_head = f.b_head;
   pa.w_warp = w->w_warp; pa.b_warp = w->b_warp; pa.w_rot = w->w_rotation; pa.b_rot = w->b_rotation;
   pa.w_scale = w->w_scaling; pa.b_scale = w->b_scaling;
   pa.emb = w->is_blender ? EMB_B : EMB_T;
@@ -1442,13 +1443,11 @@ static int mlp_pack_rc(const TraseMlpWeights* w, void* ws, RcNet& net, hipStream
   pa.w_warp = w->w_warp; pa.b_warp = w->b_warp; pa.w_rot = w->w_rotation; pa.b_rot = w->b_rotation;
   pa.w_scale = w->w_scaling; pa.b_scale = w->b_scaling;
   pa.emb = w->is_blender ? EMB_B : EMB_T;
-  char* c = (char*)ws + mlp_ws_bytes_blk();
-  __bf16* stream_w = (__bf16*)c; c += align_up(sizeof(__bf16) * (size_t)RC_FWD_FRAGS * 512);
-  float* bias = (float*)c;
-  net.wstream = stream_w; net.bias = bias; net.temb = nullptr;
+  MlpFwdWs f; mlp_fwd_layout(ws, f);
+  net.wstream = f.rc_stream; net.bias = f.rc_bias; net.temb = nullptr;
   {
     ProfScope ps("mlp_pack", stream);
-    hipLaunchKernelGGL(mlp_pack_rc_kernel, dim3((RC_FWD_FRAGS * 512 + 255) / 256), dim3(256), 0, stream, pa, stream_w, bias);
+    hipLaunchKernelGGL(mlp_pack_rc_kernel, dim3((RC_FWD_FRAGS * 512 + 255) / 256), dim3(256), 0, stream, pa, f.rc_stream, f.rc_bias);
   }
   TRASE_POST_LAUNCH("mlp_pack", stream, 0);
   return TRASE_OK;

@@ -231,18 +231,18 @@ using namespace trase;
 
 extern "C" {
 
-// workspace: A bf16 [N1][C] | B bf16 [N2][C] | inv1 [N1] | inv2 [N2] | best_j [N1] | cos [N1] | partial [ceil(N1/256)] | second_j [N1]
-static size_t nn_off(int C, int N1, int N2, size_t off[8]) {
-  size_t o = 0;
-  off[0] = o; o += align_up(sizeof(__bf16) * (size_t)N1 * C);
-  off[1] = o; o += align_up(sizeof(__bf16) * (size_t)N2 * C);
-  off[2] = o; o += align_up(sizeof(float) * (size_t)N1);
-  off[3] = o; o += align_up(sizeof(float) * (size_t)N2);
-  off[4] = o; o += align_up(sizeof(int32_t) * (size_t)N1);
-  off[5] = o; o += align_up(sizeof(float) * (size_t)N1);
-  off[6] = o; o += align_up(sizeof(float) * (size_t)((N1 + 255) / 256));
-  off[7] = o; o += align_up(sizeof(int32_t) * (size_t)N1);
-  return o;
+struct NnWs { __bf16 *A, *B; float *inv1, *inv2; int32_t* bj; float *cosv, *partial; int32_t* sj; };
+static size_t nn_layout(void* ws, int C, int N1, int N2, NnWs& w) {
+  WsCursor c(ws);
+  w.A = c.take<__bf16>((size_t)N1 * C);                 // [N1][C]
+  w.B = c.take<__bf16>((size_t)N2 * C);                 // [N2][C]
+  w.inv1 = c.take<float>((size_t)N1);
+  w.inv2 = c.take<float>((size_t)N2);
+  w.bj = c.take<int32_t>((size_t)N1);                   // best j
+  w.cosv = c.take<float>((size_t)N1);
+  w.partial = c.take<float>((size_t)((N1 + 255) / 256));
+  w.sj = c.take<int32_t>((size_t)N1);                   // second-best j
+  return c.bytes();
 }
 
 static int nn_check(int C, int N1, int N2) {
@@ -256,8 +256,8 @@ int trase_nnfm_sizes(int32_t C, int32_t N1, int32_t N2, size_t* ws_bytes) {
   int rc = nn_check(C, N1, N2);
   if (rc) return rc;
   if (!ws_bytes) { set_error("nnfm_sizes: null"); return TRASE_ERR_INVALID; }
-  size_t off[8];
-  *ws_bytes = nn_off(C, N1, N2, off);
+  NnWs w;
+  *ws_bytes = nn_layout(nullptr, C, N1, N2, w);
   return TRASE_OK;
 }
 
@@ -265,37 +265,32 @@ int trase_nnfm_forward(const float* feat1, const float* feats2, int32_t C, int32
                        size_t ws_bytes, int32_t device, trase_stream_t stream_) {
   int rc = nn_check(C, N1, N2);
   if (rc) return rc;
-  size_t off[8];
-  if (!feat1 || !feats2 || !loss || !ws || ws_bytes < nn_off(C, N1, N2, off)) { set_error("nnfm_forward: bad arguments / workspace too small"); return TRASE_ERR_WORKSPACE; }
+  NnWs w;
+  if (!feat1 || !feats2 || !loss || !ws || ws_bytes < nn_layout(ws, C, N1, N2, w)) { set_error("nnfm_forward: bad arguments / workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   LaunchCtx c{stream, 0, 0};
-  char* w = (char*)ws;
-  __bf16* A = (__bf16*)(w + off[0]); __bf16* B = (__bf16*)(w + off[1]);
-  float* inv1 = (float*)(w + off[2]); float* inv2 = (float*)(w + off[3]);
-  int32_t* bj = (int32_t*)(w + off[4]); float* cosv = (float*)(w + off[5]); float* partial = (float*)(w + off[6]);
-  int32_t* sj = (int32_t*)(w + off[7]);
   { ProfScope ps("nnfm_prep", stream);
-    hipLaunchKernelGGL(nnfm_prep_kernel, dim3((N1 + 63) / 64), dim3(256), 0, stream, feat1, C, N1, A, inv1);
-    hipLaunchKernelGGL(nnfm_prep_kernel, dim3((N2 + 63) / 64), dim3(256), 0, stream, feats2, C, N2, B, inv2); }
+    hipLaunchKernelGGL(nnfm_prep_kernel, dim3((N1 + 63) / 64), dim3(256), 0, stream, feat1, C, N1, w.A, w.inv1);
+    hipLaunchKernelGGL(nnfm_prep_kernel, dim3((N2 + 63) / 64), dim3(256), 0, stream, feats2, C, N2, w.B, w.inv2); }
   TRASE_POST_LAUNCH("nnfm_prep", stream, c.debug);
   { ProfScope ps("nnfm_match", stream);
     const dim3 grid((N1 + 32 * NN_WPB - 1) / (32 * NN_WPB)), block(NN_WPB * WAVE);
     switch (C / 64) {
-      case 1: hipLaunchKernelGGL(nnfm_match_kernel<4>, grid, block, 0, stream, A, N1, B, N2, bj, sj); break;
-      case 2: hipLaunchKernelGGL(nnfm_match_kernel<8>, grid, block, 0, stream, A, N1, B, N2, bj, sj); break;
-      case 3: hipLaunchKernelGGL(nnfm_match_kernel<12>, grid, block, 0, stream, A, N1, B, N2, bj, sj); break;
-      case 4: hipLaunchKernelGGL(nnfm_match_kernel<16>, grid, block, 0, stream, A, N1, B, N2, bj, sj); break;
-      case 5: hipLaunchKernelGGL(nnfm_match_kernel<20>, grid, block, 0, stream, A, N1, B, N2, bj, sj); break;
-      case 6: hipLaunchKernelGGL(nnfm_match_kernel<24>, grid, block, 0, stream, A, N1, B, N2, bj, sj); break;
-      case 7: hipLaunchKernelGGL(nnfm_match_kernel<28>, grid, block, 0, stream, A, N1, B, N2, bj, sj); break;
-      default: hipLaunchKernelGGL(nnfm_match_kernel<32>, grid, block, 0, stream, A, N1, B, N2, bj, sj); break;
+      case 1: hipLaunchKernelGGL(nnfm_match_kernel<4>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
+      case 2: hipLaunchKernelGGL(nnfm_match_kernel<8>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
+      case 3: hipLaunchKernelGGL(nnfm_match_kernel<12>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
+      case 4: hipLaunchKernelGGL(nnfm_match_kernel<16>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
+      case 5: hipLaunchKernelGGL(nnfm_match_kernel<20>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
+      case 6: hipLaunchKernelGGL(nnfm_match_kernel<24>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
+      case 7: hipLaunchKernelGGL(nnfm_match_kernel<28>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
+      default: hipLaunchKernelGGL(nnfm_match_kernel<32>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
     } }
   TRASE_POST_LAUNCH("nnfm_match", stream, c.debug);
   const int nb = (N1 + 255) / 256;
   { ProfScope ps("nnfm_finish", stream);
-    hipLaunchKernelGGL(nnfm_finish_kernel, dim3(nb), dim3(256), 0, stream, feat1, feats2, C, N1, N2, inv1, inv2, bj, sj, cosv, partial);
-    hipLaunchKernelGGL(nnfm_sum_kernel, dim3(1), dim3(256), 0, stream, partial, nb, N1, loss); }
+    hipLaunchKernelGGL(nnfm_finish_kernel, dim3(nb), dim3(256), 0, stream, feat1, feats2, C, N1, N2, w.inv1, w.inv2, w.bj, w.sj, w.cosv, w.partial);
+    hipLaunchKernelGGL(nnfm_sum_kernel, dim3(1), dim3(256), 0, stream, w.partial, nb, N1, loss); }
   TRASE_POST_LAUNCH("nnfm_finish", stream, c.debug);
   return TRASE_OK;
 }
@@ -304,14 +299,13 @@ int trase_nnfm_backward(const float* feat1, const float* feats2, int32_t C, int3
                         const void* ws, size_t ws_bytes, float* dL_dfeat1, int32_t device, trase_stream_t stream_) {
   int rc = nn_check(C, N1, N2);
   if (rc) return rc;
-  size_t off[8];
-  if (!feat1 || !feats2 || !g_loss || !dL_dfeat1 || !ws || ws_bytes < nn_off(C, N1, N2, off)) { set_error("nnfm_backward: bad arguments / workspace too small"); return TRASE_ERR_WORKSPACE; }
+  NnWs w;
+  if (!feat1 || !feats2 || !g_loss || !dL_dfeat1 || !ws || ws_bytes < nn_layout(const_cast<void*>(ws), C, N1, N2, w)) { set_error("nnfm_backward: bad arguments / workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  const char* w = (const char*)ws;
   { ProfScope ps("nnfm_bwd", stream);
     hipLaunchKernelGGL(nnfm_bwd_kernel, dim3((N1 + 255) / 256, 8), dim3(256), 0, stream, feat1, feats2, C, N1, N2,
-                       (const float*)(w + off[2]), (const float*)(w + off[3]), (const int32_t*)(w + off[4]), (const float*)(w + off[5]),
+                       w.inv1, w.inv2, w.bj, w.cosv,
                        g_loss, dL_dfeat1); }
   TRASE_POST_LAUNCH("nnfm_bwd", stream, 0);
   return TRASE_OK;

@@ -43,21 +43,21 @@ struct PairWs {
   int nblk;
 };
 
-static size_t pair_ws_carve(int S, PairWs* w, void* base) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
-  const int bx = (S + 255) / 256, by = (S + PH_ROWS - 1) / PH_ROWS;
-  const size_t o_fn = take(sizeof(float) * PH_F * (size_t)S), o_r = take(sizeof(float) * (size_t)S), o_a = take(sizeof(float) * (size_t)S),
-               o_b = take(sizeof(uint32_t) * PH_MAXW * (size_t)S), o_cp = take(sizeof(int) * (size_t)S), o_cn = take(sizeof(int) * (size_t)S),
-               o_c = take(sizeof(float) * 8), o_p = take(sizeof(double) * 8 * (size_t)bx * by),
-               o_d = take(sizeof(float) * PH_F * (size_t)S * PH_CHUNKS), o_k = take(sizeof(int) * PH_MAXN);
-  if (w && base) {
-    char* b = (char*)base;
-    w->fn = (float*)(b + o_fn); w->rinv = (float*)(b + o_r); w->a = (float*)(b + o_a); w->bits = (uint32_t*)(b + o_b);
-    w->colP = (int*)(b + o_cp); w->colN = (int*)(b + o_cn); w->consts = (float*)(b + o_c); w->partial = (double*)(b + o_p);
-    w->dpart = (float*)(b + o_d); w->rank = (int*)(b + o_k); w->nblk = bx * by;
-  }
-  return off;
+static size_t pair_ws_layout(void* ws, int S, PairWs& w) {
+  const size_t s = (size_t)S;
+  WsCursor c(ws);
+  w.nblk = ((S + 255) / 256) * ((S + PH_ROWS - 1) / PH_ROWS);
+  w.fn = c.take<float>(PH_F * s);
+  w.rinv = c.take<float>(s);
+  w.a = c.take<float>(s);
+  w.bits = c.take<uint32_t>(PH_MAXW * s);
+  w.colP = c.take<int>(s);
+  w.colN = c.take<int>(s);
+  w.consts = c.take<float>(8);
+  w.partial = c.take<double>(8 * (size_t)w.nblk);
+  w.dpart = c.take<float>(PH_F * s * PH_CHUNKS);
+  w.rank = c.take<int>(PH_MAXN);
+  return c.bytes();
 }
 
 // ---- mask statistics ---------------------------------------------------------------------------------------------------
@@ -637,7 +637,8 @@ int trase_mask_stats(const uint8_t* sam_masks, int32_t N, int64_t HW, int32_t* c
 
 int trase_compact_pixels_sizes(int64_t HW, size_t* ws_bytes) {
   if (!ws_bytes || HW < 1) { set_error("trase_compact_pixels_sizes: bad arguments"); return TRASE_ERR_INVALID; }
-  *ws_bytes = align_up(sizeof(uint32_t) * (size_t)((HW + CP_TILE - 1) / CP_TILE));
+  uint32_t* counts;
+  *ws_bytes = array_layout(nullptr, (size_t)((HW + CP_TILE - 1) / CP_TILE), counts);
   return TRASE_OK;
 }
 
@@ -645,13 +646,14 @@ int trase_compact_pixels(const uint8_t* flags, int64_t HW, int32_t* pix, int32_t
                          int32_t device, trase_stream_t stream_) {
   if (!flags || !pix || !count2 || HW < 1 || cap < 1) { set_error("trase_compact_pixels: bad arguments"); return TRASE_ERR_INVALID; }
   const int nblocks = (int)((HW + CP_TILE - 1) / CP_TILE);
-  if (!ws || ws_bytes < align_up(sizeof(uint32_t) * (size_t)nblocks)) { set_error("trase_compact_pixels: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  uint32_t* counts;
+  if (!ws || ws_bytes < array_layout(ws, (size_t)nblocks, counts)) { set_error("trase_compact_pixels: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   {
     ProfScope ps("compact_pixels", stream);
-    hipLaunchKernelGGL(cp_count_kernel, dim3(nblocks), dim3(256), 0, stream, flags, (long long)HW, (uint32_t*)ws);
-    hipLaunchKernelGGL(cp_scatter_kernel, dim3(nblocks), dim3(256), 0, stream, flags, (long long)HW, (const uint32_t*)ws, nblocks, pix, cap,
+    hipLaunchKernelGGL(cp_count_kernel, dim3(nblocks), dim3(256), 0, stream, flags, (long long)HW, counts);
+    hipLaunchKernelGGL(cp_scatter_kernel, dim3(nblocks), dim3(256), 0, stream, flags, (long long)HW, counts, nblocks, pix, cap,
                        count2);
   }
   TRASE_POST_LAUNCH("compact_pixels", stream, 0);
@@ -660,7 +662,8 @@ int trase_compact_pixels(const uint8_t* flags, int64_t HW, int32_t* pix, int32_t
 
 int trase_pairhead_sizes(int32_t S, size_t* ws_bytes) {
   if (!ws_bytes || S < 1) { set_error("trase_pairhead_sizes: bad arguments"); return TRASE_ERR_INVALID; }
-  *ws_bytes = pair_ws_carve(S, nullptr, nullptr);
+  PairWs w;
+  *ws_bytes = pair_ws_layout(nullptr, S, w);
   return TRASE_OK;
 }
 
@@ -684,10 +687,10 @@ int trase_pairhead_forward_n(const float* feats, int32_t F, int64_t HW, const ui
     set_error("trase_pairhead_forward: %d sampled masks (at most %d)", n_sampled_masks, 32 * PH_MAXW); return TRASE_ERR_INVALID;
   }
   PairWs w;
-  if (!ws || ws_bytes < pair_ws_carve(S, &w, ws)) { set_error("trase_pairhead_forward: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  if (!ws || ws_bytes < pair_ws_layout(ws, S, w)) { set_error("trase_pairhead_forward: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  // colP and colN are neighbours in the workspace (pair_ws_carve): one fill for both
+  // colP and colN are neighbours in the workspace (pair_ws_layout): one fill for both
   launch_zero_bytes(w.colP, (size_t)((char*)w.colN - (char*)w.colP) + sizeof(int) * (size_t)S, stream);
   const dim3 grid((S + 255) / 256, (S + PH_ROWS - 1) / PH_ROWS);
   {
@@ -721,7 +724,7 @@ int trase_pairhead_backward_n(int32_t F, int64_t HW, const int32_t* pix, int32_t
     set_error("trase_pairhead_backward: bad arguments"); return TRASE_ERR_INVALID;
   }
   PairWs w;
-  if (!ws || ws_bytes < pair_ws_carve(S, &w, const_cast<void*>(ws))) { set_error("trase_pairhead_backward: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  if (!ws || ws_bytes < pair_ws_layout(const_cast<void*>(ws), S, w)) { set_error("trase_pairhead_backward: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   if (!accumulate) launch_zero_bytes(dL_dfeats, sizeof(float) * (size_t)F * (size_t)HW, stream);
@@ -738,21 +741,23 @@ int trase_pairhead_backward_n(int32_t F, int64_t HW, const int32_t* pix, int32_t
 
 int trase_featnorm_sizes(int64_t HW, size_t* ws_bytes) {
   if (!ws_bytes || HW < 1) { set_error("trase_featnorm_sizes: bad arguments"); return TRASE_ERR_INVALID; }
-  *ws_bytes = align_up(sizeof(double) * 1024);
+  double* partial;
+  *ws_bytes = array_layout(nullptr, 1024, partial);
   return TRASE_OK;
 }
 
 int trase_featnorm_forward(const float* feats, int32_t F, int64_t HW, float* out2, void* ws, size_t ws_bytes, int32_t device,
                            trase_stream_t stream_) {
   if (!feats || !out2 || F < 1 || HW < 1) { set_error("trase_featnorm_forward: bad arguments"); return TRASE_ERR_INVALID; }
-  if (!ws || ws_bytes < align_up(sizeof(double) * 1024)) { set_error("trase_featnorm_forward: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  double* partial;
+  if (!ws || ws_bytes < array_layout(ws, 1024, partial)) { set_error("trase_featnorm_forward: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const int nblk = (int)std::min<long long>(1024, (HW + 255) / 256);
   {
     ProfScope ps("featnorm_fwd", stream);
-    hipLaunchKernelGGL(featnorm_fwd_kernel, dim3(nblk), dim3(256), 0, stream, feats, (long long)HW, F, (double*)ws);
-    hipLaunchKernelGGL(featnorm_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)ws, nblk, (long long)HW, out2);
+    hipLaunchKernelGGL(featnorm_fwd_kernel, dim3(nblk), dim3(256), 0, stream, feats, (long long)HW, F, partial);
+    hipLaunchKernelGGL(featnorm_final_kernel, dim3(1), dim3(256), 0, stream, partial, nblk, (long long)HW, out2);
   }
   TRASE_POST_LAUNCH("featnorm_fwd", stream, 0);
   return TRASE_OK;

@@ -355,12 +355,16 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void seg_assign_cosine_kernel(const
 
 using namespace trase;
 
-static size_t seg_ws_bytes(int32_t N, int32_t D, int32_t K, bool with_slots) {
+// per-block slabs | their sum | (the query mask and the label sums only) every sample's slot
+static size_t seg_layout(void* ws, int32_t N, int32_t D, int32_t K, bool with_slots, LabelSumsWs& w) {
   const size_t E = (size_t)seg_slab_floats(K, D);
-  size_t b = align_up(sizeof(float) * E * seg_blocks(N)) + align_up(sizeof(float) * E);
-  if (with_slots) b += align_up(sizeof(int32_t) * (size_t)N);
-  return b;
+  WsCursor c(ws);
+  w.slabs = c.take<float>(E * seg_blocks(N));
+  w.total = c.take<float>(E);
+  w.slot = with_slots ? c.take<int32_t>((size_t)N) : nullptr;
+  return c.bytes();
 }
+static size_t seg_ws_bytes(int32_t N, int32_t D, int32_t K, bool with_slots) { LabelSumsWs w; return seg_layout(nullptr, N, D, K, with_slots, w); }
 
 static int seg_launch_accum(int mode, const float* X, int32_t N, int32_t D, int32_t K, const float* centres, const int32_t* ids,
                             const int32_t* sel, int32_t* slot_out, float* slabs, const int32_t* state, hipStream_t stream) {
@@ -378,22 +382,16 @@ static int seg_launch_accum(int mode, const float* X, int32_t N, int32_t D, int3
 
 // The per-label sums of the query mask for callers outside this file (hdbscan.hip: the centres of labelled samples): launches
 // 1 and 2 with the slots taken from `sel` (S <= LABEL_SUMS_MAX labels on the device).  *total_out (inside ws) then holds the
-// S x D sums followed by the S counts.  ws: label_sums_ws_bytes(N, D, S).
+// S x D sums followed by the S counts.  w: label_sums_layout(ws, N, D, S, w).
 namespace trase {
-size_t label_sums_ws_bytes(int N, int D, int S) { return seg_ws_bytes(N, D, S, true); }
-int launch_label_sums(const float* X, int N, int D, const int32_t* ids, const int32_t* sel, int S, void* ws, const float** total_out,
-                      hipStream_t stream) {
+size_t label_sums_layout(void* ws, int N, int D, int S, LabelSumsWs& w) { return seg_layout(ws, N, D, S, true, w); }
+int launch_label_sums(const float* X, int N, int D, const int32_t* ids, const int32_t* sel, int S, const LabelSumsWs& w, hipStream_t stream) {
   static_assert(LABEL_SUMS_MAX == SEG_MAX_S, "label sums go through the query mask's accumulate kernel");
   const int G = seg_blocks(N), E = seg_slab_floats(S, D);
-  float* slabs = static_cast<float*>(ws);
-  char* p = static_cast<char*>(ws) + align_up(sizeof(float) * (size_t)E * G);
-  float* total = reinterpret_cast<float*>(p);
-  int32_t* slot = reinterpret_cast<int32_t*>(p + align_up(sizeof(float) * (size_t)E));
-  seg_launch_accum(1, X, N, D, S, nullptr, ids, sel, slot, slabs, nullptr, stream);
+  seg_launch_accum(1, X, N, D, S, nullptr, ids, sel, w.slot, w.slabs, nullptr, stream);
   TRASE_POST_LAUNCH("label_sums_accum", stream, 0);
-  hipLaunchKernelGGL(seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, stream, slabs, G, E, total, nullptr);
+  hipLaunchKernelGGL(seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, stream, w.slabs, G, E, w.total, nullptr);
   TRASE_POST_LAUNCH("label_sums_reduce", stream, 0);
-  *total_out = total;
   return TRASE_OK;
 }
 }  // namespace trase
@@ -422,22 +420,21 @@ int trase_kmeans_steps(const float* X, int32_t N, int32_t D, int32_t K, float* c
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const int G = seg_blocks(N), E = seg_slab_floats(K, D);
-  float* slabs = static_cast<float*>(ws);
-  float* total = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up(sizeof(float) * (size_t)E * G));
+  LabelSumsWs w; seg_layout(ws, N, D, K, false, w);
   for (int step = 0; step < n_steps; ++step) {
     {
       ProfScope ps("kmeans_assign_accum", stream);
-      seg_launch_accum(0, X, N, D, K, centres, nullptr, nullptr, ids_out, slabs, state, stream);
+      seg_launch_accum(0, X, N, D, K, centres, nullptr, nullptr, ids_out, w.slabs, state, stream);
     }
     TRASE_POST_LAUNCH("kmeans_assign_accum", stream, 0);
     {
       ProfScope ps("kmeans_reduce", stream);
-      hipLaunchKernelGGL(seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, stream, slabs, G, E, total, state);
+      hipLaunchKernelGGL(seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, stream, w.slabs, G, E, w.total, state);
     }
     TRASE_POST_LAUNCH("kmeans_reduce", stream, 0);
     {
       ProfScope ps("kmeans_finalize", stream);
-      hipLaunchKernelGGL(kmeans_finalize_kernel, dim3(1), dim3(1024), 0, stream, X, N, D, K, total, centres, reseed_key, tol,
+      hipLaunchKernelGGL(kmeans_finalize_kernel, dim3(1), dim3(1024), 0, stream, X, N, D, K, w.total, centres, reseed_key, tol,
                          iter_limit, state);
     }
     TRASE_POST_LAUNCH("kmeans_finalize", stream, 0);
@@ -467,23 +464,20 @@ int trase_segment_mask(const float* X, int32_t N, int32_t D, const int32_t* ids,
   TRASE_CHECK(hipSetDevice(device));
   if (S == 0) return launch_zero_bytes(mask_out, (size_t)N, stream);
   const int G = seg_blocks(N), E = seg_slab_floats(S, D);
-  float* slabs = static_cast<float*>(ws);
-  char* p = static_cast<char*>(ws) + align_up(sizeof(float) * (size_t)E * G);
-  float* total = reinterpret_cast<float*>(p);
-  int32_t* slot = reinterpret_cast<int32_t*>(p + align_up(sizeof(float) * (size_t)E));
+  LabelSumsWs w; seg_layout(ws, N, D, S, true, w);
   {
     ProfScope ps("segment_accum", stream);
-    seg_launch_accum(1, X, N, D, S, nullptr, ids, sel, slot, slabs, nullptr, stream);
+    seg_launch_accum(1, X, N, D, S, nullptr, ids, sel, w.slot, w.slabs, nullptr, stream);
   }
   TRASE_POST_LAUNCH("segment_accum", stream, 0);
   {
     ProfScope ps("segment_reduce", stream);
-    hipLaunchKernelGGL(seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, stream, slabs, G, E, total, nullptr);
+    hipLaunchKernelGGL(seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, stream, w.slabs, G, E, w.total, nullptr);
   }
   TRASE_POST_LAUNCH("segment_reduce", stream, 0);
   {
     ProfScope ps("segment_mask", stream);
-    hipLaunchKernelGGL(seg_mask_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, X, N, D, S, total, slot, threshold, mask_out);
+    hipLaunchKernelGGL(seg_mask_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, X, N, D, S, w.total, w.slot, threshold, mask_out);
   }
   TRASE_POST_LAUNCH("segment_mask", stream, 0);
   return TRASE_OK;

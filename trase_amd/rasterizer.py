@@ -397,7 +397,7 @@ def last_tile_row_loads(allreduce: bool = False) -> torch.Tensor:
     H, W = _Policy.last_hw
     gx8, gy8 = (W + 7) // 8, (H + 7) // 8
     cap = int(_Policy.last_capacity)
-    off = 2 * ((4 * cap + 255) // 256 * 256)              # BinBuf: point_list | pair_slot | ranges (trase_amd/csrc/api.hip carve_bin)
+    off = 2 * ((4 * cap + 255) // 256 * 256)              # BinBuf: point_list | pair_slot | ranges (trase_amd/csrc/api.hip bin_layout)
     rng = _Policy.last_bin[off:off + 8 * gx8 * gy8].view(torch.int32).reshape(gy8, gx8, 2).to(torch.int64)
     per_sub_row = (rng[..., 1] - rng[..., 0]).clamp_min(0).sum(dim=1)
     if gy8 % 2:
