@@ -729,6 +729,53 @@ int trase_compose_sizes(const int32_t* counts, int32_t n_parts, int32_t F, int64
 int trase_compose_part(const TraseComposePart* part, int64_t row_offset, int64_t P_total, float* means3D, float* scales,
                        float* rotations, float* opacities, float* shs, float* sh_objs, int32_t device, trase_stream_t stream);
 
+/* ---- segment output and scoring (render.py:344-366, :380-395; metrics_segmentation.py:33-48, :118-150) ---------------------
+ * trase_evaluate_frame: ONE launch over a W x H frame; a thread owns 4 consecutive pixels of a row (16-byte accesses where
+ * the planes allow it, scalar ones for row tails and unaligned rows).  Per pixel p:
+ *   inside = 1 - T(p) >= threshold   with T = final_T, or the final_T of `ws` (the img workspace of a forward that ran WITHOUT
+ *                                    TRASE_VARIANT_FORWARD_ONLY; ws, final_T and pred_in exclude each other); a NaN is outside;
+ *          = pred_in[p] != 0         with a given mask; = 1 with neither;
+ *   alpha = 1 - T;  pred_mask = inside (bytes 0 / 1);  pred_mask_u8 = 255 * inside in all three channels;
+ *   object[c] = inside ? image[c] : outside;  object_u8 = to8b(object) = trunc(255 * clip(x, 0, 1)) in fp32, a NaN gives 0.
+ *   image, object, pair_*: (3,H,W) fp32 planes; alpha (H,W) fp32; pred_in, pred_mask, gt_mask (H,W) bytes; *_u8 (H,W,3) bytes.
+ *   Every output may be NULL.  image == NULL: only the mask part runs.
+ * Scores, added to record[0 .. TRASE_EVAL_RECORD_WORDS) (device, int64, zeroed by the caller before the frame's first call):
+ *   gt_mask (non-zero = object): [0] += |inside & gt|, [1] += |inside | gt|, [2] += |inside == gt|, [3] += W * H;
+ *   gt_object (kind TRASE_EVAL_GT_*; fp32 values in [0,1]): [5] += 3 * W * H and, with quantize, [4] += sum (q(object) - q(gt))^2
+ *     over the 3 W H values, q(x) = trunc(clamp(x * 255 + 0.5, 0, 255)) in fp32 (torchvision's save_image; a NaN gives 0; 8-bit
+ *     inputs are used as stored) -- an exact integer.  Without quantize, partials[b] (device, float64,
+ *     TRASE_EVAL_MAX_BLOCKS slots, zeroed by the caller) = workgroup b's sum of (object - gt)^2 in float64, gt bytes read as
+ *     g / 255; the squared error is the sum of the slots in index order.
+ *   Words [6] and [7] are the caller's.  pair_object / pair_gt: the compared pair as fp32 planes (quantised: q / 255).
+ *   Counts are reduced per wave and per workgroup and added with one 64-bit integer atomic instruction per workgroup; there
+ *   are no float atomics: bitwise reproducible.  The inputs are read only.  Limits: W * H < 2^31. */
+#define TRASE_EVAL_RECORD_WORDS 8
+#define TRASE_EVAL_MAX_BLOCKS 2048
+enum { TRASE_EVAL_GT_NONE = 0, TRASE_EVAL_GT_F32_CHW = 1, TRASE_EVAL_GT_U8_CHW = 2, TRASE_EVAL_GT_U8_HWC = 3 };
+typedef struct TraseEvalFrame {
+  int32_t W;
+  int32_t H;
+  float threshold;
+  float outside;                    /* the value outside the mask: 0, or 1 with a white background */
+  int32_t gt_object_kind;           /* TRASE_EVAL_GT_* */
+  int32_t quantize;
+  const float* image;
+  const float* final_T;
+  const uint8_t* pred_in;
+  float* object;
+  float* alpha;
+  uint8_t* pred_mask;
+  uint8_t* object_u8;
+  uint8_t* pred_mask_u8;
+  const uint8_t* gt_mask;
+  const void* gt_object;
+  float* pair_object;
+  float* pair_gt;
+  int64_t* record;
+  double* partials;
+} TraseEvalFrame;
+int trase_evaluate_frame(const TraseEvalFrame* f, const TraseRastWorkspace* ws, int32_t device, trase_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

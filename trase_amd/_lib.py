@@ -119,6 +119,17 @@ class ComposePart(C.Structure):
     ]
 
 
+class EvalFrame(C.Structure):
+    _fields_ = [
+        ("W", C.c_int32), ("H", C.c_int32), ("threshold", C.c_float), ("outside", C.c_float),
+        ("gt_object_kind", C.c_int32), ("quantize", C.c_int32),
+        ("image", C.c_void_p), ("final_T", C.c_void_p), ("pred_in", C.c_void_p),
+        ("object", C.c_void_p), ("alpha", C.c_void_p), ("pred_mask", C.c_void_p), ("object_u8", C.c_void_p),
+        ("pred_mask_u8", C.c_void_p), ("gt_mask", C.c_void_p), ("gt_object", C.c_void_p),
+        ("pair_object", C.c_void_p), ("pair_gt", C.c_void_p), ("record", C.c_void_p), ("partials", C.c_void_p),
+    ]
+
+
 # every symbol include/trase_rast.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("trase_rast_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(RastSizes)]),
@@ -257,6 +268,7 @@ SYMBOLS = [
     ("trase_compose_sizes", C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     ("trase_compose_part", C.c_int, [C.POINTER(ComposePart), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_evaluate_frame", C.c_int, [C.POINTER(EvalFrame), C.POINTER(RastWorkspace), C.c_int32, C.c_void_p]),
     ("trase_adam_step", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_int32, C.c_void_p]),
     ("trase_adam_step_guarded", C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

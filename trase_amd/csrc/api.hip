@@ -775,4 +775,34 @@ int trase_prof_report(char* buf, size_t buf_bytes) {
   return TRASE_OK;
 }
 
+// ---- segment output and scoring (evaluate.hip) -----------------------------------------------------------------------------
+int trase_evaluate_frame(const TraseEvalFrame* f, const TraseRastWorkspace* ws, int32_t device, trase_stream_t stream_) {
+  if (!f) { set_error("trase_evaluate_frame: null frame"); return TRASE_ERR_INVALID; }
+  if (f->W < 1 || f->H < 1 || (int64_t)f->W * f->H >= ((int64_t)1 << 31)) {
+    set_error("trase_evaluate_frame: need W, H >= 1, W * H < 2^31 (got W %d, H %d)", f->W, f->H);
+    return TRASE_ERR_INVALID;
+  }
+  if (f->gt_object_kind < TRASE_EVAL_GT_NONE || f->gt_object_kind > TRASE_EVAL_GT_U8_HWC || (f->gt_object_kind != TRASE_EVAL_GT_NONE) != (f->gt_object != nullptr)) {
+    set_error("trase_evaluate_frame: gt_object and gt_object_kind (%d) do not agree", f->gt_object_kind);
+    return TRASE_ERR_INVALID;
+  }
+  if (ws && (f->final_T || f->pred_in)) { set_error("trase_evaluate_frame: a workspace, final_T and pred_in exclude each other"); return TRASE_ERR_INVALID; }
+  if (f->final_T && f->pred_in) { set_error("trase_evaluate_frame: final_T and pred_in exclude each other"); return TRASE_ERR_INVALID; }
+  if (!f->image && (f->object || f->object_u8 || f->gt_object || f->pair_object || f->pair_gt)) {
+    set_error("trase_evaluate_frame: object outputs and gt_object need an image"); return TRASE_ERR_INVALID;
+  }
+  if (f->alpha && !ws && !f->final_T) { set_error("trase_evaluate_frame: alpha needs a transmittance"); return TRASE_ERR_INVALID; }
+  if ((f->gt_mask || f->gt_object) && !f->record) { set_error("trase_evaluate_frame: a ground truth needs a record"); return TRASE_ERR_INVALID; }
+  if (f->gt_object && !f->quantize && !f->partials) { set_error("trase_evaluate_frame: the unquantised squared error needs its partial slots"); return TRASE_ERR_INVALID; }
+  const float* final_T = f->final_T;
+  if (ws) {
+    // the transmittance a forward WITHOUT TRASE_VARIANT_FORWARD_ONLY left in its img workspace
+    if (!ws->img || ws->img_bytes < img_bytes(f->W, f->H)) { set_error("trase_evaluate_frame: img workspace missing/too small"); return TRASE_ERR_WORKSPACE; }
+    ImgBuf im; img_layout(ws->img, f->W, f->H, im);
+    final_T = im.final_T;
+  }
+  TRASE_CHECK(hipSetDevice(device));
+  return launch_evaluate(*f, final_T, (hipStream_t)stream_);
+}
+
 }  // extern "C"

@@ -449,6 +449,8 @@ constexpr int LABEL_SUMS_MAX = 128;
 struct LabelSumsWs { float* slabs; float* total; int32_t* slot; };     // total: the S x D sums followed by the S counts
 size_t label_sums_layout(void* ws, int N, int D, int S, LabelSumsWs& w);
 int launch_label_sums(const float* X, int N, int D, const int32_t* ids, const int32_t* sel, int S, const LabelSumsWs& w, hipStream_t stream);
+// one pass over a frame: cut-out, mask, 8-bit frames and the frame's score record (evaluate.hip)
+int launch_evaluate(const TraseEvalFrame& f, const float* final_T, hipStream_t stream);
 int launch_split_pair_ids(const LaunchCtx& c, const uint32_t* sorted, int P, uint32_t* ids0, uint32_t* ids1);
 int radix_passes(int bit_lo, int bit_hi, int digit_bits = 8);
 // The depth sort (round 5).  Default: an order-preserving 27-bit key -- the float32 depth bits ABOVE those of the 0.2 near-cull

@@ -115,7 +115,8 @@ def chunk_ranges(P: int, chunks: int):
 class _RenderRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, d_xyz, f_dc, f_rest, opacity, scaling, d_scaling, rotation, d_rotation, gfeat, means2D,
-                raster_settings, norm_features, override_color=None, mask=None, se3=None, sh_dir_raw=False, fwd_only=False):
+                raster_settings, norm_features, override_color=None, mask=None, se3=None, sh_dir_raw=False, fwd_only=False,
+                keep_img=None):
         # override_color (P,3) / mask (P) bool / se3 (P,4,4): render()'s inference call patterns (gaussian_renderer/__init__.py:75-80,
         # :112-113, :123-135), sh_dir_raw: pipe.convert_SHs_python (:103-108) -- all inside the per-Gaussian kernels (round 6)
         lib = _lib.load()
@@ -161,7 +162,9 @@ class _RenderRaw(torch.autograd.Function):
         # fwd_only: render() was called under torch.no_grad() -- nobody will differentiate this forward, and the state only a
         # backward reads is not written (TRASE_VARIANT_FORWARD_ONLY).  (Decided by the caller: inside an autograd Function's
         # forward the grad mode is always off.)
-        if fwd_only:
+        # keep_img (a dict; trase_amd.evaluate.render_segment): the caller reads the transmittance this forward leaves in its img
+        # workspace, so the store that FORWARD_ONLY skips stays, and the workspace is handed over under "img"
+        if fwd_only and keep_img is None:
             s.variant |= _r_VARIANT_FORWARD_ONLY
 
         image, feats, depth = _output_maps(F, H, W, device, bool(s.tile_row_begin or s.tile_row_end))
@@ -222,7 +225,9 @@ class _RenderRaw(torch.autograd.Function):
         # radii back: the dict's `radii` / `visibility_filter` have mask.sum() entries.  The kernels keep full-size arrays (a
         # removed Gaussian has radius 0); the subset is taken here -- the one synchronising op of this path (the reference's
         # seven boolean indexings synchronise seven times).
-        radii_out = radii[mask] if mask is not None else radii
+        radii_out = radii[mask] if (mask is not None and keep_img is None) else radii
+        if keep_img is not None:               # (full-size radii: the subset's boolean index would synchronise)
+            keep_img["img"] = img
         ctx.mark_non_differentiable(radii_out)
         ctx.save_for_backward(xyz, d_xyz if d_xyz is not None else z, f_dc, f_rest, opacity, scaling,
                               d_scaling if d_scaling is not None else z, rotation,
@@ -378,7 +383,7 @@ class _RenderRaw(torch.autograd.Function):
                 if t is not None:
                     t.zero_()
         return (g_xyz if need[0] else None, g_dxyz, g_dc, g_rest, g_op, g_sc, g_dsc, g_rot, g_drot, g_feat,
-                g_m2d if need[10] else None, None, None, g_color, None, g_se3, None, None)
+                g_m2d if need[10] else None, None, None, g_color, None, g_se3, None, None, None)
 
 
 # ---- two views per launch sequence ---------------------------------------------------------------------------------------
@@ -479,8 +484,10 @@ def _fusable(pc, pipe, d_xyz, d_rotation, d_scaling, is_6dof, override_color, ma
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, d_xyz, d_rotation, d_scaling, is_6dof=False,
            scaling_modifier=1.0, override_color=None, mask=None, norm_gaussian_features=True,
-           is_smooth_gaussian_features=False, smooth_K=16):
-    """Same contract as the reference's render() (gaussian_renderer/__init__.py:37-155)."""
+           is_smooth_gaussian_features=False, smooth_K=16, _keep_img=None):
+    """Same contract as the reference's render() (gaussian_renderer/__init__.py:37-155).  ``_keep_img`` is private to
+    ``trase_amd.evaluate.render_segment``: the fused forward keeps its per-pixel transmittance and hands its img workspace
+    over in that dict; only the rasterizer's four outputs come back, with full-size radii, and nothing synchronises."""
     xyz = pc.get_xyz
     # The reference builds `zeros_like(xyz, requires_grad=True) + 0` (gaussian_renderer/__init__.py:48-52): a dummy whose VALUES
     # nobody reads -- the rasterizer returns the screen-space gradient through it and train.py reads `.grad`.  Here: a fresh
@@ -514,8 +521,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, d_xyz, d_rotation
             pc._xyz, None if is_6dof else T(d_xyz), pc._features_dc, pc._features_rest, pc._opacity, pc._scaling,
             None if cov_python else T(d_scaling), pc._rotation, None if cov_python else T(d_rotation), gfeat, screenspace_points,
             raster_settings, norm_gaussian_features, override_color, mask, T(d_xyz) if is_6dof else None, sh_py,
-            not torch.is_grad_enabled())
+            not torch.is_grad_enabled(), _keep_img)
+        if _keep_img is not None:
+            return {"render": rendered_image, "radii": radii, "render_gaussian_features": rendered_feats, "depth": depth}
     else:
+        if _keep_img is not None:
+            raise ValueError("render_segment: these arguments do not take the fused forward (see trase_amd.renderer._fusable)")
         # the reference's own composition around the (HIP) rasterizer
         rasterizer = GaussianRasterizer(raster_settings=raster_settings)
         if is_6dof:
