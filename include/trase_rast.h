@@ -776,6 +776,53 @@ typedef struct TraseEvalFrame {
 } TraseEvalFrame;
 int trase_evaluate_frame(const TraseEvalFrame* f, const TraseRastWorkspace* ws, int32_t device, trase_stream_t stream);
 
+/* ---- trajectory view and frame finish (utils/time_utils.py:375-396; gui.py:1154-1191, :1080-1122) ---------------------------
+ * Scratch of these entry points is passed as explicit buffers whose sizes are the constants below.
+ * trase_fps_sample: farthest-point sampling of the rows of `points` (fp32 (N,3)) with mask == NULL or mask[i] != 0, the
+ *   reference's loop at B = 1: out[0] = the start row (start_dev, a DEVICE pointer to one int64 row, if non-NULL, else `start`);
+ *   the running minimum distance of every candidate starts at 1e10 and is lowered on strict < to
+ *   d = (dx*dx + dy*dy) + dz*dz, every product and sum rounded to fp32 (no fused multiply-add: what numpy float32 gives bit
+ *   for bit); out[i + 1] = the arg-max, the LOWEST row among equal distances (once every distance is 0 the lowest candidate
+ *   row repeats).  out: npoint int64 rows of `points`.  npoint ordinary launches on the stream (npoint - 1 of up to
+ *   TRASE_FPS_MAX_BLOCKS workgroups and a last one of one workgroup), no cooperative launch, no host read.  The start row must
+ *   be a candidate (the caller's check).  Scratch: dist, N fp32; partial, 2 * TRASE_FPS_MAX_BLOCKS uint64.  Bitwise
+ *   reproducible.  Limits: 1 <= N < 2^31, 1 <= npoint <= TRASE_FPS_MAX_SAMPLES.
+ * trase_trajectory_append: slot_out (G,3) fp32 = points[rows[g]] (rows int64 on the device; a row outside [0, N) gives NaN).
+ * trase_trajectory_draw: the polylines of G trajectories over S samples, oldest first: sample s is row (first + s) % cap of
+ *   coords ((cap,G,3) fp32 world positions; a plain (S,G,3) array has first = 0, cap = S).  Three launches: winner (H * W int32
+ *   scratch, left holding the result) = -1; one wave per segment (g; s, s + 1) -- with S == 1 the single sample -- projects both
+ *   ends in float64, p = [x, y, z, 1] @ full_proj (HOST pointer, 16 doubles, row-major, row-vector convention), px = (p.x / p.w
+ *   + 1) / 2 * W, py likewise with H, no w > 0 test, truncated toward zero to integers, and draws
+ *     dx = |bx - ax| >= dy = |by - ay|: for every integer x from ax to bx, y = ay + sign(by - ay) * floor((2 |x - ax| dy + dx) / (2 dx))
+ *     (otherwise with the roles of x and y swapped; a == b is one pixel), in 64-bit integers, over the in-image part of the
+ *   major axis only, pixels outside the image dropped, with atomicMax(winner, g): the HIGHEST trajectory index wins a pixel.
+ *   A sample with a non-finite coordinate or one of magnitude >= 2^20 breaks its polyline: no segment it ends is drawn.
+ *   overlay_out (optional, (H,W,4) fp32) = (colors[winner], 1) where a line passes, zeros elsewhere; colors (G,3) fp32.
+ *   Limits: S <= cap <= TRASE_TRAJ_MAX_SAMPLES, G <= TRASE_TRAJ_MAX_TRACKS, W * H < 2^31.  Bitwise reproducible.
+ * trase_present_frame: out (H,W,3) fp32 = the frame as the viewer shows it, one launch.  image: (3,h,w) fp32 planes, or with
+ *   `depth` one (h,w) plane whose values v become (v - min) / (max - min + 1e-20) in all three channels, min and max over the
+ *   plane by two launches in front (integer atomics on the ordered-int image of the floats; a NaN takes no part; minmax: 2
+ *   int32 words of scratch).  Bilinear resize to (H,W) with ATen's fp32 arithmetic for align_corners = False: scale =
+ *   float(in) / out, src = max(fma(scale, dst + 0.5f, -0.5f), 0) (the product fused into the subtraction, as ATen's kernel is
+ *   compiled), i0 = int(src), i1 = min(i0 + 1, in - 1), l1 = src - i0,
+ *   l0 = 1 - l1, value = h0 * (w0 * a + w1 * b) + h1 * (w0 * c + w1 * d); equal sizes copy.  Then clamp to [0,1] (a NaN stays),
+ *   control_overlay ((H,W,3) or NULL): b * (sum of its channels == 0) + it; overlay ((H,W,4) or NULL): b * (1 - a) + rgb * a;
+ *   tint ((H,W,3) or NULL): b + tint_weight * tint, not clamped.  Every blend product and sum is rounded to fp32 on its own.
+ *   The inputs are read only.  Limits: h * w < 2^31, H * W < 2^31. */
+#define TRASE_FPS_MAX_BLOCKS 256
+#define TRASE_FPS_MAX_SAMPLES 65536
+#define TRASE_TRAJ_MAX_TRACKS 65536
+#define TRASE_TRAJ_MAX_SAMPLES 1024
+int trase_fps_sample(const float* points, int32_t N, const uint8_t* mask, int32_t start, const int64_t* start_dev, int32_t npoint,
+                     int64_t* out, float* dist, uint64_t* partial, int32_t device, trase_stream_t stream);
+int trase_trajectory_append(const float* points, int32_t N, const int64_t* rows, int32_t G, float* slot_out, int32_t device,
+                            trase_stream_t stream);
+int trase_trajectory_draw(const float* coords, int32_t S, int32_t G, int32_t first, int32_t cap, const double* full_proj, int32_t W,
+                          int32_t H, const float* colors, float* overlay_out, int32_t* winner, int32_t device, trase_stream_t stream);
+int trase_present_frame(const float* image, int32_t h, int32_t w, int32_t depth, int32_t H, int32_t W, const float* control_overlay,
+                        const float* overlay, const float* tint, float tint_weight, float* out, int32_t* minmax, int32_t device,
+                        trase_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
