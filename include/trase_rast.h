@@ -572,6 +572,28 @@ int trase_pairhead_forward_n(const float* feats, int32_t F, int64_t HW, const ui
 int trase_pairhead_backward_n(int32_t F, int64_t HW, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode, float positive_th,
                               float negative_th, int32_t use_weights, const float* out8, const float* g2, const void* ws,
                               size_t ws_bytes, int32_t accumulate, float* dL_dfeats, int32_t device, trase_stream_t stream);
+/* The same head for a feature image of ANOTHER size than the masks: feats is [F = 32][Hr][Wr], the masks, pix, S and S_dev stay at
+ * the masks' resolution h x w (pix ascending).  The column of a sampled pixel is the bilinear blend of its four taps in feats --
+ * torch's upsample_bilinear2d with align_corners = False (train.py:283-284's `interpolate`), source index fma(in / out, dst + 0.5,
+ * -0.5) clamped at 0 -- and the resized map is never formed.  Needs Hr * Wr < 2^31 and h * w < 2^31.
+ * trase_pairhead_sizes_resized: bytes of the workspace the two calls below share (the forward's, kept for the backward).
+ * trase_pairhead_forward_resized: out8 as trase_pairhead_forward_n.
+ * trase_pairhead_backward_resized: writes EVERY element of dL_dfeats [F][Hr][Wr] exactly once (no zero fill, no atomics: a pixel
+ *   gathers the sampled mask pixels it is a tap of, in a fixed order).  feats, out2 (of trase_featnorm_forward on the same image) and
+ *   g_reg (device float, dL/d regulariser) are all null, or all given: then the regulariser's gradient is added in the same pass.
+ * trase_pairhead_columns_resized: columns [S][F] = the un-normalised resized columns of the S pixels pix[] alone. */
+int trase_pairhead_sizes_resized(int32_t S, int32_t Hr, int32_t Wr, int32_t h, int32_t w, size_t* ws_bytes);
+int trase_pairhead_forward_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w,
+                                   const uint8_t* sam_masks, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
+                                   const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
+                                   float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
+                                   int32_t device, trase_stream_t stream);
+int trase_pairhead_backward_resized(int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const int32_t* pix, int32_t S,
+                                    const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
+                                    const float* out8, const float* g2, const void* ws, size_t ws_bytes, const float* feats,
+                                    const float* out2, const float* g_reg, float* dL_dfeats, int32_t device, trase_stream_t stream);
+int trase_pairhead_columns_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const int32_t* pix,
+                                   int32_t S, float* columns, int32_t device, trase_stream_t stream);
 int trase_featnorm_sizes(int64_t HW, size_t* ws_bytes);
 int trase_featnorm_forward(const float* feats, int32_t F, int64_t HW, float* out2, void* ws, size_t ws_bytes, int32_t device,
                            trase_stream_t stream);

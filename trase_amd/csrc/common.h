@@ -215,6 +215,20 @@ __device__ __forceinline__ unsigned long long lanemask_lt() {
   return (l == 0) ? 0ull : (~0ull >> (64 - l));
 }
 
+// Source taps of one axis of a bilinear resize (present_frame, the resized loss head): ATen's
+// area_pixel_compute_source_index for align_corners = False, as its kernel is compiled: the product is fused into the
+// subtraction.  The unfused value can differ by an ulp of src, i.e. 4e-6 in the weights at src >= 32, far more than the
+// roundings of the interpolation itself.  scale = float(in) / out.
+__host__ __device__ __forceinline__ void bilinear_source(float scale, int dst, int in, int& i0, int& i1, float& l0, float& l1) {
+  float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
+  src = src < 0.f ? 0.f : src;
+  i0 = (int)src;
+  if (i0 > in - 1) i0 = in - 1;                        // (cannot happen for dst < out; keeps every read inside the plane)
+  i1 = i0 < in - 1 ? i0 + 1 : i0;
+  l1 = src - (float)i0;
+  l0 = 1.0f - l1;
+}
+
 // float atomic add that must lower to global_atomic_add_f32 (no CAS loop)
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
 

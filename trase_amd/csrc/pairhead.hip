@@ -19,6 +19,14 @@
 //   ph_bwd          per sampled pixel t, all u: d f_t += coeff(t, u) f_u  (32 chunks of u, partials reduced in order)
 //   ph_scatter      back through the normalisation, scattered into the zero-filled (32, H, W) gradient image
 // plus featnorm_fwd / _bwd for the regulariser (1 - mean_p |F_p|)^2 (train.py:281-282).
+// The *_resized entry points run the same head on a feature image of ANOTHER size than the masks (train.py:283-284's bilinear
+// `interpolate`, which every --downsample_mask recipe needs) without forming the resized map: a resized column is four taps
+// of the (32, Hr, Wr) image, so
+//   ph_gather<true>  blends the four taps per channel, then normalises as above
+//   ph_tables/_slots per-axis (first destination, count) of every source row / column; sample index per mask pixel or -1
+//   ph_scatter<true> keeps the per-sample gradient v (S, 32) in the workspace
+//   ph_spread        one thread per pixel of the (32, Hr, Wr) gradient gathers its taps' h * w * v in a fixed order and
+//                    writes 32 channels once -- with the regulariser's term when asked: no zero fill, no atomics
 // Built with -ffp-contract=off: the weight arithmetic follows torch's op order; dot products use explicit fmaf.
 #include "common.h"
 
@@ -43,9 +51,8 @@ struct PairWs {
   int nblk;
 };
 
-static size_t pair_ws_layout(void* ws, int S, PairWs& w) {
+static void pair_ws_walk(WsCursor& c, int S, PairWs& w) {
   const size_t s = (size_t)S;
-  WsCursor c(ws);
   w.nblk = ((S + 255) / 256) * ((S + PH_ROWS - 1) / PH_ROWS);
   w.fn = c.take<float>(PH_F * s);
   w.rinv = c.take<float>(s);
@@ -57,6 +64,33 @@ static size_t pair_ws_layout(void* ws, int S, PairWs& w) {
   w.partial = c.take<double>(8 * (size_t)w.nblk);
   w.dpart = c.take<float>(PH_F * s * PH_CHUNKS);
   w.rank = c.take<int>(PH_MAXN);
+}
+static size_t pair_ws_layout(void* ws, int S, PairWs& w) {
+  WsCursor c(ws);
+  pair_ws_walk(c, S, w);
+  return c.bytes();
+}
+
+// the head on a (32, Hr, Wr) feature image with (h, w) masks: scale = float(in) / out per axis, as ATen takes it
+struct ResizeGeom { int Hr, Wr, h, w; float scale_h, scale_w; };
+static ResizeGeom resize_geom(int Hr, int Wr, int h, int w) { return ResizeGeom{Hr, Wr, h, w, (float)Hr / (float)h, (float)Wr / (float)w}; }
+
+struct ResizedWs {
+  PairWs pair;
+  float* v;                           // [S][32] gradient of the resized (un-normalised) columns
+  int* slot;                          // [h * w] index of the sample at a mask pixel, -1: not sampled
+  int* row_first; int* row_count;     // [Hr] mask rows whose upper tap is this source row: first, how many
+  int* col_first; int* col_count;     // [Wr] the same for columns
+};
+static size_t resized_ws_layout(void* ws, int S, const ResizeGeom& g, ResizedWs& r) {
+  WsCursor c(ws);
+  pair_ws_walk(c, S, r.pair);
+  r.v = c.take<float>(PH_F * (size_t)S);
+  r.slot = c.take<int>((size_t)g.h * g.w);
+  r.row_first = c.take<int>(g.Hr);
+  r.row_count = c.take<int>(g.Hr);
+  r.col_first = c.take<int>(g.Wr);
+  r.col_count = c.take<int>(g.Wr);
   return c.bytes();
 }
 
@@ -241,9 +275,33 @@ __global__ __launch_bounds__(256) void ph_rank_kernel(const uint8_t* __restrict_
   if (threadIdx.x == 0) consts[2] = (float)carry;
 }
 
+// the four taps of mask pixel p in a (Hr, Wr) plane and their weights (bilinear_source: ATen's align_corners = False rule)
+struct ResizeTaps { int o00, o01, o10, o11; float h0, h1, w0, w1; };
+__device__ __forceinline__ ResizeTaps resize_taps(const ResizeGeom& g, int p) {
+  const int y = p / g.w, x = p - y * g.w;
+  int y0, y1, x0, x1;
+  ResizeTaps t;
+  bilinear_source(g.scale_h, y, g.Hr, y0, y1, t.h0, t.h1);
+  bilinear_source(g.scale_w, x, g.Wr, x0, x1, t.w0, t.w1);
+  t.o00 = y0 * g.Wr + x0; t.o01 = y0 * g.Wr + x1; t.o10 = y1 * g.Wr + x0; t.o11 = y1 * g.Wr + x1;
+  return t;
+}
+__device__ __forceinline__ float resize_blend(const float* __restrict__ plane, const ResizeTaps& t) {
+  const float a = plane[t.o00], b = plane[t.o01], c = plane[t.o10], d = plane[t.o11];
+  float v;
+  {
+#pragma clang fp contract(fast)                        // as ATen's kernel is compiled; the rest of the file is contract(off)
+    v = t.h0 * (t.w0 * a + t.w1 * b) + t.h1 * (t.w0 * c + t.w1 * d);
+  }
+  return v;
+}
+
 // eight lanes per sampled pixel: lane l walks the masks n = l, l + 8, ... (scattered one-byte reads), the partial
-// membership words / size sums are combined with shuffles; four channels of the feature column per lane
-__global__ __launch_bounds__(256) void ph_gather_kernel(const float* __restrict__ feats, long long HW,
+// membership words / size sums are combined with shuffles; four channels of the feature column per lane.
+// RESIZED: feats is (32, g.Hr, g.Wr) and the column is the bilinear blend of its four taps; pix, HW and the masks stay at
+// mask resolution
+template <bool RESIZED>
+__global__ __launch_bounds__(256) void ph_gather_kernel(const float* __restrict__ feats, long long HW, ResizeGeom g,
                                                         const uint8_t* __restrict__ masks, int N, const int* __restrict__ rank,
                                                         const uint32_t* __restrict__ mask_size, const int32_t* __restrict__ pix,
                                                         int S_cap, const int* __restrict__ S_ptr, float* __restrict__ fn,
@@ -255,8 +313,15 @@ __global__ __launch_bounds__(256) void ph_gather_kernel(const float* __restrict_
   const long long p = pix[min(s, S - 1)];
   float x[4];
   float ss = 0.f;
+  if constexpr (RESIZED) {
+    const ResizeTaps t = resize_taps(g, (int)p);
+    const size_t plane = (size_t)g.Hr * g.Wr;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) { x[e] = feats[(size_t)(4 * l + e) * HW + p]; ss = fmaf(x[e], x[e], ss); }
+    for (int e = 0; e < 4; ++e) { x[e] = resize_blend(feats + (size_t)(4 * l + e) * plane, t); ss = fmaf(x[e], x[e], ss); }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { x[e] = feats[(size_t)(4 * l + e) * HW + p]; ss = fmaf(x[e], x[e], ss); }
+  }
   uint32_t b[PH_MAXW];
 #pragma unroll
   for (int k = 0; k < PH_MAXW; ++k) b[k] = 0u;
@@ -296,6 +361,59 @@ __global__ __launch_bounds__(256) void ph_gather_kernel(const float* __restrict_
     // per_pixel_mean_mask_size = sum(size of covering masks) / (cover count + 1e-9)   (utils/feature_utils.py:30-31)
     a[s] = (float)(long long)tot / ((float)cnt + 1e-9f);
   }
+}
+
+// the un-normalised resized columns alone, (S, 32): F.interpolate(feats)[:, sampled_pixel].T without the map
+__global__ __launch_bounds__(256) void ph_columns_kernel(const float* __restrict__ feats, ResizeGeom g, const int32_t* __restrict__ pix,
+                                                         int S, float* __restrict__ out) {
+  const int gid = blockIdx.x * 256 + threadIdx.x;
+  const int s = gid >> 3, l = gid & 7;
+  if (s >= S) return;
+  const ResizeTaps t = resize_taps(g, pix[s]);
+  const size_t plane = (size_t)g.Hr * g.Wr;
+  float x[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) x[e] = resize_blend(feats + (size_t)(4 * l + e) * plane, t);
+  *reinterpret_cast<float4*>(out + (size_t)s * PH_F + 4 * l) = make_float4(x[0], x[1], x[2], x[3]);
+}
+
+// smallest destination index d in [0, out] whose upper tap i0(d) is >= i (i0 is monotone in d: a correctly rounded fma is)
+__device__ __forceinline__ int first_dst_from(float scale, int in, int out, int i) {
+  int lo = 0, hi = out;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    int i0, i1; float l0, l1;
+    bilinear_source(scale, mid, in, i0, i1, l0, l1);
+    if (i0 >= i) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+// per source row / column: the destinations whose upper tap it is, [first, first + count) -- from the helper the forward's
+// taps come from, so the backward visits exactly the taps the forward read
+__global__ __launch_bounds__(256) void ph_tables_kernel(ResizeGeom g, int* __restrict__ row_first, int* __restrict__ row_count,
+                                                        int* __restrict__ col_first, int* __restrict__ col_count) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < g.Hr) {
+    const int a = first_dst_from(g.scale_h, g.Hr, g.h, i);
+    row_first[i] = a; row_count[i] = first_dst_from(g.scale_h, g.Hr, g.h, i + 1) - a;
+  }
+  if (i < g.Wr) {
+    const int a = first_dst_from(g.scale_w, g.Wr, g.w, i);
+    col_first[i] = a; col_count[i] = first_dst_from(g.scale_w, g.Wr, g.w, i + 1) - a;
+  }
+}
+// slot[p] = s with pix[s] == p, or -1: pix is ascending, so every mask pixel looks itself up (one write per element)
+__global__ __launch_bounds__(256) void ph_slots_kernel(const int32_t* __restrict__ pix, int S_cap, const int* __restrict__ S_ptr,
+                                                       int HW, int* __restrict__ slot) {
+  const int S = S_ptr ? min(*S_ptr, S_cap) : S_cap;            // device-side count (sync-free head) or the host's
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+  int lo = 0, hi = max(S, 0);
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (pix[mid] >= p) hi = mid; else lo = mid + 1;
+  }
+  slot[p] = (lo < S && pix[lo] == p) ? lo : -1;
 }
 
 // ptp_max = (max a)^2; w_max = max(1, ptp_max / (min non-zero a)^2); the matrix minimum of the clamped ratio is exactly 1
@@ -521,6 +639,8 @@ __global__ __launch_bounds__(256) void ph_bwd_kernel(const float* __restrict__ f
 
 // reduce the chunks in order, back through x -> x / max(|x|, eps), scatter into the gradient image.
 // One thread per (sampled pixel, channel): a 32-lane half wave owns a pixel and reduces <fn, d> with shuffles.
+// TO_WS: the per-sample vector is kept as row s of the (S, 32) array `dfeats` instead (the resized head spreads it over its taps)
+template <bool TO_WS>
 __global__ __launch_bounds__(256) void ph_scatter_kernel(const float* __restrict__ dpart, const float* __restrict__ fn,
                                                          const float* __restrict__ rinv, const int32_t* __restrict__ pix, int S_cap,
                                                          const int* __restrict__ S_ptr, long long HW, int accumulate,
@@ -539,8 +659,75 @@ __global__ __launch_bounds__(256) void ph_scatter_kernel(const float* __restrict
   if (!(r < 1e12f)) proj = 0.f;                             // |x| <= eps: the clamp is active, d x = r d
   if (s >= S) return;
   const float v = r * (d - f * proj);
+  if constexpr (TO_WS) { dfeats[(size_t)s * PH_F + c] = v; return; }
   float* o = dfeats + (size_t)c * HW + pix[ss];            // sampled pixels are distinct: no atomics
   *o = accumulate ? *o + v : v;
+}
+
+// The gradient of the (32, Hr, Wr) image under the resized head, one thread per pixel (Y, X), every element written once.
+// Mask row dy reads source row Y either as its upper tap (i0 == Y, weight h0 -- and h1 as well where the clamp made both taps
+// one row) or as its lower tap (i0 == Y - 1, weight h1); the tables give both runs, columns alike.  The candidates are visited
+// in a fixed order (lower-tap run before upper-tap run, ascending inside a run, rows outside columns) and those that are sampled
+// add h * w * v[slot]: the sum does not depend on how the work is scheduled.  REG: plus the regulariser's term of this pixel
+// (featnorm_bwd_kernel's arithmetic), whose 32 feature values are read here anyway.
+template <bool REG>
+__global__ __launch_bounds__(256) void ph_spread_kernel(const float* __restrict__ v, const int* __restrict__ slot,
+                                                        const int* __restrict__ row_first, const int* __restrict__ row_count,
+                                                        const int* __restrict__ col_first, const int* __restrict__ col_count,
+                                                        ResizeGeom g, const float* __restrict__ feats, const float* __restrict__ out2,
+                                                        const float* __restrict__ g_reg, float* __restrict__ dfeats) {
+  const int HW = g.Hr * g.Wr;
+  const int P = blockIdx.x * 256 + threadIdx.x;
+  if (P >= HW) return;
+  const int Y = P / g.Wr, X = P - Y * g.Wr;
+  float acc[PH_F];
+#pragma unroll
+  for (int c = 0; c < PH_F; ++c) acc[c] = 0.f;
+  for (int ky = 0; ky < 2; ++ky) {
+    const int sy = Y - 1 + ky;
+    if (sy < 0) continue;
+    const int dy0 = row_first[sy], dy1 = dy0 + row_count[sy];
+    for (int dy = dy0; dy < dy1; ++dy) {
+      int y0, y1; float h0, h1;
+      bilinear_source(g.scale_h, dy, g.Hr, y0, y1, h0, h1);
+      const float hy = ky == 0 ? h1 : (y1 == y0 ? h0 + h1 : h0);
+      for (int kx = 0; kx < 2; ++kx) {
+        const int sx = X - 1 + kx;
+        if (sx < 0) continue;
+        const int dx0 = col_first[sx], dx1 = dx0 + col_count[sx];
+        for (int dx = dx0; dx < dx1; ++dx) {
+          const int s = slot[dy * g.w + dx];
+          if (s < 0) continue;
+          int x0, x1; float w0, w1;
+          bilinear_source(g.scale_w, dx, g.Wr, x0, x1, w0, w1);
+          const float wt = hy * (kx == 0 ? w1 : (x1 == x0 ? w0 + w1 : w0));
+          const float4* vs = reinterpret_cast<const float4*>(v + (size_t)s * PH_F);
+#pragma unroll
+          for (int q = 0; q < PH_F / 4; ++q) {
+            const float4 u = vs[q];
+            acc[4 * q] = fmaf(wt, u.x, acc[4 * q]); acc[4 * q + 1] = fmaf(wt, u.y, acc[4 * q + 1]);
+            acc[4 * q + 2] = fmaf(wt, u.z, acc[4 * q + 2]); acc[4 * q + 3] = fmaf(wt, u.w, acc[4 * q + 3]);
+          }
+        }
+      }
+    }
+  }
+  if constexpr (REG) {
+    const float coef = g_reg[0] * (-2.0f * (1.0f - out2[1])) / (float)HW;
+    float x[PH_F];
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < PH_F; ++c) x[c] = feats[(size_t)c * HW + P];
+#pragma unroll
+    for (int c = 0; c < PH_F; ++c) ss = fmaf(x[c], x[c], ss);
+    const float n = sqrtf(ss);
+    const float k = (n > 0.f) ? coef / n : 0.f;
+#pragma unroll
+    for (int c = 0; c < PH_F; ++c) dfeats[(size_t)c * HW + P] = k * x[c] + acc[c];
+  } else {
+#pragma unroll
+    for (int c = 0; c < PH_F; ++c) dfeats[(size_t)c * HW + P] = acc[c];
+  }
 }
 
 // ---- feature-norm regulariser ----------------------------------------------------------------------------------------------
@@ -696,7 +883,7 @@ int trase_pairhead_forward_n(const float* feats, int32_t F, int64_t HW, const ui
   {
     ProfScope ps("pairhead_fwd", stream);
     hipLaunchKernelGGL(ph_rank_kernel, dim3(1), dim3(256), 0, stream, sampled_mask, N, w.rank, w.consts);
-    hipLaunchKernelGGL(ph_gather_kernel, dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, sam_masks, N, w.rank,
+    hipLaunchKernelGGL(ph_gather_kernel<false>, dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, ResizeGeom{}, sam_masks, N, w.rank,
                        mask_size, pix, S, (const int*)S_dev, w.fn, w.rinv, w.a, w.bits);
     hipLaunchKernelGGL(ph_consts_kernel, dim3(1), dim3(256), 0, stream, w.a, S, (const int*)S_dev, w.consts);
     hipLaunchKernelGGL(ph_flags_kernel, grid, dim3(256), 0, stream, w.fn, w.bits, S, (const int*)S_dev, positive_th, negative_th, mode, w.colP,
@@ -732,10 +919,131 @@ int trase_pairhead_backward_n(int32_t F, int64_t HW, const int32_t* pix, int32_t
     ProfScope ps("pairhead_bwd", stream);
     hipLaunchKernelGGL(ph_bwd_kernel, dim3((S + 255) / 256, PH_CHUNKS), dim3(256), 0, stream, w.fn, w.bits, w.a, w.consts, S, (const int*)S_dev,
                        positive_th, negative_th, mode, use_weights, w.colP, w.colN, out8, g2, w.dpart);
-    hipLaunchKernelGGL(ph_scatter_kernel, dim3((S * PH_F + 255) / 256), dim3(256), 0, stream, w.dpart, w.fn, w.rinv, pix, S, (const int*)S_dev,
+    hipLaunchKernelGGL(ph_scatter_kernel<false>, dim3((S * PH_F + 255) / 256), dim3(256), 0, stream, w.dpart, w.fn, w.rinv, pix, S, (const int*)S_dev,
                        (long long)HW, accumulate, dL_dfeats);
   }
   TRASE_POST_LAUNCH("pairhead_bwd", stream, 0);
+  return TRASE_OK;
+}
+
+// the argument rules the three *_resized entry points share; 0 when the sizes are usable
+static int resized_sizes_ok(const char* who, int32_t S, int32_t Hr, int32_t Wr, int32_t h, int32_t w) {
+  if (S < 1 || Hr < 1 || Wr < 1 || h < 1 || w < 1) {
+    set_error("%s: need S, Hr, Wr, h, w >= 1 (got S %d, features %d x %d, masks %d x %d)", who, S, Hr, Wr, h, w);
+    return TRASE_ERR_INVALID;
+  }
+  if ((int64_t)Hr * Wr >= ((int64_t)1 << 31) || (int64_t)h * w >= ((int64_t)1 << 31)) {
+    set_error("%s: need Hr * Wr < 2^31 and h * w < 2^31 (got features %d x %d, masks %d x %d)", who, Hr, Wr, h, w);
+    return TRASE_ERR_INVALID;
+  }
+  return TRASE_OK;
+}
+
+int trase_pairhead_sizes_resized(int32_t S, int32_t Hr, int32_t Wr, int32_t h, int32_t w, size_t* ws_bytes) {
+  if (!ws_bytes) { set_error("trase_pairhead_sizes_resized: null pointer"); return TRASE_ERR_INVALID; }
+  if (int rc = resized_sizes_ok("trase_pairhead_sizes_resized", S, Hr, Wr, h, w)) return rc;
+  ResizedWs r;
+  *ws_bytes = resized_ws_layout(nullptr, S, resize_geom(Hr, Wr, h, w), r);
+  return TRASE_OK;
+}
+
+int trase_pairhead_forward_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w,
+                                   const uint8_t* sam_masks, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
+                                   const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
+                                   float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
+                                   int32_t device, trase_stream_t stream_) {
+  if (!feats || !sam_masks || !sampled_mask || !mask_size || !pix || !out8) {
+    set_error("trase_pairhead_forward_resized: null pointer"); return TRASE_ERR_INVALID;
+  }
+  if (int rc = resized_sizes_ok("trase_pairhead_forward_resized", S, Hr, Wr, h, w)) return rc;
+  if (N < 1 || N > PH_MAXN || mode < 0 || mode > 2) { set_error("trase_pairhead_forward_resized: bad arguments"); return TRASE_ERR_INVALID; }
+  if (F != PH_F) { set_error("trase_pairhead_forward_resized: %d feature channels (compiled for %d)", F, PH_F); return TRASE_ERR_INVALID; }
+  if (n_sampled_masks < 0 || n_sampled_masks > 32 * PH_MAXW) {
+    set_error("trase_pairhead_forward_resized: %d sampled masks (at most %d)", n_sampled_masks, 32 * PH_MAXW); return TRASE_ERR_INVALID;
+  }
+  const ResizeGeom g = resize_geom(Hr, Wr, h, w);
+  ResizedWs r;
+  if (!ws || ws_bytes < resized_ws_layout(ws, S, g, r)) { set_error("trase_pairhead_forward_resized: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  const PairWs& p = r.pair;
+  const int HW = h * w;
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  launch_zero_bytes(p.colP, (size_t)((char*)p.colN - (char*)p.colP) + sizeof(int) * (size_t)S, stream);
+  const dim3 grid((S + 255) / 256, (S + PH_ROWS - 1) / PH_ROWS);
+  {
+    ProfScope ps("pairhead_fwd_resized", stream);
+    hipLaunchKernelGGL(ph_rank_kernel, dim3(1), dim3(256), 0, stream, sampled_mask, N, p.rank, p.consts);
+    // what the backward gathers through: written here, where the workspace is still the caller's to write
+    hipLaunchKernelGGL(ph_tables_kernel, dim3((std::max(Hr, Wr) + 255) / 256), dim3(256), 0, stream, g, r.row_first, r.row_count, r.col_first,
+                       r.col_count);
+    hipLaunchKernelGGL(ph_slots_kernel, dim3((HW + 255) / 256), dim3(256), 0, stream, pix, S, (const int*)S_dev, HW, r.slot);
+    hipLaunchKernelGGL(ph_gather_kernel<true>, dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, g, sam_masks, N, p.rank,
+                       mask_size, pix, S, (const int*)S_dev, p.fn, p.rinv, p.a, p.bits);
+    hipLaunchKernelGGL(ph_consts_kernel, dim3(1), dim3(256), 0, stream, p.a, S, (const int*)S_dev, p.consts);
+    hipLaunchKernelGGL(ph_flags_kernel, grid, dim3(256), 0, stream, p.fn, p.bits, S, (const int*)S_dev, positive_th, negative_th, mode, p.colP,
+                       p.colN, p.partial);
+    hipLaunchKernelGGL(ph_sum_kernel, grid, dim3(256), 0, stream, p.fn, p.bits, p.a, p.consts, S, (const int*)S_dev, positive_th, negative_th,
+                       mode, use_weights, p.colP, p.colN, p.partial);
+    hipLaunchKernelGGL(ph_final_kernel, dim3(1), dim3(256), 0, stream, p.partial, p.nblk, p.colP, p.colN, S, (const int*)S_dev, mode, p.consts,
+                       out8);
+  }
+  TRASE_POST_LAUNCH("pairhead_fwd_resized", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_pairhead_backward_resized(int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const int32_t* pix, int32_t S,
+                                    const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
+                                    const float* out8, const float* g2, const void* ws, size_t ws_bytes, const float* feats,
+                                    const float* out2, const float* g_reg, float* dL_dfeats, int32_t device, trase_stream_t stream_) {
+  if (!pix || !out8 || !g2 || !dL_dfeats) { set_error("trase_pairhead_backward_resized: null pointer"); return TRASE_ERR_INVALID; }
+  const bool reg = feats || out2 || g_reg;
+  if (reg && !(feats && out2 && g_reg)) {
+    set_error("trase_pairhead_backward_resized: the regulariser needs feats, out2 and g_reg together"); return TRASE_ERR_INVALID;
+  }
+  if (int rc = resized_sizes_ok("trase_pairhead_backward_resized", S, Hr, Wr, h, w)) return rc;
+  if (mode < 0 || mode > 2) { set_error("trase_pairhead_backward_resized: bad arguments"); return TRASE_ERR_INVALID; }
+  if (F != PH_F) { set_error("trase_pairhead_backward_resized: %d feature channels (compiled for %d)", F, PH_F); return TRASE_ERR_INVALID; }
+  const ResizeGeom g = resize_geom(Hr, Wr, h, w);
+  ResizedWs r;
+  if (!ws || ws_bytes < resized_ws_layout(const_cast<void*>(ws), S, g, r)) {
+    set_error("trase_pairhead_backward_resized: workspace too small"); return TRASE_ERR_WORKSPACE;
+  }
+  const PairWs& p = r.pair;
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    ProfScope ps("pairhead_bwd_resized", stream);
+    hipLaunchKernelGGL(ph_bwd_kernel, dim3((S + 255) / 256, PH_CHUNKS), dim3(256), 0, stream, p.fn, p.bits, p.a, p.consts, S, (const int*)S_dev,
+                       positive_th, negative_th, mode, use_weights, p.colP, p.colN, out8, g2, p.dpart);
+    hipLaunchKernelGGL(ph_scatter_kernel<true>, dim3((S * PH_F + 255) / 256), dim3(256), 0, stream, p.dpart, p.fn, p.rinv, pix, S,
+                       (const int*)S_dev, 0ll, 0, r.v);
+  }
+  {
+    ProfScope ps("pairhead_spread", stream);
+    const dim3 dense((unsigned)(((int64_t)Hr * Wr + 255) / 256));
+    if (reg)
+      hipLaunchKernelGGL(ph_spread_kernel<true>, dense, dim3(256), 0, stream, r.v, r.slot, r.row_first, r.row_count, r.col_first, r.col_count, g,
+                         feats, out2, g_reg, dL_dfeats);
+    else
+      hipLaunchKernelGGL(ph_spread_kernel<false>, dense, dim3(256), 0, stream, r.v, r.slot, r.row_first, r.row_count, r.col_first, r.col_count, g,
+                         feats, out2, g_reg, dL_dfeats);
+  }
+  TRASE_POST_LAUNCH("pairhead_bwd_resized", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_pairhead_columns_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const int32_t* pix,
+                                   int32_t S, float* columns, int32_t device, trase_stream_t stream_) {
+  if (!feats || !pix || !columns) { set_error("trase_pairhead_columns_resized: null pointer"); return TRASE_ERR_INVALID; }
+  if (int rc = resized_sizes_ok("trase_pairhead_columns_resized", S, Hr, Wr, h, w)) return rc;
+  if (F != PH_F) { set_error("trase_pairhead_columns_resized: %d feature channels (compiled for %d)", F, PH_F); return TRASE_ERR_INVALID; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    ProfScope ps("pairhead_columns_resized", stream);
+    hipLaunchKernelGGL(ph_columns_kernel, dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, resize_geom(Hr, Wr, h, w), pix, S, columns);
+  }
+  TRASE_POST_LAUNCH("pairhead_columns_resized", stream, 0);
   return TRASE_OK;
 }
 

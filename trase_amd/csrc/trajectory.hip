@@ -228,19 +228,6 @@ struct PresentArgs {
   float* out;                    // (H, W, 3)
 };
 
-// ATen's area_pixel_compute_source_index for align_corners = False, as its kernel is compiled: the product is fused into the
-// subtraction.  The unfused value can differ by an ulp of src, i.e. 4e-6 in the weights at src >= 32, far more than the
-// roundings of the interpolation itself.
-__device__ __forceinline__ void present_source(float scale, int dst, int in, int& i0, int& i1, float& l0, float& l1) {
-  float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;                        // (cannot happen for dst < out; keeps every read inside the plane)
-  i1 = i0 < in - 1 ? i0 + 1 : i0;
-  l1 = src - (float)i0;
-  l0 = 1.0f - l1;
-}
-
 __global__ __launch_bounds__(256) void present_kernel(PresentArgs a) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= a.H * a.W) return;
@@ -249,8 +236,8 @@ __global__ __launch_bounds__(256) void present_kernel(PresentArgs a) {
   int y0 = y, y1 = y, x0 = x, x1 = x;
   float hl0 = 1.f, hl1 = 0.f, wl0 = 1.f, wl1 = 0.f;
   if (!same) {
-    present_source(a.scale_h, y, a.h, y0, y1, hl0, hl1);
-    present_source(a.scale_w, x, a.w, x0, x1, wl0, wl1);
+    bilinear_source(a.scale_h, y, a.h, y0, y1, hl0, hl1);
+    bilinear_source(a.scale_w, x, a.w, x0, x1, wl0, wl1);
   }
   float mn = 0.f, den = 1.f;
   if (a.depth) {

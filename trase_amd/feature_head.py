@@ -13,8 +13,11 @@ kernels of ``csrc/pairhead.hip`` evaluate them on the fly:
                                                             mask_size=sizes)
     loss = loss_pos + loss_neg + opt.rfn * feature_norm_reg(full_res_rendered_features)
 
-``rendered_features`` is the (32, H, W) feature image at mask resolution (after the reference's bilinear
-``interpolate`` when the sizes differ, train.py:284).  There is no CPU path.
+``rendered_features`` is the (32, Hr, Wr) feature image as rendered.  When the masks have another size (every
+``--downsample_mask`` recipe: a half or a quarter, not always an integral ratio) the head takes each sampled pixel's column as
+the four bilinear taps train.py:283-284's ``interpolate`` would blend -- the resized map is never formed -- and the backward
+writes the full-resolution gradient in one dense pass without atomics; ``with_norm_reg=True`` then is the reference's
+composition: norm at render resolution, pairs at mask resolution.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -164,6 +167,90 @@ class _PairHead(torch.autograd.Function):
         return (d_feats,) + (None,) * 11
 
 
+class _PairHeadResized(torch.autograd.Function):
+    """_PairHead for features of another size than the masks: the sampled columns are bilinear taps of the (32, Hr, Wr) image,
+    and the backward writes every element of its gradient once (taps and, with_reg, the regulariser's term in one pass)."""
+
+    @staticmethod
+    def forward(ctx, feats, masks_u8, sampled_mask_u8, n_sampled, mask_size, pix, mode, pth, nth, use_w, with_reg, s_dev=None):
+        lib = _lib.load()
+        dev = feats.device
+        F, Hr, Wr = feats.shape
+        N, h, w = masks_u8.shape
+        S = pix.numel()
+        f = feats.detach().float().contiguous()
+        nbytes = C.c_size_t()
+        _lib.check(lib.trase_pairhead_sizes_resized(S, Hr, Wr, h, w, C.byref(nbytes)), "trase_pairhead_sizes_resized")
+        ws = _bytes(nbytes.value, dev)
+        out8 = torch.empty(8, device=dev)
+        d = _dev_index(dev)
+        _lib.check(lib.trase_pairhead_forward_resized(_lib.ptr(f), F, Hr, Wr, h, w, _lib.ptr(masks_u8), N, _lib.ptr(sampled_mask_u8),
+                                                      int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S, _lib.ptr(s_dev), int(mode),
+                                                      float(pth), float(nth), int(use_w), _lib.ptr(out8), _lib.ptr(ws), ws.numel(), d,
+                                                      _stream(dev)), "trase_pairhead_forward_resized")
+        ctx.s_dev = s_dev
+        sims = out8[4:6].clone()
+        ctx.mark_non_differentiable(sims)
+        ctx.cfg = (F, Hr, Wr, h, w, S, int(mode), float(pth), float(nth), int(use_w), bool(with_reg))
+        if not with_reg:
+            ctx.save_for_backward(ws, out8, pix)
+            return out8[0], out8[2], sims
+        # the regulariser of train.py:280-282 on the image as rendered (before the resize)
+        _lib.check(lib.trase_featnorm_sizes(Hr * Wr, C.byref(nbytes)), "trase_featnorm_sizes")
+        ws_r = _bytes(nbytes.value, dev)
+        out2 = torch.empty(2, device=dev)
+        _lib.check(lib.trase_featnorm_forward(_lib.ptr(f), F, Hr * Wr, _lib.ptr(out2), _lib.ptr(ws_r), ws_r.numel(), d, _stream(dev)),
+                   "trase_featnorm_forward")
+        ctx.save_for_backward(ws, out8, pix, f, out2)
+        return out8[0], out8[2], sims, out2[0]
+
+    @staticmethod
+    def backward(ctx, g_pos, g_neg, _g_sims, g_reg=None):
+        lib = _lib.load()
+        F, Hr, Wr, h, w, S, mode, pth, nth, use_w, with_reg = ctx.cfg
+        ws, out8, pix = ctx.saved_tensors[:3]
+        dev = ws.device
+        g2 = torch.stack([g_pos.reshape(()), g_neg.reshape(())]).float().contiguous()
+        d_feats = torch.empty((F, Hr, Wr), device=dev)
+        f = out2 = gg = None
+        if with_reg:
+            f, out2 = ctx.saved_tensors[3:]
+            gg = g_reg.reshape(1).float().contiguous()
+        _lib.check(lib.trase_pairhead_backward_resized(F, Hr, Wr, h, w, _lib.ptr(pix), S, _lib.ptr(ctx.s_dev), mode, pth, nth, use_w,
+                                                       _lib.ptr(out8), _lib.ptr(g2), _lib.ptr(ws), ws.numel(), _lib.ptr(f), _lib.ptr(out2),
+                                                       _lib.ptr(gg), _lib.ptr(d_feats), _dev_index(dev), _stream(dev)),
+                   "trase_pairhead_backward_resized")
+        return (d_feats,) + (None,) * 11
+
+
+@torch.no_grad()
+def resized_columns(rendered_features, size, sampled_pixel):
+    """``F.interpolate(rendered_features[None], size, mode="bilinear")[0][:, sampled_pixel].T`` as (S, 32) float32 without the
+    resized map: the un-normalised columns the head derives its similarities from, in boolean-index order (one synchronisation,
+    for S).  With ``size`` equal to the features' own it is plain indexing, as ``interpolate`` copies then."""
+    if rendered_features.device.type != "cuda":
+        raise RuntimeError("trase_amd.feature_head runs on the GPU only (there is no CPU path)")
+    h, w = int(size[0]), int(size[1])
+    if rendered_features.dim() != 3 or rendered_features.shape[0] != 32:
+        raise ValueError("rendered_features must be (32, Hr, Wr)")
+    if tuple(sampled_pixel.shape) != (h, w):
+        raise ValueError(f"sampled_pixel must be [{h}, {w}]")
+    dev = rendered_features.device
+    sp = (sampled_pixel != 0).to(dev)
+    F, Hr, Wr = rendered_features.shape
+    if (Hr, Wr) == (h, w):
+        return rendered_features[:, sp].T.float().contiguous()
+    pix = torch.nonzero(sp.reshape(-1)).reshape(-1).to(torch.int32)
+    out = torch.empty((pix.numel(), F), device=dev)
+    if pix.numel() == 0:
+        return out
+    f = rendered_features.float().contiguous()
+    lib = _lib.load()
+    _lib.check(lib.trase_pairhead_columns_resized(_lib.ptr(f), F, Hr, Wr, h, w, _lib.ptr(pix), pix.numel(), _lib.ptr(out),
+                                                  _dev_index(dev), _stream(dev)), "trase_pairhead_columns_resized")
+    return out
+
+
 def contrastive_head(rendered_features, sam_masks, sampled_pixel, sampled_mask, mode="soft", positive_th=0.75, negative_th=0.5,
                      use_weights=True, mask_size=None, with_norm_reg=False):
     """(loss_pos, loss_neg, pos_similarity, neg_similarity[, norm_reg]) of train.py:272-296:
@@ -171,16 +258,18 @@ def contrastive_head(rendered_features, sam_masks, sampled_pixel, sampled_mask, 
     ``C_F[C == 1].mean()``, ``C_F[C == 0].mean()`` for the matrices the reference derives from ``sam_masks``,
     ``sampled_pixel``, ``sampled_mask`` and the (32, H, W) features.  No synchronisation when ``sampled_pixel`` comes from
     ``get_sample_pixel_and_mask`` (it carries the draw's target count: the indices are compacted and counted on the device); one --
-    the number of sampled pixels -- for any other boolean mask (the reference synchronises at every boolean index).  ``with_norm_reg=True`` also returns the regulariser
-    ``(1 - rendered_features.norm(dim=0).mean()) ** 2`` (train.py:281-282) of the same image -- valid when the rendered
-    features already have the mask resolution, so that train.py:284's ``interpolate`` is the identity -- and shares one
-    dense gradient pass with the pair losses."""
+    the number of sampled pixels -- for any other boolean mask (the reference synchronises at every boolean index).
+    ``rendered_features`` is (32, Hr, Wr); where (Hr, Wr) is not the masks' (H, W) the sampled columns are those of train.py:284's
+    bilinear ``interpolate`` to (H, W), taken as four taps each.  ``with_norm_reg=True`` also returns the regulariser
+    ``(1 - rendered_features.norm(dim=0).mean()) ** 2`` (train.py:280-282) of the image as rendered, and shares one dense
+    gradient pass with the pair losses."""
     if mode not in _MODES:
         raise ValueError(f"contrastive mode {mode!r} (expected one of {sorted(_MODES)})")
     m = _masks_u8(sam_masks)
     N, H, W = m.shape
-    if rendered_features.dim() != 3 or tuple(rendered_features.shape[1:]) != (H, W) or rendered_features.shape[0] != 32:
-        raise ValueError(f"rendered_features must be (32, {H}, {W}) -- the mask resolution (train.py:284 interpolates to it)")
+    if rendered_features.dim() != 3 or rendered_features.shape[0] != 32 or min(rendered_features.shape[1:]) < 1:
+        raise ValueError("rendered_features must be (32, Hr, Wr)")
+    resized = tuple(rendered_features.shape[1:]) != (H, W)
     if rendered_features.device != m.device:
         raise ValueError("rendered_features and sam_masks live on different devices")
     if tuple(sampled_pixel.shape) != (H, W) or sampled_mask.numel() != N:
@@ -225,8 +314,9 @@ def contrastive_head(rendered_features, sam_masks, sampled_pixel, sampled_mask, 
             z = rendered_features.sum() * 0.0
             nan = torch.full((), float("nan"), device=dev)
             return (z, z, nan, nan, feature_norm_reg(rendered_features)) if with_norm_reg else (z, z, nan, nan)
-    res = _PairHead.apply(rendered_features, m, sm, n_sampled, mask_size.contiguous(), pix, _MODES[mode], positive_th, negative_th,
-                          1 if use_weights else 0, bool(with_norm_reg), s_dev)
+    res = (_PairHeadResized if resized else _PairHead).apply(rendered_features, m, sm, n_sampled, mask_size.contiguous(), pix,
+                                                             _MODES[mode], positive_th, negative_th, 1 if use_weights else 0,
+                                                             bool(with_norm_reg), s_dev)
     lp, ln, sims = res[:3]
     return (lp, ln, sims[0], sims[1], res[3]) if with_norm_reg else (lp, ln, sims[0], sims[1])
 
