@@ -193,6 +193,11 @@ int trase_rast_status(const TraseRastWorkspace* ws, int64_t status[3], trase_str
  * debugging -- the counterpart of reading the reference's geomBuffer; entries of culled Gaussians are undefined. */
 int trase_rast_geom_layout(int32_t P, int64_t off[6]);
 
+/* The same for the bin workspace of `capacity` pairs and T 8x8 sub-tiles: off[0] point_list u32[capacity], off[1] pair_slot
+ * u32[capacity], off[2] ranges uint2[T + 1] ([begin, end) of every sub-tile's list, row-major over the sub-tile grid, then
+ * the sentinel entry). */
+int trase_rast_bin_layout(int64_t capacity, int32_t T, int64_t off[3]);
+
 /* Stage 2: binning (tile lists in depth order) + alpha compositing. */
 int trase_rast_render(const TraseRastSettings* s, const TraseRastInputs* in, const TraseRastOutputs* out,
                       const TraseRastWorkspace* ws, trase_stream_t stream);

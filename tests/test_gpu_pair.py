@@ -101,3 +101,48 @@ def test_render_views_handles_an_odd_view_and_unfused_views():
     for x, y in zip(serial, batched):
         assert torch.equal(x, y)
     assert torch.equal(mixed[1], mixed_ref[1])
+
+
+def test_deferred_views_keep_their_converted_inputs_alive(monkeypatch):
+    """render_views under no_grad records both views before anything is launched.  An override colour given in float64 and an
+    is_6dof transform given as a non-contiguous slice reach the kernels as float32 contiguous COPIES that only the deferred
+    record refers to: it must hold them (the result alone could come out right by luck of the allocator)."""
+    from gaussian_renderer import render
+    from trase_amd import rasterizer as R
+    from trase_amd import renderer
+    from trase_amd.synthetic import SynthGaussianModel, SynthPipe, make_scene, orbit_camera
+    dev = torch.device("cuda", 0)
+    n, w, h = 256, 64, 48
+    pc = SynthGaussianModel(make_scene(n, feat_dim=32, seed=6, scale_mult=0.8).to(dev), requires_grad=False)
+    cams = [orbit_camera(w, h, angle=0.3 + 1.1 * k).to(dev) for k in range(2)]
+    bg = torch.zeros(3, device=dev)
+    g = torch.Generator().manual_seed(9)
+    colour = torch.rand(n, 3, generator=g, dtype=torch.float64).to(dev)
+    wide = torch.zeros(2, n, 4, 8, device=dev)
+    wide[..., :4] = torch.eye(4, device=dev) + 0.02 * torch.randn(2, n, 4, 4, generator=g).to(dev)
+    se3 = [wide[k, :, :, :4] for k in range(2)]
+    assert not se3[0].is_contiguous()
+    kw = dict(is_6dof=True, override_color=colour)
+    recorded = []
+    flush = renderer._flush_pair
+    monkeypatch.setattr(renderer, "_flush_pair", lambda recs: (recorded.extend(recs), flush(recs))[1])
+    R.set_sync(False, capacity=64 * n)
+    try:
+        with torch.no_grad():
+            serial = [render(c, pc, SynthPipe(), bg, se3[k], 0.0, 0.0, **kw) for k, c in enumerate(cams)]
+            serial = [{k: v.clone() for k, v in o.items() if k != "viewspace_points"} for o in serial]
+            paired = renderer.render_views(cams, pc, SynthPipe(), bg, se3, 0.0, 0.0, **kw)
+        R.check_overflow()
+    finally:
+        R.set_sync(True)
+    assert len(recorded) == 2
+    for k, rec in enumerate(recorded):
+        kept = {t.data_ptr(): t for t in rec["keep"] if torch.is_tensor(t)}
+        for field, given in (("colors_precomp", colour), ("d_xyz_se3", se3[k])):
+            p = getattr(rec["rec"], field)
+            assert p and p != given.data_ptr(), f"view {k}: {field} was meant to need a converted copy"
+            assert p in kept and kept[p].dtype is torch.float32 and kept[p].is_contiguous(), f"view {k}: nothing keeps the {field} copy alive"
+    for k in range(2):
+        for name in ("render", "render_gaussian_features", "depth", "radii", "visibility_filter"):
+            assert torch.equal(serial[k][name], paired[k][name]), f"view {k}: {name} differs between render_views and render()"
+    assert float(serial[0]["render"].abs().max()) > 0 and not torch.equal(serial[0]["render"], serial[1]["render"])

@@ -276,6 +276,50 @@ def test_edge_cases_empty_culled_and_huge():
     assert float(g[2].min()) > 0.9
 
 
+@pytest.mark.parametrize("feat", [0, 32])
+@pytest.mark.parametrize("policy", ["sync", "one-call"])
+@pytest.mark.parametrize("door", ["operator", "render"])
+def test_empty_scene_through_both_doors(door, policy, feat):
+    """No Gaussians at all, forward and backward, through GaussianRasterizer and through the fused render(), with the
+    synchronising capacity policy and with a known capacity (one call per direction): the maps are the background composite
+    (colour = background exactly, features and depth zero), the gradients are empty or zero."""
+    from diff_gaussian_rasterization import GaussianRasterizer
+    from gaussian_renderer import render
+    from trase_amd import rasterizer as R
+    from trase_amd import renderer
+    from trase_amd.synthetic import SynthGaussianModel, SynthPipe, make_scene, orbit_camera
+    dev = _dev()
+    w = h = 16
+    bg = torch.tensor([0.3, 0.6, 0.9], device=dev)
+    cam = orbit_camera(w, h, angle=0.4).to(dev)
+    R.set_sync(True) if policy == "sync" else R.set_sync(False, capacity=1024)
+    try:
+        if door == "operator":
+            e = lambda *s: torch.empty(*s, device=dev, requires_grad=True)
+            leaves = dict(means3D=e(0, 3), means2D=e(0, 3), shs=e(0, 16, 3), opacities=e(0, 1), scales=e(0, 3), rotations=e(0, 4))
+            if feat:
+                leaves["sh_objs"] = e(0, 1, feat)
+            img, radii, feats, depth = GaussianRasterizer(raster_settings=settings_for(cam, bg=(0.3, 0.6, 0.9), device=dev))(**leaves)
+            leaves = list(leaves.values())
+        else:
+            pc = SynthGaussianModel(make_scene(0, feat_dim=32, seed=1).to(dev))
+            renderer.set_forward_scope("all" if feat else "image")
+            o = render(cam, pc, SynthPipe(), bg, 0.0, 0.0, 0.0)
+            img, radii, feats, depth = o["render"], o["radii"], o["render_gaussian_features"], o["depth"]
+            leaves = pc.parameters() + [o["viewspace_points"]]
+            assert o["visibility_filter"].numel() == 0
+        assert radii.numel() == 0 and tuple(img.shape) == (3, h, w) and tuple(feats.shape) == (feat, h, w) and tuple(depth.shape) == (1, h, w)
+        assert torch.equal(img, bg[:, None, None].expand(3, h, w)), "colour is not the background"
+        assert float(depth.abs().max()) == 0 and (feat == 0 or float(feats.abs().max()) == 0)
+        (img.sum() + 2 * feats.sum() + 3 * depth.sum()).backward()
+        R.check_overflow()
+        for t in leaves:
+            assert t.grad is None or (t.grad.shape == t.shape and float(t.grad.abs().sum()) == 0), "gradient of an empty scene"
+    finally:
+        renderer.set_forward_scope("all")
+        R.set_sync(True)
+
+
 def test_argument_errors_match_reference_wording():
     from diff_gaussian_rasterization import GaussianRasterizer
     dev = _dev()

@@ -132,3 +132,36 @@ def test_strips_through_the_operator_entry_point(feat, image_only):
             continue
         scale = float(v.abs().max())
         assert float((acc[k] - v).abs().max()) <= 2e-5 * max(scale, 1e-12) + 1e-9, (k, float((acc[k] - v).abs().max()), scale)
+
+
+def test_bin_layout_offsets_describe_the_real_workspace():
+    """40 x 24: 5 x 3 sub-tiles, an odd number of sub-tile rows.  The `ranges` read through trase_rast_bin_layout partition
+    the culled pairs [0, R_eff) among the sub-tiles, and last_tile_row_loads (which reads them the same way) counts every pair."""
+    import ctypes as C
+    from diff_gaussian_rasterization import GaussianRasterizer
+    from tests.util import settings_for, small_case
+    from trase_amd import _lib
+    from trase_amd import rasterizer as R
+    dev = torch.device("cuda", 0)
+    w, h, T = 40, 24, 15
+    act, cam = small_case(n=64, w=w, h=h, feat=0, seed=5)
+    a = {k: v.to(dev) for k, v in act.items() if v is not None}
+    R.set_sync(True)
+    GaussianRasterizer(raster_settings=settings_for(cam, device=dev))(
+        means3D=a["means3D"], means2D=torch.zeros(64, 3, device=dev), shs=a["shs"], opacities=a["opacities"], scales=a["scales"],
+        rotations=a["rotations"])
+    r_eff = R.last_status()[2]
+    assert r_eff > 0
+    cap, binb = int(R._Policy.last_capacity), R._Policy.last_bin
+    off = (C.c_int64 * 3)()
+    assert _lib.load().trase_rast_bin_layout(cap, T, C.byref(off)) == 0
+    assert off[0] == 0 and off[1] >= 4 * cap and off[2] >= off[1] + 4 * cap and off[2] + 8 * (T + 1) <= binb.numel()
+    rng = binb[off[2]:off[2] + 8 * T].view(torch.int32).reshape(T, 2).cpu().tolist()
+    assert all(0 <= b <= e <= r_eff for b, e in rng), rng
+    edge = 0
+    for b, e in sorted(r for r in rng if r[1] > r[0]):          # the non-empty lists follow each other without a gap
+        assert b == edge, rng
+        edge = e
+    assert edge == r_eff, (rng, r_eff)
+    loads = R.last_tile_row_loads()
+    assert loads.numel() == 2 and int(loads.sum()) == r_eff

@@ -131,12 +131,24 @@ static int list_pack_bits(const TraseRastSettings* s, int P) {
   return lg < 1 ? 31 : 32 - lg;       // never 32: the kernels evaluate (1u << jb) and v >> jb
 }
 
-static int validate(const TraseRastSettings* s, const TraseRastInputs* in) {
+// what both input records are checked for first: sizes, the camera, the feature width
+template <class Inputs>
+static int validate_head(const TraseRastSettings* s, const Inputs* in) {
   if (!s || !in) { set_error("null settings/inputs"); return TRASE_ERR_INVALID; }
   if (in->P < 0 || s->image_width <= 0 || s->image_height <= 0) { set_error("bad sizes"); return TRASE_ERR_INVALID; }
   if (!s->bg || !s->viewmatrix || !s->projmatrix || !s->campos) { set_error("bg/viewmatrix/projmatrix/campos are required"); return TRASE_ERR_INVALID; }
   if (in->F != 0 && in->F != 16 && in->F != 32) { set_error("feature width %d not compiled in (0,16,32)", in->F); return TRASE_ERR_UNSUPPORTED; }
-  if (in->P == 0) return TRASE_OK;   // nothing to validate: empty tensors carry null pointers
+  return TRASE_OK;
+}
+static int check_sh_degree(const TraseRastSettings* s) {
+  if (s->sh_degree < 0 || s->sh_degree > 3) { set_error("sh_degree %d outside 0..3", s->sh_degree); return TRASE_ERR_INVALID; }
+  return TRASE_OK;
+}
+
+static int validate(const TraseRastSettings* s, const TraseRastInputs* in) {
+  int rc = validate_head(s, in);
+  if (rc) return rc;
+  if (in->P == 0) return TRASE_OK;   // nothing to validate: empty tensors carry null pointers (the degree included: validate_raw tests it first)
   if ((in->shs == nullptr) == (in->colors_precomp == nullptr)) {
     set_error("Please provide excatly one of either SHs or precomputed colors!");   // wording of the lineage's wrapper
     return TRASE_ERR_INVALID;
@@ -147,7 +159,8 @@ static int validate(const TraseRastSettings* s, const TraseRastInputs* in) {
     return TRASE_ERR_INVALID;
   }
   if (!in->means3D || !in->opacities) { set_error("means3D/opacities are required"); return TRASE_ERR_INVALID; }
-  if (s->sh_degree < 0 || s->sh_degree > 3) { set_error("sh_degree %d outside 0..3", s->sh_degree); return TRASE_ERR_INVALID; }
+  rc = check_sh_degree(s);
+  if (rc) return rc;
   if (in->shs && (in->M < (s->sh_degree + 1) * (s->sh_degree + 1) || in->M > 16)) {
     set_error("shs holds %d coefficients, degree %d needs %d (max 16)", in->M, s->sh_degree, (s->sh_degree + 1) * (s->sh_degree + 1));
     return TRASE_ERR_INVALID;
@@ -189,8 +202,8 @@ static int run_maybe_graphed(int entry_id, std::initializer_list<std::pair<const
   {   // the CALLER is capturing (a whole training iteration inside torch.cuda.graph): its graph takes the launches as they are --
       // a replay of our own cached graph cannot be enqueued on a capturing stream
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return body(stream);
-    (void)hipGetLastError();
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) (void)hipGetLastError();      // only the query's own failure is cleared: an earlier sticky error stays
+    else if (cs != hipStreamCaptureStatusNone) return body(stream);
   }
   std::string key((const char*)&entry_id, sizeof(entry_id));
   for (auto& p : parts) if (p.first) key.append((const char*)p.first, p.second); else key.append(p.second, '\0');
@@ -265,19 +278,141 @@ static int depth_order(const LaunchCtx& c, const TraseRastSettings* s, const Geo
                            (s->image_height + TILE - 1) / TILE, pack_bits);
 }
 
-enum { WS_GEOM = 1, WS_PRE = 2, WS_BIN = 4, WS_IMG = 8, WS_TMP = 16 };
-static int check_ws(const TraseRastInputs* in, const TraseRastSettings* s, const TraseRastWorkspace* ws, int need) {
+enum { WS_GEOM = 1, WS_PRE = 2, WS_BIN = 4, WS_IMG = 8, WS_TMP = 16, WS_BWD = 32 };     // WS_TMP / WS_BWD: tmp as stage-2 / as backward scratch
+static int check_ws(int P, int F, const TraseRastSettings* s, const TraseRastWorkspace* ws, int need) {
   if (!ws) { set_error("null workspace"); return TRASE_ERR_WORKSPACE; }
   const int gx = (s->image_width + SUB - 1) / SUB, gy = (s->image_height + SUB - 1) / SUB;
-  if ((need & WS_GEOM) && (!ws->geom || ws->geom_bytes < geom_bytes(in->P))) { set_error("geom workspace missing/too small"); return TRASE_ERR_WORKSPACE; }
-  if ((need & WS_PRE) && (!ws->pre || ws->pre_bytes < pre_bytes(in->P))) { set_error("pre workspace missing/too small"); return TRASE_ERR_WORKSPACE; }
+  if ((need & WS_GEOM) && (!ws->geom || ws->geom_bytes < geom_bytes(P))) { set_error("geom workspace missing/too small"); return TRASE_ERR_WORKSPACE; }
+  if ((need & WS_PRE) && (!ws->pre || ws->pre_bytes < pre_bytes(P))) { set_error("pre workspace missing/too small"); return TRASE_ERR_WORKSPACE; }
   if (need & (WS_BIN | WS_TMP)) {
     if (ws->capacity < 1 || ws->capacity > 0xfffffff0ll) { set_error("capacity out of range"); return TRASE_ERR_WORKSPACE; }
   }
   if ((need & WS_BIN) && (!ws->bin || ws->bin_bytes < bin_bytes(ws->capacity, gx * gy))) { set_error("bin workspace missing/too small"); return TRASE_ERR_WORKSPACE; }
   if ((need & WS_IMG) && (!ws->img || ws->img_bytes < img_bytes(s->image_width, s->image_height))) { set_error("img workspace missing/too small"); return TRASE_ERR_WORKSPACE; }
   if ((need & WS_TMP) && (!ws->tmp || ws->tmp_bytes < tmp_bytes(ws->capacity))) { set_error("tmp workspace missing/too small"); return TRASE_ERR_WORKSPACE; }
+  if ((need & WS_BWD) && (!ws->tmp || ws->tmp_bytes < bwd_tmp_bytes(P, F, ws->capacity))) { set_error("backward tmp workspace too small"); return TRASE_ERR_WORKSPACE; }
   return TRASE_OK;
+}
+
+// ---- one resolved call: what every entry point needs before its first launch -----------------------------------------------------
+struct Call {
+  LaunchCtx c;
+  int gx, gy;                // gx x gy 8x8 sub-tiles
+  int64_t cap;
+  GeomBuf g; BinBuf b; ImgBuf im; PreBuf pre; BwdBuf bw;      // carved only when `need` names them
+};
+// the launch context and the workspaces `need` names, carved (no checks: resolve(), or the caller, has made them)
+static void carve(Call& k, const TraseRastSettings* s, int P, int F, const TraseRastWorkspace* ws, int need, hipStream_t stream) {
+  k.c = LaunchCtx{stream, s->debug, s->variant};
+  k.cap = ws->capacity;
+  k.gx = (s->image_width + SUB - 1) / SUB; k.gy = (s->image_height + SUB - 1) / SUB;
+  if (need & WS_GEOM) geom_layout(ws->geom, P, k.g);
+  if (need & WS_PRE) pre_layout(ws->pre, P, k.pre);
+  if (need & WS_BIN) bin_layout(ws->bin, ws->capacity, k.gx * k.gy, k.b);
+  if (need & WS_IMG) img_layout(ws->img, s->image_width, s->image_height, k.im);
+  if (need & WS_BWD) bwd_layout(ws->tmp, P, F, ws->capacity, k.bw);
+}
+// checks the workspaces `need` names, then `last_check()` (an entry point's own refusals, which come behind the workspaces'),
+// selects the device and carves
+template <class Check>
+static int resolve(Call& k, const TraseRastSettings* s, int P, int F, const TraseRastWorkspace* ws, int need, hipStream_t stream,
+                   Check&& last_check) {
+  int rc = check_ws(P, F, s, ws, need);
+  if (!rc) rc = last_check();
+  if (rc) return rc;
+  TRASE_CHECK(hipSetDevice(s->device));
+  carve(k, s, P, F, ws, need, stream);
+  return TRASE_OK;
+}
+static int resolve(Call& k, const TraseRastSettings* s, int P, int F, const TraseRastWorkspace* ws, int need, hipStream_t stream) {
+  return resolve(k, s, P, F, ws, need, stream, [] { return (int)TRASE_OK; });
+}
+
+// Stage 1: per-Gaussian kernel (`per_gaussian(call, depth keys, key27)`: the one launch the two front doors differ in), depth
+// order, scan of the sub-tile counts
+template <class Launch>
+static int stage1(const TraseRastSettings* s, int P, int F, int32_t* radii, const TraseRastWorkspace* ws, hipStream_t stream,
+                  Launch&& per_gaussian) {
+  Call k;
+  int rc = resolve(k, s, P, F, ws, WS_GEOM | WS_PRE, stream);
+  if (rc) return rc;
+  if (P == 0) return launch_zero_bytes(k.g.hdr, sizeof(uint32_t) * HDR_WORDS, stream);   // (P > 0: the preprocess kernel clears it; a kernel, not a memset node: common.h)
+  const DepthSortCfg cfg = depth_sort_cfg(s->variant);
+  rc = per_gaussian(k, k.pre.sort.keys[strip_mode(s) ? 1 - cfg.start : cfg.start], cfg.key_bits == 27);
+  if (rc) return rc;
+  return depth_order(k.c, s, k.g, k.pre, P, radii, list_pack_bits(s, P));
+}
+
+// the input record of the compositing launchers: they read P, F and the feature rows
+static TraseRastInputs compositing_inputs(int P, int F, const float* feat_rows) {
+  TraseRastInputs in;
+  memset(&in, 0, sizeof(in));
+  in.P = P; in.M = 16; in.F = F; in.sh_objs = feat_rows;
+  return in;
+}
+
+// Stage 2: pair emit, sub-tile sort, ranges, compositing.  The caller has validated its input record.
+static int stage2(const TraseRastSettings* s, int P, int F, const float* feat_rows, const TraseRastOutputs* out,
+                  const TraseRastWorkspace* ws, hipStream_t stream) {
+  if (!out || !out->image || !out->depth || (P > 0 && !out->radii) || (F > 0 && !out->feats)) { set_error("null output"); return TRASE_ERR_INVALID; }
+  Call k;
+  int rc = resolve(k, s, P, F, ws, WS_GEOM | WS_PRE | WS_BIN | WS_IMG | WS_TMP, stream);
+  if (rc) return rc;
+  const TraseRastInputs in = compositing_inputs(P, F, feat_rows);
+  const LaunchCtx& c = k.c;
+  const GeomBuf& g = k.g;
+  BinBuf& b = k.b;
+  const int T = k.gx * k.gy;
+  b.id_end = k.pre.id_end;     // the forward turns packed list values into row slots (HDR_PACK)
+  PairBuf t; tmp_layout(ws->tmp, ws->capacity, t);
+  const uint32_t cap = (uint32_t)ws->capacity;
+  if (P > 0) {
+    int bits = 1;
+    while ((1 << bits) < T + 1) ++bits;          // keys 0..T (T = sentinel sub-tile)
+    // the sort carries each pair's emit-order slot (generated on the fly in the first pass); arrange
+    // the value ping-pong so that the last pass lands in the saved pair_slot array
+    const int passes = radix_passes(0, bits);
+    const int final_idx = passes & 1;
+    t.sort.vals[final_idx] = b.pair_slot;
+    t.sort.vals[final_idx ^ 1] = t.spare_vals;
+    rc = launch_emit_pairs(c, *s, g, out->radii, k.pre.sort.vals[0], P, k.pre, t.sort.keys[0], t.pair_gauss, cap, b.ranges,
+                           t.sort.vals[0]);
+    if (rc) return rc;
+    int idx = 0;
+    rc = radix_sort_pairs(c, t.sort, g.hdr + HDR_R_EFF, cap, 0, bits, false, &idx);
+    if (rc) return rc;
+    if (idx != final_idx) { set_error("internal: tile sort ended in buffer %d", idx); return TRASE_ERR_INVALID; }
+    // ranges only; with emit-order slots as list values the forward's staging step translates slot -> id
+    rc = launch_tile_ranges(c, t.sort.keys[idx], g.hdr + HDR_R_EFF, cap, b.ranges, T + 1, g.hdr + 16, false);
+    if (rc) return rc;
+    return launch_render_fwd(c, *s, in, *out, g, b, k.im, t.pair_gauss, (uint32_t)cap);
+  }
+  launch_zero_bytes(b.ranges, sizeof(uint2) * ((size_t)T + 1), stream);
+  return launch_render_fwd(c, *s, in, *out, g, b, k.im);
+}
+
+// What the compositing backward sees of a call's cotangents: the depth gradient only under TRASE_VARIANT_DEPTH_GRAD (lineage:
+// depth carries no gradient); a feature map the loss does not use (GAUSSIAN-state iterations) contributes nothing -- feature
+// width 0, the MFMA kernel's image-only scope
+struct Cotangents { TraseRastGrads g; TraseRastInputs in; };
+static Cotangents scope_cotangents(const TraseRastSettings* s, int P, int F, const float* feat_rows, const float* dL_dimage,
+                                   const float* dL_dfeats, const float* dL_ddepth) {
+  Cotangents ct;
+  memset(&ct.g, 0, sizeof(ct.g));
+  ct.g.dL_dimage = dL_dimage; ct.g.dL_dfeats = dL_dfeats;
+  ct.g.dL_ddepth = (s->variant & TRASE_VARIANT_DEPTH_GRAD) ? dL_ddepth : nullptr;
+  ct.in = compositing_inputs(P, dL_dfeats ? F : 0, feat_rows);
+  return ct;
+}
+
+// Compositing backward: one gradient row per (sub-tile, Gaussian) pair, written to the pair's emit-order slot; afterwards
+// every Gaussian sums its contiguous rows (launch_reduce_rows).  No atomics, bit-reproducible.
+static int compose_bwd(const Call& k, const TraseRastSettings* s, const Cotangents& ct, const float* out_depth) {
+  const BwdBuf& bw = k.bw;
+  if ((ct.in.F == 32 || ct.in.F == 0) && !valu_backward(s))
+    return launch_render_bwd_hw(k.c, *s, ct.in, k.g, k.b, k.im, ct.g, bw.rows, bw.row_flags, bw.flags_bytes, out_depth);
+  launch_zero_bytes(bw.row_flags, (size_t)k.cap, k.c.stream);
+  return launch_render_bwd_gs(k.c, *s, ct.in, k.g, k.b, k.im, ct.g, bw.rows, bw.row_flags, out_depth);
 }
 
 }  // namespace trase
@@ -313,23 +448,24 @@ int trase_rast_geom_layout(int32_t P, int64_t off[6]) {
   return TRASE_OK;
 }
 
+int trase_rast_bin_layout(int64_t capacity, int32_t T, int64_t off[3]) {
+  if (capacity < 1 || capacity > 0xfffffff0ll || T < 1 || !off) { set_error("trase_rast_bin_layout: bad arguments"); return TRASE_ERR_INVALID; }
+  const uintptr_t base = 256;      // as above
+  BinBuf b;
+  bin_layout((void*)base, capacity, T, b);
+  const void* const field[3] = {b.point_list, b.pair_slot, b.ranges};
+  for (int i = 0; i < 3; ++i) off[i] = (int64_t)((uintptr_t)field[i] - base);
+  return TRASE_OK;
+}
+
 int trase_rast_preprocess(const TraseRastSettings* s, const TraseRastInputs* in, const TraseRastOutputs* out,
-                          const TraseRastWorkspace* ws, trase_stream_t stream_) {
+                          const TraseRastWorkspace* ws, trase_stream_t stream) {
   int rc = validate(s, in);
   if (rc) return rc;
   if (!out || (in->P > 0 && !out->radii)) { set_error("radii output required"); return TRASE_ERR_INVALID; }
-  rc = check_ws(in, s, ws, WS_GEOM | WS_PRE);
-  if (rc) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(s->device));
-  LaunchCtx c{stream, s->debug, s->variant};
-  GeomBuf g; geom_layout(ws->geom, in->P, g);
-  PreBuf t; pre_layout(ws->pre, in->P, t);
-  if (in->P == 0) return launch_zero_bytes(g.hdr, sizeof(uint32_t) * HDR_WORDS, stream);   // (P > 0: the preprocess kernel clears it; a kernel, not a memset node: common.h)
-  const DepthSortCfg cfg = depth_sort_cfg(s->variant);
-  rc = launch_preprocess_fwd(c, *s, *in, out->radii, g, t.sort.keys[strip_mode(s) ? 1 - cfg.start : cfg.start], cfg.key_bits == 27);
-  if (rc) return rc;
-  return depth_order(c, s, g, t, in->P, out->radii, list_pack_bits(s, in->P));
+  return stage1(s, in->P, in->F, out->radii, ws, (hipStream_t)stream, [&](const Call& k, uint32_t* keys, bool key27) {
+    return launch_preprocess_fwd(k.c, *s, *in, out->radii, k.g, keys, key27);
+  });
 }
 
 int trase_rast_status(const TraseRastWorkspace* ws, int64_t status[3], trase_stream_t stream_) {
@@ -347,48 +483,9 @@ int trase_rast_status(const TraseRastWorkspace* ws, int64_t status[3], trase_str
 }
 
 int trase_rast_render(const TraseRastSettings* s, const TraseRastInputs* in, const TraseRastOutputs* out,
-                      const TraseRastWorkspace* ws, trase_stream_t stream_) {
-  int rc = validate(s, in);
-  if (rc) return rc;
-  if (!out || !out->image || !out->depth || (in->P > 0 && !out->radii) || (in->F > 0 && !out->feats)) { set_error("null output"); return TRASE_ERR_INVALID; }
-  rc = check_ws(in, s, ws, WS_GEOM | WS_PRE | WS_BIN | WS_IMG | WS_TMP);
-  if (rc) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(s->device));
-  LaunchCtx c{stream, s->debug, s->variant};
-  const int gx = (s->image_width + SUB - 1) / SUB, gy = (s->image_height + SUB - 1) / SUB;
-  const int T = gx * gy;
-  GeomBuf g; geom_layout(ws->geom, in->P, g);
-  BinBuf b; bin_layout(ws->bin, ws->capacity, T, b);
-  ImgBuf im; img_layout(ws->img, s->image_width, s->image_height, im);
-  PreBuf pre; pre_layout(ws->pre, in->P, pre);
-  b.id_end = pre.id_end;       // the forward turns packed list values into row slots (HDR_PACK)
-  PairBuf t; tmp_layout(ws->tmp, ws->capacity, t);
-  const uint32_t cap = (uint32_t)ws->capacity;
-  if (in->P > 0) {
-    int bits = 1;
-    while ((1 << bits) < T + 1) ++bits;          // keys 0..T (T = sentinel sub-tile)
-    // the sort carries each pair's emit-order slot (generated on the fly in the first pass); arrange
-    // the value ping-pong so that the last pass lands in the saved pair_slot array
-    const int passes = radix_passes(0, bits);
-    const int final_idx = passes & 1;
-    t.sort.vals[final_idx] = b.pair_slot;
-    t.sort.vals[final_idx ^ 1] = t.spare_vals;
-    rc = launch_emit_pairs(c, *s, g, out->radii, pre.sort.vals[0], in->P, pre, t.sort.keys[0], t.pair_gauss, cap, b.ranges,
-                           t.sort.vals[0]);
-    if (rc) return rc;
-    int idx = 0;
-    rc = radix_sort_pairs(c, t.sort, g.hdr + HDR_R_EFF, cap, 0, bits, false, &idx);
-    if (rc) return rc;
-    if (idx != final_idx) { set_error("internal: tile sort ended in buffer %d", idx); return TRASE_ERR_INVALID; }
-    // ranges only; with emit-order slots as list values the forward's staging step translates slot -> id
-    rc = launch_tile_ranges(c, t.sort.keys[idx], g.hdr + HDR_R_EFF, cap, b.ranges, T + 1, g.hdr + 16, false);
-    if (rc) return rc;
-    return launch_render_fwd(c, *s, *in, *out, g, b, im, t.pair_gauss, (uint32_t)cap);
-  } else {
-    launch_zero_bytes(b.ranges, sizeof(uint2) * ((size_t)T + 1), stream);
-  }
-  return launch_render_fwd(c, *s, *in, *out, g, b, im);
+                      const TraseRastWorkspace* ws, trase_stream_t stream) {
+  const int rc = validate(s, in);
+  return rc ? rc : stage2(s, in->P, in->F, in->sh_objs, out, ws, (hipStream_t)stream);
 }
 
 int trase_rast_forward(const TraseRastSettings* s, const TraseRastInputs* in, const TraseRastOutputs* out,
@@ -432,62 +529,34 @@ static int backward_impl(const TraseRastSettings* s, const TraseRastInputs* in, 
   int rc = validate(s, in);
   if (rc) return rc;
   if (!gr || !out || (in->P > 0 && !out->radii)) { set_error("null grads/outputs"); return TRASE_ERR_INVALID; }
-  rc = check_ws(in, s, ws, WS_GEOM | WS_PRE | WS_BIN | WS_IMG);
-  if (rc) return rc;
-  if (!ws->tmp || ws->tmp_bytes < bwd_tmp_bytes(in->P, in->F, ws->capacity)) { set_error("backward tmp workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(s->device));
-  LaunchCtx c{stream, s->debug, s->variant};
-  const int gx = (s->image_width + SUB - 1) / SUB, gy = (s->image_height + SUB - 1) / SUB;
-  GeomBuf g; geom_layout(ws->geom, in->P, g);
-  BinBuf b; bin_layout(ws->bin, ws->capacity, gx * gy, b);
-  ImgBuf im; img_layout(ws->img, s->image_width, s->image_height, im);
-  PreBuf pre; pre_layout(ws->pre, in->P, pre);
-  BwdBuf bw; bwd_layout(ws->tmp, in->P, in->F, ws->capacity, bw);
-  if (in->P == 0) return TRASE_OK;
-  TraseRastGrads g2 = *gr;
-  if (!(s->variant & TRASE_VARIANT_DEPTH_GRAD)) g2.dL_ddepth = nullptr;   // lineage: depth carries no gradient
-  TraseRastInputs in2 = *in;
-  bool zero_feats = false;
-  if (!g2.dL_dfeats) {
-    // feature map unused by the loss (GAUSSIAN state): its channels contribute nothing
-    in2.F = 0;
-    zero_feats = g2.dL_dsh_objs != nullptr && in->F > 0;
-    g2.dL_dsh_objs = nullptr;
-  }
-  if (zero_feats) launch_zero_bytes(gr->dL_dsh_objs, sizeof(float) * (size_t)in->F * in->P, stream);
-  // phase 1: one gradient row per (sub-tile, Gaussian) pair, written to the pair's emit-order slot;
-  // phase 2: every Gaussian sums its contiguous rows.  No atomics, bit-reproducible.
-  // F == 0 here also means "no feature cotangent" (GAUSSIAN-state iterations): the MFMA kernel's image-only scope
-  if ((in2.F == 32 || in2.F == 0) && !valu_backward(s)) {
-    rc = launch_render_bwd_hw(c, *s, in2, g, b, im, g2, bw.rows, bw.row_flags, bw.flags_bytes, out->depth);
-  } else {
-    launch_zero_bytes(bw.row_flags, (size_t)ws->capacity, stream);
-    rc = launch_render_bwd_gs(c, *s, in2, g, b, im, g2, bw.rows, bw.row_flags, out->depth);
-  }
+  Call k;
+  rc = resolve(k, s, in->P, in->F, ws, WS_GEOM | WS_PRE | WS_BIN | WS_IMG | WS_BWD, stream);
+  if (rc || in->P == 0) return rc;
+  const Cotangents ct = scope_cotangents(s, in->P, in->F, in->sh_objs, gr->dL_dimage, gr->dL_dfeats, gr->dL_ddepth);
+  float* const d_feats = gr->dL_dfeats ? gr->dL_dsh_objs : nullptr;
+  // feature map unused by the loss: the gradient of its rows is zero
+  if (!gr->dL_dfeats && gr->dL_dsh_objs && in->F > 0) launch_zero_bytes(gr->dL_dsh_objs, sizeof(float) * (size_t)in->F * in->P, stream);
+  rc = compose_bwd(k, s, ct, out->depth);
   if (rc) return rc;
   // a tile-row strip: the forward compacted the ids of the Gaussians with a pair in the strip in front of the depth order and
-  // sorted only those -- the ranks behind them hold nothing.  The reduction walks the live ranks only (round 5: it used to walk
-  // all P and read ids out of the unsorted tail: a memory fault for strips through THIS entry point; the raw entry point
-  // always did this); the rows it does not write -- Gaussians without a pair: zero gradient -- start at zero.
+  // sorted only those -- the ranks behind them hold nothing, so the reduction walks the live ranks only; the rows it does not
+  // write -- Gaussians without a pair: zero gradient -- start at zero.
   const int live_only = strip_mode(s) ? 1 : 0;
   if (live_only) {
-    launch_zero_bytes(bw.acc, sizeof(float) * BWD_ACC * (size_t)in->P, stream);
-    if (g2.dL_dsh_objs) launch_zero_bytes(g2.dL_dsh_objs, sizeof(float) * (size_t)in2.F * in->P, stream);
+    launch_zero_bytes(k.bw.acc, sizeof(float) * BWD_ACC * (size_t)in->P, stream);
+    if (d_feats) launch_zero_bytes(d_feats, sizeof(float) * (size_t)ct.in.F * in->P, stream);
   }
-  rc = launch_reduce_rows(c, g, pre, in->P, in2.F, bw.rows, bw.row_flags, bw.acc, g2.dL_dsh_objs, nullptr, 0, -1, -1, live_only);
+  rc = launch_reduce_rows(k.c, k.g, k.pre, in->P, ct.in.F, k.bw.rows, k.bw.row_flags, k.bw.acc, d_feats, nullptr, 0, -1, -1, live_only);
   if (rc) return rc;
-  return launch_preprocess_bwd(c, *s, *in, out->radii, g, bw.acc, *gr);
+  return launch_preprocess_bwd(k.c, *s, *in, out->radii, k.g, k.bw.acc, *gr);
 }
 
 // ---- render() with A1 fused in (raw parameters) ---------------------------------------------------------
 static int validate_raw(const TraseRastSettings* s, const TraseRastRawInputs* r) {
-  if (!s || !r) { set_error("null settings/inputs"); return TRASE_ERR_INVALID; }
-  if (r->P < 0 || s->image_width <= 0 || s->image_height <= 0) { set_error("bad sizes"); return TRASE_ERR_INVALID; }
-  if (!s->bg || !s->viewmatrix || !s->projmatrix || !s->campos) { set_error("bg/viewmatrix/projmatrix/campos are required"); return TRASE_ERR_INVALID; }
-  if (r->F != 0 && r->F != 16 && r->F != 32) { set_error("feature width %d not compiled in (0,16,32)", r->F); return TRASE_ERR_UNSUPPORTED; }
-  if (s->sh_degree < 0 || s->sh_degree > 3) { set_error("sh_degree %d outside 0..3", s->sh_degree); return TRASE_ERR_INVALID; }
-  if (r->P == 0) return TRASE_OK;
+  int rc = validate_head(s, r);
+  if (!rc) rc = check_sh_degree(s);
+  if (rc || r->P == 0) return rc;
   if (!r->xyz || !r->opacity || !r->scaling || !r->rotation || (!r->colors_precomp && (!r->features_dc || !r->features_rest))) {
     set_error("raw inputs: xyz/opacity/scaling/rotation and either features_dc + features_rest or colors_precomp are required"); return TRASE_ERR_INVALID;
   }
@@ -497,32 +566,14 @@ static int validate_raw(const TraseRastSettings* s, const TraseRastRawInputs* r)
   return TRASE_OK;
 }
 
-static TraseRastInputs raw_as_inputs(const TraseRastRawInputs* r) {
-  TraseRastInputs in;
-  memset(&in, 0, sizeof(in));
-  in.P = r->P; in.M = 16; in.F = r->F; in.sh_objs = r->featn;
-  return in;
-}
-
 int trase_rast_preprocess_raw(const TraseRastSettings* s, const TraseRastRawInputs* raw, const TraseRastOutputs* out,
-                              const TraseRastWorkspace* ws, trase_stream_t stream_) {
+                              const TraseRastWorkspace* ws, trase_stream_t stream) {
   int rc = validate_raw(s, raw);
   if (rc) return rc;
   if (!out || (raw->P > 0 && !out->radii)) { set_error("radii output required"); return TRASE_ERR_INVALID; }
-  const TraseRastInputs in = raw_as_inputs(raw);
-  rc = check_ws(&in, s, ws, WS_GEOM | WS_PRE);
-  if (rc) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(s->device));
-  LaunchCtx c{stream, s->debug, s->variant};
-  GeomBuf g; geom_layout(ws->geom, in.P, g);
-  PreBuf t; pre_layout(ws->pre, in.P, t);
-  if (in.P == 0) return launch_zero_bytes(g.hdr, sizeof(uint32_t) * HDR_WORDS, stream);   // (P > 0: the preprocess kernel clears it; a kernel, not a memset node: common.h)
-  const DepthSortCfg cfg = depth_sort_cfg(s->variant);
-  rc = launch_preprocess_fwd_raw(c, *s, *raw, out->radii, g, t.sort.keys[strip_mode(s) ? 1 - cfg.start : cfg.start], cfg.key_bits == 27, 0u,
-                                 depth_dead_key(cfg.key_bits == 27));
-  if (rc) return rc;
-  return depth_order(c, s, g, t, in.P, out->radii, list_pack_bits(s, in.P));
+  return stage1(s, raw->P, raw->F, out->radii, ws, (hipStream_t)stream, [&](const Call& k, uint32_t* keys, bool key27) {
+    return launch_preprocess_fwd_raw(k.c, *s, *raw, out->radii, k.g, keys, key27, 0u, depth_dead_key(key27));
+  });
 }
 
 // ---- two views per launch sequence (reduced to what is latency-bound) ---------------------------------
@@ -549,30 +600,26 @@ static int forward_raw_pair_impl(const TraseRastSettings* const s[2], const Tras
                                  const TraseRastWorkspace* const ws[2], void* pair_ws, hipStream_t stream) {
   const int P = raw[0]->P;
   TRASE_CHECK(hipSetDevice(s[0]->device));
+  Call k[2];       // (the entry point has checked both views' workspaces)
+  for (int v = 0; v < 2; ++v) carve(k[v], s[v], P, raw[v]->F, ws[v], WS_GEOM | WS_PRE, stream);
   const size_t n = 2 * (size_t)P;
   PairSortWs pw; pair_ws_layout(pair_ws, P, pw);
   const SortBufs& cs = pw.sort;
   uint32_t* const n_word = pw.n_word;
   launch_fill_u32(n_word, (uint32_t)n, stream);
-  GeomBuf g[2];
-  PreBuf t[2];
   for (int v = 0; v < 2; ++v) {
-    LaunchCtx c{stream, s[v]->debug, s[v]->variant};
-    geom_layout(ws[v]->geom, P, g[v]);
-    pre_layout(ws[v]->pre, P, t[v]);
-    const int rc = launch_preprocess_fwd_raw(c, *s[v], *raw[v], out[v]->radii, g[v], cs.keys[0] + (size_t)v * P, false,
+    const int rc = launch_preprocess_fwd_raw(k[v].c, *s[v], *raw[v], out[v]->radii, k[v].g, cs.keys[0] + (size_t)v * P, false,
                                              v ? 0x80000000u : 0u, v ? 0xffffffffu : 0x7fffffffu);
     if (rc) return rc;
   }
-  LaunchCtx c0{stream, s[0]->debug, s[0]->variant};
+  const LaunchCtx& c0 = k[0].c;
   int idx = 0;
   int rc = radix_sort_pairs(c0, cs, n_word, (uint32_t)n, 0, 32, true, &idx, 8, 0);      // ids generated on the fly: 0 .. 2 P - 1
   if (rc) return rc;
   if (idx != 0) { set_error("internal: pair depth sort ended in buffer %d", idx); return TRASE_ERR_INVALID; }
-  launch_split_pair_ids(c0, cs.vals[0], P, t[0].sort.vals[0], t[1].sort.vals[0]);
+  launch_split_pair_ids(c0, cs.vals[0], P, k[0].pre.sort.vals[0], k[1].pre.sort.vals[0]);
   for (int v = 0; v < 2; ++v) {
-    LaunchCtx c{stream, s[v]->debug, s[v]->variant};
-    rc = launch_scan_tiles(c, g[v], t[v].sort.vals[0], P, t[v], 0xffffffffu, out[v]->radii, (s[v]->image_width + TILE - 1) / TILE,
+    rc = launch_scan_tiles(k[v].c, k[v].g, k[v].pre.sort.vals[0], P, k[v].pre, 0xffffffffu, out[v]->radii, (s[v]->image_width + TILE - 1) / TILE,
                            (s[v]->image_height + TILE - 1) / TILE, list_pack_bits(s[v], P));
     if (rc) return rc;
     rc = trase_rast_render_raw(s[v], raw[v], out[v], ws[v], (trase_stream_t)stream);
@@ -594,8 +641,7 @@ int trase_rast_forward_raw_pair(const TraseRastSettings* s0, const TraseRastRawI
     int rc = validate_raw(s[v], raw[v]);
     if (rc) return rc;
     if (raw[v]->P > 0 && !out[v]->radii) { set_error("radii output required"); return TRASE_ERR_INVALID; }
-    const TraseRastInputs in = raw_as_inputs(raw[v]);
-    rc = check_ws(&in, s[v], ws[v], WS_GEOM | WS_PRE);
+    rc = check_ws(raw[v]->P, raw[v]->F, s[v], ws[v], WS_GEOM | WS_PRE);
     if (rc) return rc;
     if (strip_mode(s[v])) { set_error("trase_rast_forward_raw_pair: tile-row strips are rendered one view at a time"); return TRASE_ERR_UNSUPPORTED; }
   }
@@ -614,14 +660,9 @@ int trase_rast_forward_raw_pair(const TraseRastSettings* s0, const TraseRastRawI
 
 int trase_rast_render_raw(const TraseRastSettings* s, const TraseRastRawInputs* raw, const TraseRastOutputs* out,
                           const TraseRastWorkspace* ws, trase_stream_t stream) {
-  int rc = validate_raw(s, raw);
-  if (rc) return rc;
-  // stage 2 only needs P, F and the feature rows: reuse the regular entry point on a synthetic input record
-  TraseRastInputs in = raw_as_inputs(raw);
-  static const float dummy = 0.f;
-  in.means3D = &dummy; in.opacities = &dummy; in.shs = &dummy; in.scales = &dummy; in.rotations = &dummy;   // never dereferenced in stage 2
-  if (in.F > 0 && !in.sh_objs) { set_error("featn required"); return TRASE_ERR_INVALID; }
-  return trase_rast_render(s, &in, out, ws, stream);
+  // (an empty scene carries null pointers, the feature rows included: nothing reads them, as through trase_rast_render)
+  const int rc = validate_raw(s, raw);
+  return rc ? rc : stage2(s, raw->P, raw->F, raw->featn, out, ws, (hipStream_t)stream);
 }
 
 // The raw backward in two phases (see include/trase_rast.h): phase & 1 = compositing backward over every sub-tile (one
@@ -632,49 +673,28 @@ static int backward_raw_phases(const TraseRastSettings* s, const TraseRastRawInp
   int rc = validate_raw(s, raw);
   if (rc) return rc;
   if (!gr || !out || (raw->P > 0 && !out->radii)) { set_error("null grads/outputs"); return TRASE_ERR_INVALID; }
-  TraseRastInputs in = raw_as_inputs(raw);
-  rc = check_ws(&in, s, ws, WS_GEOM | WS_PRE | WS_BIN | WS_IMG);
-  if (rc) return rc;
-  if (!ws->tmp || ws->tmp_bytes < bwd_tmp_bytes(in.P, in.F, ws->capacity)) { set_error("backward tmp workspace too small"); return TRASE_ERR_WORKSPACE; }
-  if (s->variant & TRASE_VARIANT_FORWARD_ONLY) {
-    set_error("backward on a forward that ran with TRASE_VARIANT_FORWARD_ONLY: its backward-only state was never stored"); return TRASE_ERR_INVALID;
-  }
   const bool ranged = p_begin >= 0;
-  if (ranged && (p_begin % 64 != 0 || p_end > raw->P || p_end < p_begin || (p_end != raw->P && p_end % 64 != 0))) {
-    set_error("backward_raw_gaussians: [%d, %d) must start on a multiple of 64 and end on one or at P = %d", p_begin, p_end, raw->P);
-    return TRASE_ERR_INVALID;
-  }
   hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(s->device));
-  LaunchCtx c{stream, s->debug, s->variant};
-  const int gx = (s->image_width + SUB - 1) / SUB, gy = (s->image_height + SUB - 1) / SUB;
-  GeomBuf g; geom_layout(ws->geom, in.P, g);
-  BinBuf b; bin_layout(ws->bin, ws->capacity, gx * gy, b);
-  ImgBuf im; img_layout(ws->img, s->image_width, s->image_height, im);
-  PreBuf pre; pre_layout(ws->pre, in.P, pre);
-  BwdBuf bw; bwd_layout(ws->tmp, in.P, in.F, ws->capacity, bw);
-  if (in.P == 0) return TRASE_OK;
-  TraseRastGrads g2;
-  memset(&g2, 0, sizeof(g2));
-  g2.dL_dimage = gr->dL_dimage; g2.dL_dfeats = gr->dL_dfeats;
-  g2.dL_ddepth = (s->variant & TRASE_VARIANT_DEPTH_GRAD) ? gr->dL_ddepth : nullptr;
-  float* d_feats = gr->dL_dgaussian_features;
-  const bool no_feat_cotangent = !g2.dL_dfeats;
-  if (no_feat_cotangent) {
-    in.F = 0;
-    d_feats = nullptr;
-  }
+  Call k;
+  rc = resolve(k, s, raw->P, raw->F, ws, WS_GEOM | WS_PRE | WS_BIN | WS_IMG | WS_BWD, stream, [&] {
+    if (s->variant & TRASE_VARIANT_FORWARD_ONLY) {
+      set_error("backward on a forward that ran with TRASE_VARIANT_FORWARD_ONLY: its backward-only state was never stored"); return (int)TRASE_ERR_INVALID;
+    }
+    if (ranged && (p_begin % 64 != 0 || p_end > raw->P || p_end < p_begin || (p_end != raw->P && p_end % 64 != 0))) {
+      set_error("backward_raw_gaussians: [%d, %d) must start on a multiple of 64 and end on one or at P = %d", p_begin, p_end, raw->P);
+      return (int)TRASE_ERR_INVALID;
+    }
+    return (int)TRASE_OK;
+  });
+  if (rc || raw->P == 0) return rc;
+  const Cotangents ct = scope_cotangents(s, raw->P, raw->F, raw->featn, gr->dL_dimage, gr->dL_dfeats, gr->dL_ddepth);
+  float* const d_feats = gr->dL_dfeats ? gr->dL_dgaussian_features : nullptr;
   // sparse strip gradients: only the rows of the Gaussians with a pair in the strip are written (the caller keeps the others zero)
   const bool sparse = strip_mode(s) && !ranged && (s->variant & TRASE_VARIANT_SPARSE_STRIP_GRADS) != 0;
   if (phase & 1) {
-    if (no_feat_cotangent && gr->dL_dgaussian_features && raw->F > 0 && !sparse)
+    if (!gr->dL_dfeats && gr->dL_dgaussian_features && raw->F > 0 && !sparse)
       launch_zero_bytes(gr->dL_dgaussian_features, sizeof(float) * (size_t)raw->F * raw->P, stream);
-    if ((in.F == 32 || in.F == 0) && !valu_backward(s)) {
-      rc = launch_render_bwd_hw(c, *s, in, g, b, im, g2, bw.rows, bw.row_flags, bw.flags_bytes, out->depth);
-    } else {
-      launch_zero_bytes(bw.row_flags, (size_t)ws->capacity, stream);
-      rc = launch_render_bwd_gs(c, *s, in, g, b, im, g2, bw.rows, bw.row_flags, out->depth);
-    }
+    rc = compose_bwd(k, s, ct, out->depth);
     if (rc) return rc;
   }
   if (phase & 2) {
@@ -682,11 +702,11 @@ static int backward_raw_phases(const TraseRastSettings* s, const TraseRastRawInp
     // depth order); the feature-gradient rows of the others are zeroed by the per-Gaussian kernel, which writes their other
     // gradients as zeros anyway
     const int live_only = (strip_mode(s) && !ranged) ? 1 : 0;
-    rc = launch_reduce_rows(c, g, pre, in.P, in.F, bw.rows, bw.row_flags, bw.acc, d_feats, raw->gaussian_features, raw->norm_features,
-                            ranged ? p_begin : -1, ranged ? p_end : -1, live_only);
+    rc = launch_reduce_rows(k.c, k.g, k.pre, raw->P, ct.in.F, k.bw.rows, k.bw.row_flags, k.bw.acc, d_feats, raw->gaussian_features,
+                            raw->norm_features, ranged ? p_begin : -1, ranged ? p_end : -1, live_only);
     if (rc) return rc;
-    rc = launch_preprocess_bwd_raw(c, *s, *raw, out->radii, g, bw.acc, *gr, ranged ? p_begin : 0, ranged ? p_end : raw->P,
-                                   (live_only && d_feats && !sparse) ? 1 : 0, sparse ? pre.live_ids : nullptr);
+    rc = launch_preprocess_bwd_raw(k.c, *s, *raw, out->radii, k.g, k.bw.acc, *gr, ranged ? p_begin : 0, ranged ? p_end : raw->P,
+                                   (live_only && d_feats && !sparse) ? 1 : 0, sparse ? k.pre.live_ids : nullptr);
   }
   return rc;
 }
@@ -716,12 +736,10 @@ int trase_rast_zero_live_rows(const TraseRastSettings* s, const TraseRastRawInpu
     set_error("zero_live_rows: geom / pre workspaces of the forward whose live rows are to be cleared are required");
     return TRASE_ERR_WORKSPACE;
   }
-  hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(s->device));
-  LaunchCtx c{stream, s->debug, s->variant};
-  GeomBuf g; geom_layout(ws->geom, raw->P, g);
-  PreBuf pre; pre_layout(ws->pre, raw->P, pre);
-  return launch_zero_live_rows(c, g, pre, raw->P, raw->F, *gr);
+  Call k;
+  carve(k, s, raw->P, raw->F, ws, WS_GEOM | WS_PRE, (hipStream_t)stream_);
+  return launch_zero_live_rows(k.c, k.g, k.pre, raw->P, raw->F, *gr);
 }
 
 int trase_rast_backward_raw_compose(const TraseRastSettings* s, const TraseRastRawInputs* raw, const TraseRastOutputs* out,
@@ -796,7 +814,8 @@ int trase_evaluate_frame(const TraseEvalFrame* f, const TraseRastWorkspace* ws, 
   if (f->gt_object && !f->quantize && !f->partials) { set_error("trase_evaluate_frame: the unquantised squared error needs its partial slots"); return TRASE_ERR_INVALID; }
   const float* final_T = f->final_T;
   if (ws) {
-    // the transmittance a forward WITHOUT TRASE_VARIANT_FORWARD_ONLY left in its img workspace
+    // the transmittance a forward WITHOUT TRASE_VARIANT_FORWARD_ONLY left in its img workspace (a frame has no settings record:
+    // the one workspace it reads is carved here)
     if (!ws->img || ws->img_bytes < img_bytes(f->W, f->H)) { set_error("trase_evaluate_frame: img workspace missing/too small"); return TRASE_ERR_WORKSPACE; }
     ImgBuf im; img_layout(ws->img, f->W, f->H, im);
     final_T = im.final_T;

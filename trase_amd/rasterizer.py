@@ -370,12 +370,9 @@ def last_status():
     """(num_rendered, overflow, num_rendered_after_culling) of the most recent forward. Synchronises."""
     if _Policy.last_geom is None:
         return None
-    lib = _lib.load()
-    ws = _lib.RastWorkspace()
-    ws.geom = _lib.ptr(_Policy.last_geom)
-    ws.geom_bytes = _Policy.last_geom.numel()
     st = (C.c_int64 * 3)()
-    _lib.check(lib.trase_rast_status(C.byref(ws), C.byref(st), _stream(_Policy.last_geom.device)), "trase_rast_status")
+    _lib.check(_lib.load().trase_rast_status(C.byref(_workspace(_Policy.last_geom)), C.byref(st), _stream(_Policy.last_geom.device)),
+               "trase_rast_status")
     return int(st[0]), int(st[1]), int(st[2])
 
 
@@ -396,9 +393,9 @@ def last_tile_row_loads(allreduce: bool = False) -> torch.Tensor:
                            "the ranks' strips")
     H, W = _Policy.last_hw
     gx8, gy8 = (W + 7) // 8, (H + 7) // 8
-    cap = int(_Policy.last_capacity)
-    off = 2 * ((4 * cap + 255) // 256 * 256)              # BinBuf: point_list | pair_slot | ranges (trase_amd/csrc/api.hip bin_layout)
-    rng = _Policy.last_bin[off:off + 8 * gx8 * gy8].view(torch.int32).reshape(gy8, gx8, 2).to(torch.int64)
+    off = (C.c_int64 * 3)()              # point_list | pair_slot | ranges
+    _lib.check(_lib.load().trase_rast_bin_layout(int(_Policy.last_capacity), gx8 * gy8, C.byref(off)), "trase_rast_bin_layout")
+    rng = _Policy.last_bin[off[2]:off[2] + 8 * gx8 * gy8].view(torch.int32).reshape(gy8, gx8, 2).to(torch.int64)
     per_sub_row = (rng[..., 1] - rng[..., 0]).clamp_min(0).sum(dim=1)
     if gy8 % 2:
         per_sub_row = torch.cat([per_sub_row, per_sub_row.new_zeros(1)])
@@ -501,7 +498,9 @@ def _output_maps(F: int, H: int, W: int, device, zero: bool):
     return buf[:3], buf[3:3 + F], buf[3 + F:]
 
 
-def _fill_settings(rs: GaussianRasterizationSettings, device, keep: list) -> _lib.RastSettings:
+def _fill_settings(rs: GaussianRasterizationSettings, device, keep: list, ctx=None) -> _lib.RastSettings:
+    """ctx: the autograd context of the forward whose backward this is -- its variant, strip and feature background, not whatever
+    the globals say now (a change in between must not split the pair)"""
     s = _lib.RastSettings()
     s.image_height, s.image_width = int(rs.image_height), int(rs.image_width)
     s.tanfovx, s.tanfovy = float(rs.tanfovx), float(rs.tanfovy)
@@ -509,9 +508,10 @@ def _fill_settings(rs: GaussianRasterizationSettings, device, keep: list) -> _li
     s.sh_degree = int(rs.sh_degree)
     s.prefiltered, s.debug = int(bool(rs.prefiltered)), int(rs.debug)   # debug=2 additionally names every kernel on stderr
     s.device = device.index if device.index is not None else torch.cuda.current_device()
-    s.variant = _Policy.variant
-    s.tile_row_begin, s.tile_row_end = _Policy.tile_rows
-    s.feat_bg = _Policy.feat_bg
+    src = _Policy if ctx is None else ctx
+    s.variant = src.variant
+    s.tile_row_begin, s.tile_row_end = src.tile_rows
+    s.feat_bg = src.feat_bg
     for name in ("bg", "viewmatrix", "projmatrix", "campos"):
         t = _prep(getattr(rs, name), name, device)
         if t is None:
@@ -519,6 +519,73 @@ def _fill_settings(rs: GaussianRasterizationSettings, device, keep: list) -> _li
         keep.append(t)
         setattr(s, name, t.data_ptr())
     return s
+
+
+def _workspace(geom=None, pre=None, img=None, binb=None, tmp=None, capacity=0, ws=None) -> _lib.RastWorkspace:
+    """The workspace record over the given byte tensors (into `ws`, if given: stage 2 adds bin, tmp and the capacity)."""
+    ws = _lib.RastWorkspace() if ws is None else ws
+    if geom is not None:
+        ws.geom, ws.geom_bytes = _lib.ptr(geom), geom.numel()
+    if pre is not None:
+        ws.pre, ws.pre_bytes = _lib.ptr(pre), pre.numel()
+    if img is not None:
+        ws.img, ws.img_bytes = _lib.ptr(img), img.numel()
+    if binb is not None:
+        ws.bin, ws.bin_bytes = _lib.ptr(binb), binb.numel()
+    if tmp is not None:
+        ws.tmp, ws.tmp_bytes = _lib.ptr(tmp), tmp.numel()
+    ws.capacity = capacity
+    return ws
+
+
+def _rast_inputs(P, M, F, means3D, sh, sh_objs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
+    """-> (the operator path's input record, the tensors it points at)"""
+    inp = _lib.RastInputs()
+    inp.P, inp.M, inp.F = P, M, F
+    inp.means3D = _lib.ptr(means3D)
+    inp.shs, inp.sh_objs, inp.colors_precomp = _lib.ptr(sh), _lib.ptr(sh_objs), _lib.ptr(colors_precomp)
+    inp.opacities, inp.scales, inp.rotations = _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations)
+    inp.cov3D_precomp = _lib.ptr(cov3Ds_precomp)
+    return inp, [means3D, sh, sh_objs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp]
+
+
+def _run_forward(entries, s, rec, P, F, H, W, device, defer=None):
+    """The forward sequence of either front door: `rec` is its input record, `entries` its (preprocess, render, forward) entry
+    points.  -> (image, feats, depth, radii), (geom, pre, img, bin, tmp) workspaces, pair capacity.
+    defer(one_call, call): record instead of launch -- `call` holds the argument records, the stream, the tensors the output and
+    workspace records point at (`keep`) and the arguments of the `_after_render` that is then the caller's to make."""
+    lib = _lib.load()
+    preprocess, render, forward = entries
+    image, feats, depth = _output_maps(F, H, W, device, bool(s.tile_row_begin or s.tile_row_end))
+    radii = torch.empty(P, dtype=torch.int32, device=device)
+    out = _lib.RastOutputs()
+    out.image, out.radii, out.depth = _lib.ptr(image), _lib.ptr(radii), _lib.ptr(depth)
+    out.feats = _lib.ptr(feats) if F > 0 else None
+
+    geom_b, _, img_b, pre_b, _, _ = _sizes(lib, P, W, H, F, 1)
+    geom, pre, img = _bytes(geom_b, device), _bytes(pre_b, device), _bytes(img_b, device)
+    ws = _workspace(geom, pre, img)
+    stream = _stream(device)
+    args = (C.byref(s), C.byref(rec), C.byref(out), C.byref(ws), stream)
+
+    one_call = (not _Policy.sync) and _Policy.capacity > 0      # capacity known beforehand: one boundary crossing
+    if not one_call:
+        _lib.check(preprocess(*args), preprocess.__name__)
+    def _again():              # a saturated 27-bit depth key: stage 1 once more on the raw float bits
+        s.variant |= VARIANT_DEPTH32
+        _lib.check(preprocess(*args), preprocess.__name__)
+    capacity = _pick_capacity(lib, ws, stream, None if one_call else _again)
+    _, bin_b, _, _, tmp_b, _ = _sizes(lib, P, W, H, F, capacity)
+    binb, tmp = _bytes(bin_b, device), _bytes(tmp_b, device)
+    _workspace(binb=binb, tmp=tmp, capacity=capacity, ws=ws)
+    if defer is not None:
+        defer(one_call, dict(s=s, rec=rec, out=out, ws=ws, P=P, device=device, stream=stream, after=(geom, capacity, binb, (H, W)),
+                             keep=[image, feats, depth, radii, geom, pre, img, binb, tmp]))
+    else:
+        launch = forward if one_call else render
+        _lib.check(launch(*args), launch.__name__)
+        _after_render(geom, capacity, binb, (H, W))
+    return (image, feats, depth, radii), (geom, pre, img, binb, tmp), capacity
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -548,49 +615,9 @@ class _RasterizeGaussians(torch.autograd.Function):
 
         keep: list = []
         s = _fill_settings(raster_settings, device, keep)
-        inp = _lib.RastInputs()
-        inp.P, inp.M, inp.F = P, M, F
-        inp.means3D = _lib.ptr(means3D)
-        inp.shs, inp.sh_objs, inp.colors_precomp = _lib.ptr(sh), _lib.ptr(sh_objs), _lib.ptr(colors_precomp)
-        inp.opacities, inp.scales, inp.rotations = _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations)
-        inp.cov3D_precomp = _lib.ptr(cov3Ds_precomp)
-
-        image, feats, depth = _output_maps(F, H, W, device, bool(s.tile_row_begin or s.tile_row_end))
-        radii = torch.empty(P, dtype=torch.int32, device=device)
-        out = _lib.RastOutputs()
-        out.image, out.radii, out.depth = _lib.ptr(image), _lib.ptr(radii), _lib.ptr(depth)
-        out.feats = _lib.ptr(feats) if F > 0 else None
-
-        geom_b, _, img_b, pre_b, _, _ = _sizes(lib, P, W, H, F, 1)
-        geom = _bytes(geom_b, device)
-        pre = _bytes(pre_b, device)
-        img = _bytes(img_b, device)
-        ws = _lib.RastWorkspace()
-        ws.geom, ws.geom_bytes = _lib.ptr(geom), geom.numel()
-        ws.pre, ws.pre_bytes = _lib.ptr(pre), pre.numel()
-        ws.img, ws.img_bytes = _lib.ptr(img), img.numel()
-        stream = _stream(device)
-
-        one_call = (not _Policy.sync) and _Policy.capacity > 0      # capacity known beforehand: one boundary crossing
-        if not one_call:
-            _lib.check(lib.trase_rast_preprocess(C.byref(s), C.byref(inp), C.byref(out), C.byref(ws), stream),
-                       "trase_rast_preprocess")
-        def _again():              # a saturated 27-bit depth key: stage 1 once more on the raw float bits
-            s.variant |= VARIANT_DEPTH32
-            _lib.check(lib.trase_rast_preprocess(C.byref(s), C.byref(inp), C.byref(out), C.byref(ws), stream), "trase_rast_preprocess")
-        capacity = _pick_capacity(lib, ws, stream, None if one_call else _again)
-        _, bin_b, _, _, tmp_b, _ = _sizes(lib, P, W, H, F, capacity)
-        binb = _bytes(bin_b, device)
-        tmp = _bytes(tmp_b, device)
-        ws.bin, ws.bin_bytes = _lib.ptr(binb), binb.numel()
-        ws.tmp, ws.tmp_bytes = _lib.ptr(tmp), tmp.numel()
-        ws.capacity = capacity
-        if one_call:
-            _lib.check(lib.trase_rast_forward(C.byref(s), C.byref(inp), C.byref(out), C.byref(ws), stream), "trase_rast_forward")
-        else:
-            _lib.check(lib.trase_rast_render(C.byref(s), C.byref(inp), C.byref(out), C.byref(ws), stream),
-                       "trase_rast_render")
-        _after_render(geom, capacity, binb, (H, W))
+        inp, _ = _rast_inputs(P, M, F, means3D, sh, sh_objs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        (image, feats, depth, radii), (geom, pre, img, binb, _), capacity = _run_forward(
+            (lib.trase_rast_preprocess, lib.trase_rast_render, lib.trase_rast_forward), s, inp, P, F, H, W, device)
 
         ctx.raster_settings = raster_settings
         ctx.variant, ctx.tile_rows, ctx.feat_bg = s.variant, (s.tile_row_begin, s.tile_row_end), s.feat_bg
@@ -612,28 +639,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         P, M, F, H, W = ctx.dims
         device = means3D.device
         keep: list = []
-        s = _fill_settings(ctx.raster_settings, device, keep)
-        s.variant = ctx.variant                # the forward's variant (a global change in between must not split the pair)
-        s.tile_row_begin, s.tile_row_end = ctx.tile_rows
-        s.feat_bg = ctx.feat_bg
-        inp = _lib.RastInputs()
-        inp.P, inp.M, inp.F = P, M, F
-        inp.means3D = _lib.ptr(means3D)
-        inp.shs, inp.sh_objs, inp.colors_precomp = _lib.ptr(sh), _lib.ptr(sh_objs), _lib.ptr(colors_precomp)
-        inp.opacities, inp.scales, inp.rotations = _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations)
-        inp.cov3D_precomp = _lib.ptr(cov3Ds_precomp)
+        s = _fill_settings(ctx.raster_settings, device, keep, ctx)
+        inp, _ = _rast_inputs(P, M, F, means3D, sh, sh_objs, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         out = _lib.RastOutputs()
         out.radii = _lib.ptr(radii)
         out.depth = _lib.ptr(depth_out)
-
         tmp = _bytes(_sizes(lib, P, W, H, F, ctx.capacity)[5], device)
-        ws = _lib.RastWorkspace()
-        ws.geom, ws.geom_bytes = _lib.ptr(geom), geom.numel()
-        ws.bin, ws.bin_bytes = _lib.ptr(binb), binb.numel()
-        ws.img, ws.img_bytes = _lib.ptr(img), img.numel()
-        ws.pre, ws.pre_bytes = _lib.ptr(pre), pre.numel()
-        ws.tmp, ws.tmp_bytes = _lib.ptr(tmp), tmp.numel()
-        ws.capacity = ctx.capacity
+        ws = _workspace(geom, pre, img, binb, tmp, ctx.capacity)
 
         grad_image = _prep(grad_image, "grad_image", device)
         grad_feats = _prep(grad_feats, "grad_feats", device) if F > 0 else None

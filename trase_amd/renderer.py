@@ -18,10 +18,9 @@ from . import _lib
 from .sh import sh_colors_python
 from .smooth import smoothed_gaussian_features
 from .rasterizer import VARIANT_SPARSE_STRIP_GRADS as _r_VARIANT_SPARSE
-from .rasterizer import VARIANT_DEPTH32 as _r_VARIANT_DEPTH32
 from .rasterizer import VARIANT_FORWARD_ONLY as _r_VARIANT_FORWARD_ONLY
-from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, _Policy, _after_render, _release_last, _bytes, _fill_settings,
-                         _output_maps, _pick_capacity, _prep, _sizes, _stream)
+from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, _after_render, _release_last, _bytes, _fill_settings, _prep,
+                         _run_forward, _sizes, _stream, _workspace)
 
 
 def set_backward_scope(scope: str = "all") -> None:
@@ -112,6 +111,22 @@ def chunk_ranges(P: int, chunks: int):
     return out
 
 
+def _raw_inputs(P, F, norm_features, sh_dir_raw, xyz, d_xyz, f_dc, f_rest, opacity, scaling, d_scaling, rotation, d_rotation, gfeat, featn,
+                override_color, mask_u8, se3):
+    """-> (the fused path's input record, the tensors it points at); an absent optional tensor is None"""
+    raw = _lib.RastRawInputs()
+    raw.P, raw.F, raw.norm_features = P, F, int(bool(norm_features))
+    raw.xyz, raw.d_xyz = _lib.ptr(xyz), _lib.ptr(d_xyz)
+    raw.features_dc, raw.features_rest, raw.opacity = _lib.ptr(f_dc), _lib.ptr(f_rest), _lib.ptr(opacity)
+    raw.scaling, raw.d_scaling = _lib.ptr(scaling), _lib.ptr(d_scaling)
+    raw.rotation, raw.d_rotation = _lib.ptr(rotation), _lib.ptr(d_rotation)
+    raw.gaussian_features = _lib.ptr(gfeat) if F > 0 else None
+    raw.featn = _lib.ptr(featn)
+    raw.colors_precomp, raw.mask, raw.d_xyz_se3 = _lib.ptr(override_color), _lib.ptr(mask_u8), _lib.ptr(se3)
+    raw.sh_dir_undeformed = int(bool(sh_dir_raw))
+    return raw, [xyz, d_xyz, f_dc, f_rest, opacity, scaling, d_scaling, rotation, d_rotation, gfeat, featn, override_color, mask_u8, se3]
+
+
 class _RenderRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, d_xyz, f_dc, f_rest, opacity, scaling, d_scaling, rotation, d_rotation, gfeat, means2D,
@@ -149,16 +164,8 @@ class _RenderRaw(torch.autograd.Function):
         keep: list = []
         s = _fill_settings(raster_settings, device, keep)
         featn = torch.empty(P, max(F, 1), device=device)
-        raw = _lib.RastRawInputs()
-        raw.P, raw.F, raw.norm_features = P, F, int(bool(norm_features))
-        raw.xyz, raw.d_xyz = _lib.ptr(xyz), _lib.ptr(d_xyz)
-        raw.features_dc, raw.features_rest, raw.opacity = _lib.ptr(f_dc), _lib.ptr(f_rest), _lib.ptr(opacity)
-        raw.scaling, raw.d_scaling = _lib.ptr(scaling), _lib.ptr(d_scaling)
-        raw.rotation, raw.d_rotation = _lib.ptr(rotation), _lib.ptr(d_rotation)
-        raw.gaussian_features = _lib.ptr(gfeat) if F > 0 else None
-        raw.featn = _lib.ptr(featn)
-        raw.colors_precomp, raw.mask, raw.d_xyz_se3 = _lib.ptr(override_color), _lib.ptr(mask_u8), _lib.ptr(se3)
-        raw.sh_dir_undeformed = int(bool(sh_dir_raw))
+        raw, raw_tensors = _raw_inputs(P, F, norm_features, sh_dir_raw, xyz, d_xyz, f_dc, f_rest, opacity, scaling, d_scaling, rotation,
+                                       d_rotation, gfeat, featn, override_color, mask_u8, se3)
         # fwd_only: render() was called under torch.no_grad() -- nobody will differentiate this forward, and the state only a
         # backward reads is not written (TRASE_VARIANT_FORWARD_ONLY).  (Decided by the caller: inside an autograd Function's
         # forward the grad mode is always off.)
@@ -167,49 +174,18 @@ class _RenderRaw(torch.autograd.Function):
         if fwd_only and keep_img is None:
             s.variant |= _r_VARIANT_FORWARD_ONLY
 
-        image, feats, depth = _output_maps(F, H, W, device, bool(s.tile_row_begin or s.tile_row_end))
-        radii = torch.empty(P, dtype=torch.int32, device=device)
-        out = _lib.RastOutputs()
-        out.image, out.radii, out.depth = _lib.ptr(image), _lib.ptr(radii), _lib.ptr(depth)
-        out.feats = _lib.ptr(feats) if F > 0 else None
-        geom_b, _, img_b, pre_b, _, _ = _sizes(lib, P, W, H, F, 1)
-        geom, pre, img = _bytes(geom_b, device), _bytes(pre_b, device), _bytes(img_b, device)
-        ws = _lib.RastWorkspace()
-        ws.geom, ws.geom_bytes = _lib.ptr(geom), geom.numel()
-        ws.pre, ws.pre_bytes = _lib.ptr(pre), pre.numel()
-        ws.img, ws.img_bytes = _lib.ptr(img), img.numel()
-        stream = _stream(device)
-        one_call = (not _Policy.sync) and _Policy.capacity > 0      # capacity known beforehand: one boundary crossing
-        if not one_call:
-            _lib.check(lib.trase_rast_preprocess_raw(C.byref(s), C.byref(raw), C.byref(out), C.byref(ws), stream),
-                       "trase_rast_preprocess_raw")
-        def _again():              # a saturated 27-bit depth key: stage 1 once more on the raw float bits
-            s.variant |= _r_VARIANT_DEPTH32
-            _lib.check(lib.trase_rast_preprocess_raw(C.byref(s), C.byref(raw), C.byref(out), C.byref(ws), stream),
-                       "trase_rast_preprocess_raw")
-        capacity = _pick_capacity(lib, ws, stream, None if one_call else _again)
-        _, bin_b, _, _, tmp_b, _ = _sizes(lib, P, W, H, F, capacity)
-        binb, tmp = _bytes(bin_b, device), _bytes(tmp_b, device)
-        ws.bin, ws.bin_bytes = _lib.ptr(binb), binb.numel()
-        ws.tmp, ws.tmp_bytes = _lib.ptr(tmp), tmp.numel()
-        ws.capacity = capacity
+        defer = None
         if _PAIR is not None:
             # render_views(): the launch sequence of this view is issued together with the next view's (one depth sort for both);
-            # the record keeps every buffer the argument structs point at alive until then
-            if not one_call or s.tile_row_begin or s.tile_row_end:
-                raise RuntimeError("trase_amd.renderer.render_views needs the sync-free capacity policy with a known capacity "
-                                   "(rasterizer.set_sync(False, capacity=...)) and whole-image views")
-            _PAIR.append(dict(s=s, raw=raw, out=out, ws=ws, P=P, device=device, stream=stream, after=(geom, capacity, binb, (H, W)),
-                              keep=(keep, xyz, d_xyz, f_dc, f_rest, opacity, scaling, d_scaling, rotation, d_rotation, gfeat, featn,
-                                    image, feats, depth, radii, geom, pre, img, binb, tmp)))
-        elif one_call:
-            _lib.check(lib.trase_rast_forward_raw(C.byref(s), C.byref(raw), C.byref(out), C.byref(ws), stream),
-                       "trase_rast_forward_raw")
-        else:
-            _lib.check(lib.trase_rast_render_raw(C.byref(s), C.byref(raw), C.byref(out), C.byref(ws), stream),
-                       "trase_rast_render_raw")
-        if _PAIR is None:
-            _after_render(geom, capacity, binb, (H, W))
+            # the record keeps every tensor the argument records point at alive until then
+            def defer(one_call, call):
+                if not one_call or s.tile_row_begin or s.tile_row_end:
+                    raise RuntimeError("trase_amd.renderer.render_views needs the sync-free capacity policy with a known capacity "
+                                       "(rasterizer.set_sync(False, capacity=...)) and whole-image views")
+                call["keep"] += keep + raw_tensors
+                _PAIR.append(call)
+        (image, feats, depth, radii), (geom, pre, img, binb, _), capacity = _run_forward(
+            (lib.trase_rast_preprocess_raw, lib.trase_rast_render_raw, lib.trase_rast_forward_raw), s, raw, P, F, H, W, device, defer)
         ctx.raster_settings, ctx.capacity, ctx.dims = raster_settings, capacity, (P, F, H, W)
         ctx.variant, ctx.tile_rows, ctx.feat_bg = s.variant, (s.tile_row_begin, s.tile_row_end), s.feat_bg
         if (s.variant & _r_VARIANT_SPARSE) and (s.tile_row_begin != 0 or s.tile_row_end != 0):
@@ -248,33 +224,15 @@ class _RenderRaw(torch.autograd.Function):
         P, F, H, W = ctx.dims
         device = xyz.device
         keep: list = []
-        s = _fill_settings(ctx.raster_settings, device, keep)
-        s.variant = ctx.variant                # the forward's variant and strip, not whatever the globals say now
-        s.tile_row_begin, s.tile_row_end = ctx.tile_rows
-        s.feat_bg = ctx.feat_bg
-        raw = _lib.RastRawInputs()
-        raw.P, raw.F, raw.norm_features = P, F, int(ctx.norm_features)
-        raw.xyz, raw.d_xyz = _lib.ptr(xyz), (_lib.ptr(d_xyz) if has_dxyz else None)
-        raw.features_dc, raw.features_rest, raw.opacity = _lib.ptr(f_dc), _lib.ptr(f_rest), _lib.ptr(opacity)
-        raw.scaling, raw.d_scaling = _lib.ptr(scaling), (_lib.ptr(d_scaling) if has_dscale else None)
-        raw.rotation, raw.d_rotation = _lib.ptr(rotation), (_lib.ptr(d_rotation) if has_drot else None)
-        raw.gaussian_features = _lib.ptr(gfeat) if (has_feat and F > 0) else None
-        raw.featn = _lib.ptr(featn)
-        raw.colors_precomp = _lib.ptr(override_color) if has_color else None
-        raw.mask = _lib.ptr(mask_u8) if has_mask else None
-        raw.d_xyz_se3 = _lib.ptr(se3) if has_se3 else None
-        raw.sh_dir_undeformed = int(sh_dir_raw)
+        s = _fill_settings(ctx.raster_settings, device, keep, ctx)
+        raw, _ = _raw_inputs(P, F, ctx.norm_features, sh_dir_raw, xyz, d_xyz if has_dxyz else None, f_dc, f_rest, opacity, scaling,
+                             d_scaling if has_dscale else None, rotation, d_rotation if has_drot else None, gfeat if has_feat else None,
+                             featn, override_color if has_color else None, mask_u8 if has_mask else None, se3 if has_se3 else None)
         out = _lib.RastOutputs()
         out.radii = _lib.ptr(radii)
         out.depth = _lib.ptr(depth_out)
         tmp = _bytes(_sizes(lib, P, W, H, F, ctx.capacity)[5], device)
-        ws = _lib.RastWorkspace()
-        ws.geom, ws.geom_bytes = _lib.ptr(geom), geom.numel()
-        ws.bin, ws.bin_bytes = _lib.ptr(binb), binb.numel()
-        ws.img, ws.img_bytes = _lib.ptr(img), img.numel()
-        ws.pre, ws.pre_bytes = _lib.ptr(pre), pre.numel()
-        ws.tmp, ws.tmp_bytes = _lib.ptr(tmp), tmp.numel()
-        ws.capacity = ctx.capacity
+        ws = _workspace(geom, pre, img, binb, tmp, ctx.capacity)
         need = ctx.needs_input_grad   # xyz0 d_xyz1 f_dc2 f_rest3 opacity4 scaling5 d_scaling6 rotation7 d_rotation8 gfeat9 means2D10
 
         pid = ctx.param_ids
@@ -358,10 +316,7 @@ class _RenderRaw(torch.autograd.Function):
                 zg.dL_dgaussian_features = _lib.ptr(by.get("gfeat"))
                 zraw = _lib.RastRawInputs()
                 zraw.P, zraw.F = P, (by["gfeat"].shape[-1] if by.get("gfeat") is not None else 0)
-                zws = _lib.RastWorkspace()
-                zws.geom, zws.geom_bytes = _lib.ptr(pgeom), pgeom.numel()
-                zws.pre, zws.pre_bytes = _lib.ptr(ppre), ppre.numel()
-                _lib.check(lib.trase_rast_zero_live_rows(C.byref(s), C.byref(zraw), C.byref(zws), C.byref(zg), _stream(device)),
+                _lib.check(lib.trase_rast_zero_live_rows(C.byref(s), C.byref(zraw), C.byref(_workspace(pgeom, ppre)), C.byref(zg), _stream(device)),
                            "trase_rast_zero_live_rows")
             _SPARSE["prev"] = (geom, pre, P, F)
         if _GRAD_CHUNKS is not None and P > 0:
@@ -397,12 +352,12 @@ def _flush_pair(recs):
         nbytes = C.c_size_t()
         _lib.check(lib.trase_rast_pair_sizes(a["P"], C.byref(nbytes)), "trase_rast_pair_sizes")
         pair_ws = _bytes(nbytes.value, a["device"])
-        _lib.check(lib.trase_rast_forward_raw_pair(C.byref(a["s"]), C.byref(a["raw"]), C.byref(a["out"]), C.byref(a["ws"]),
-                                                   C.byref(b["s"]), C.byref(b["raw"]), C.byref(b["out"]), C.byref(b["ws"]),
+        _lib.check(lib.trase_rast_forward_raw_pair(C.byref(a["s"]), C.byref(a["rec"]), C.byref(a["out"]), C.byref(a["ws"]),
+                                                   C.byref(b["s"]), C.byref(b["rec"]), C.byref(b["out"]), C.byref(b["ws"]),
                                                    _lib.ptr(pair_ws), pair_ws.numel(), a["stream"]), "trase_rast_forward_raw_pair")
     else:
         for r in recs:
-            _lib.check(lib.trase_rast_forward_raw(C.byref(r["s"]), C.byref(r["raw"]), C.byref(r["out"]), C.byref(r["ws"]), r["stream"]),
+            _lib.check(lib.trase_rast_forward_raw(C.byref(r["s"]), C.byref(r["rec"]), C.byref(r["out"]), C.byref(r["ws"]), r["stream"]),
                        "trase_rast_forward_raw")
     for r in recs:
         _after_render(*r["after"])
