@@ -604,6 +604,36 @@ int trase_featnorm_forward(const float* feats, int32_t F, int64_t HW, float* out
                            trase_stream_t stream);
 int trase_featnorm_backward(const float* feats, int32_t F, int64_t HW, const float* out2, const float* g, float* dL_dfeats,
                             int32_t device, trase_stream_t stream);
+/* The same head on the masks AS THE REFERENCE STORES THEM (extract_masks.py:91-99): one flat stream of N * HW bits,
+ * numpy.packbits(masks.reshape(-1)) = bitarray(...).tobytes() in bitarray's default big-endian bit order.  Stream bit i is bit
+ * 7 - (i & 7) of byte i >> 3; mask n starts at stream bit n * HW (in the middle of a byte wherever HW is no multiple of 8); no
+ * row or mask is padded, only the last byte.  An eighth of the bool bytes, never expanded (train.py:245-249 does, on the host).
+ * Buffer contract of every entry point below: `bits` is 16-byte aligned; bits_bytes is a multiple of 16 and at least
+ * ceil(N * HW / 8); no byte at or past bits_bytes is read; bits at or past N * HW are ignored whatever they hold;
+ * 1 <= N <= 8192, 1 <= HW < 2^31.  Anything else returns TRASE_ERR_INVALID before a device is touched.
+ * trase_mask_stats_bits: cover_count [HW] and mask_size [N] exactly as trase_mask_stats writes them, in one pass over the stream
+ *   (integers, no float atomics: bitwise reproducible).
+ * trase_pairhead_forward_bits, trase_pairhead_forward_bits_resized: trase_pairhead_forward_n / _forward_resized with
+ *   (bits, bits_bytes) in place of sam_masks; workspace of trase_pairhead_sizes / trase_pairhead_sizes_resized, the backward is
+ *   trase_pairhead_backward_n / _backward_resized (it never reads the masks).  Same memberships, same arithmetic: the results
+ *   are bitwise those of the bool entry points.
+ * trase_pack_masks: the N * HW bool bytes (any non-zero byte is set) -> the stream; writes all bits_bytes, padding as zero.
+ * trase_unpack_masks: the stream -> N * HW bytes of exactly 0 / 1. */
+int trase_mask_stats_bits(const uint8_t* bits, size_t bits_bytes, int32_t N, int64_t HW, int32_t* cover_count, uint32_t* mask_size,
+                          int32_t device, trase_stream_t stream);
+int trase_pairhead_forward_bits(const float* feats, int32_t F, int64_t HW, const uint8_t* bits, size_t bits_bytes, int32_t N,
+                                const uint8_t* sampled_mask, int32_t n_sampled_masks, const uint32_t* mask_size, const int32_t* pix,
+                                int32_t S, const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
+                                float* out8, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+int trase_pairhead_forward_bits_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const uint8_t* bits,
+                                        size_t bits_bytes, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
+                                        const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
+                                        float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
+                                        int32_t device, trase_stream_t stream);
+int trase_pack_masks(const uint8_t* sam_masks, int32_t N, int64_t HW, uint8_t* bits, size_t bits_bytes, int32_t device,
+                     trase_stream_t stream);
+int trase_unpack_masks(const uint8_t* bits, size_t bits_bytes, int32_t N, int64_t HW, uint8_t* sam_masks, int32_t device,
+                       trase_stream_t stream);
 
 /* ---- segmentation after training: K-means and query masks (gui.py:248-270, render.py:97-105 + :334-345) ------------------
  * trase_kmeans_steps: n_steps Lloyd steps of kmeans_pytorch.kmeans(X, K, distance='euclidean') (gui.py:248-270,

@@ -241,6 +241,16 @@ SYMBOLS = [
     ("trase_featnorm_sizes", C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
     ("trase_featnorm_forward", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     ("trase_featnorm_backward", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_mask_stats_bits", C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_pairhead_forward_bits", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32,
+                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_pairhead_forward_bits_resized", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                      C.c_size_t, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                      C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
+                                                      C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_pack_masks", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_unpack_masks", C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     ("trase_nnfm_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     ("trase_nnfm_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_int32, C.c_void_p]),

@@ -266,6 +266,23 @@ bool prof_on();
 
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// the buffer contract of every entry point that reads or writes a packed mask stream (maskbits.hip, the *_bits head): a 16-byte
+// aligned buffer of bits_bytes, a multiple of 16 and at least ceil(N * HW / 8); 1 <= N <= 8192, 1 <= HW < 2^31.  0 when usable.
+static inline int mask_bits_ok(const char* who, const void* bits, size_t bits_bytes, int32_t N, int64_t HW) {
+  if (!bits) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  if (N < 1 || N > 8192 || HW < 1 || HW >= ((int64_t)1 << 31)) {
+    set_error("%s: need 1 <= N <= 8192 and 1 <= HW < 2^31 (got N %d, HW %lld)", who, N, (long long)HW); return TRASE_ERR_INVALID;
+  }
+  if (((size_t)bits & 15) != 0) { set_error("%s: the mask stream must be 16-byte aligned", who); return TRASE_ERR_INVALID; }
+  const size_t need = (size_t)(((uint64_t)N * (uint64_t)HW + 7) / 8);
+  if ((bits_bytes & 15) != 0 || bits_bytes < need) {
+    set_error("%s: bits_bytes must be a multiple of 16 and at least %zu for %d masks of %lld pixels (got %zu)", who, need, N, (long long)HW,
+              bits_bytes);
+    return TRASE_ERR_INVALID;
+  }
+  return TRASE_OK;
+}
+
 // 8x8 sub-tile rows [lo, hi) of the strip the settings select (whole image when tile_row_begin == tile_row_end == 0)
 static inline void strip_subtile_rows(const TraseRastSettings& s, int& lo, int& hi) {
   const int gy8 = (s.image_height + SUB - 1) / SUB;

@@ -300,7 +300,9 @@ __device__ __forceinline__ float resize_blend(const float* __restrict__ plane, c
 // membership words / size sums are combined with shuffles; four channels of the feature column per lane.
 // RESIZED: feats is (32, g.Hr, g.Wr) and the column is the bilinear blend of its four taps; pix, HW and the masks stay at
 // mask resolution
-template <bool RESIZED>
+// BITS: `masks` is the packed stream of maskbits.hip instead of N * HW bool bytes: membership of pixel p in mask n is stream bit
+// n * HW + p (bit 7 - (i & 7) of byte i >> 3); everything behind in4[] is the same arithmetic
+template <bool RESIZED, bool BITS>
 __global__ __launch_bounds__(256) void ph_gather_kernel(const float* __restrict__ feats, long long HW, ResizeGeom g,
                                                         const uint8_t* __restrict__ masks, int N, const int* __restrict__ rank,
                                                         const uint32_t* __restrict__ mask_size, const int32_t* __restrict__ pix,
@@ -330,7 +332,14 @@ __global__ __launch_bounds__(256) void ph_gather_kernel(const float* __restrict_
   for (int n0 = l; n0 < N; n0 += 32) {
     uint8_t in4[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) in4[e] = (n0 + 8 * e < N) ? masks[(size_t)(n0 + 8 * e) * HW + p] : (uint8_t)0;
+    for (int e = 0; e < 4; ++e) {
+      if constexpr (BITS) {
+        const unsigned long long i = (unsigned long long)(n0 + 8 * e) * (unsigned long long)HW + (unsigned long long)p;
+        in4[e] = (n0 + 8 * e < N) ? (uint8_t)((masks[i >> 3] >> (7u - (uint32_t)(i & 7u))) & 1u) : (uint8_t)0;
+      } else {
+        in4[e] = (n0 + 8 * e < N) ? masks[(size_t)(n0 + 8 * e) * HW + p] : (uint8_t)0;
+      }
+    }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int n = n0 + 8 * e;
@@ -862,19 +871,22 @@ int trase_pairhead_forward(const float* feats, int32_t F, int64_t HW, const uint
                                   negative_th, use_weights, out8, ws, ws_bytes, device, stream_);
 }
 
-int trase_pairhead_forward_n(const float* feats, int32_t F, int64_t HW, const uint8_t* sam_masks, int32_t N,
-                             const uint8_t* sampled_mask, int32_t n_sampled_masks, const uint32_t* mask_size, const int32_t* pix,
-                             int32_t S, const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
-                             float* out8, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+// the head at mask resolution on bool bytes (packed == false: who = "trase_pairhead_forward") or on the packed stream
+static int pairhead_forward_impl(const char* who, bool packed, const float* feats, int32_t F, int64_t HW, const uint8_t* sam_masks,
+                                 size_t bits_bytes, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
+                                 const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
+                                 float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
+                                 int32_t device, trase_stream_t stream_) {
   if (!feats || !sam_masks || !sampled_mask || !mask_size || !pix || !out8 || S < 1 || N < 1 || N > PH_MAXN || HW < 1 || mode < 0 || mode > 2) {
-    set_error("trase_pairhead_forward: bad arguments"); return TRASE_ERR_INVALID;
+    set_error("%s: bad arguments", who); return TRASE_ERR_INVALID;
   }
-  if (F != PH_F) { set_error("trase_pairhead_forward: %d feature channels (compiled for %d)", F, PH_F); return TRASE_ERR_INVALID; }
+  if (packed) { if (int rc = mask_bits_ok(who, sam_masks, bits_bytes, N, HW)) return rc; }
+  if (F != PH_F) { set_error("%s: %d feature channels (compiled for %d)", who, F, PH_F); return TRASE_ERR_INVALID; }
   if (n_sampled_masks < 0 || n_sampled_masks > 32 * PH_MAXW) {
-    set_error("trase_pairhead_forward: %d sampled masks (at most %d)", n_sampled_masks, 32 * PH_MAXW); return TRASE_ERR_INVALID;
+    set_error("%s: %d sampled masks (at most %d)", who, n_sampled_masks, 32 * PH_MAXW); return TRASE_ERR_INVALID;
   }
   PairWs w;
-  if (!ws || ws_bytes < pair_ws_layout(ws, S, w)) { set_error("trase_pairhead_forward: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  if (!ws || ws_bytes < pair_ws_layout(ws, S, w)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   // colP and colN are neighbours in the workspace (pair_ws_layout): one fill for both
@@ -883,8 +895,12 @@ int trase_pairhead_forward_n(const float* feats, int32_t F, int64_t HW, const ui
   {
     ProfScope ps("pairhead_fwd", stream);
     hipLaunchKernelGGL(ph_rank_kernel, dim3(1), dim3(256), 0, stream, sampled_mask, N, w.rank, w.consts);
-    hipLaunchKernelGGL(ph_gather_kernel<false>, dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, ResizeGeom{}, sam_masks, N, w.rank,
-                       mask_size, pix, S, (const int*)S_dev, w.fn, w.rinv, w.a, w.bits);
+    if (packed)
+      hipLaunchKernelGGL((ph_gather_kernel<false, true>), dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, ResizeGeom{}, sam_masks,
+                         N, w.rank, mask_size, pix, S, (const int*)S_dev, w.fn, w.rinv, w.a, w.bits);
+    else
+      hipLaunchKernelGGL((ph_gather_kernel<false, false>), dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, ResizeGeom{}, sam_masks,
+                         N, w.rank, mask_size, pix, S, (const int*)S_dev, w.fn, w.rinv, w.a, w.bits);
     hipLaunchKernelGGL(ph_consts_kernel, dim3(1), dim3(256), 0, stream, w.a, S, (const int*)S_dev, w.consts);
     hipLaunchKernelGGL(ph_flags_kernel, grid, dim3(256), 0, stream, w.fn, w.bits, S, (const int*)S_dev, positive_th, negative_th, mode, w.colP,
                        w.colN, w.partial);
@@ -895,6 +911,22 @@ int trase_pairhead_forward_n(const float* feats, int32_t F, int64_t HW, const ui
   }
   TRASE_POST_LAUNCH("pairhead_fwd", stream, 0);
   return TRASE_OK;
+}
+
+int trase_pairhead_forward_n(const float* feats, int32_t F, int64_t HW, const uint8_t* sam_masks, int32_t N,
+                             const uint8_t* sampled_mask, int32_t n_sampled_masks, const uint32_t* mask_size, const int32_t* pix,
+                             int32_t S, const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
+                             float* out8, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  return pairhead_forward_impl("trase_pairhead_forward", false, feats, F, HW, sam_masks, 0, N, sampled_mask, n_sampled_masks, mask_size, pix, S,
+                               S_dev, mode, positive_th, negative_th, use_weights, out8, ws, ws_bytes, device, stream_);
+}
+
+int trase_pairhead_forward_bits(const float* feats, int32_t F, int64_t HW, const uint8_t* bits, size_t bits_bytes, int32_t N,
+                                const uint8_t* sampled_mask, int32_t n_sampled_masks, const uint32_t* mask_size, const int32_t* pix,
+                                int32_t S, const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
+                                float* out8, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  return pairhead_forward_impl("trase_pairhead_forward_bits", true, feats, F, HW, bits, bits_bytes, N, sampled_mask, n_sampled_masks, mask_size,
+                               pix, S, S_dev, mode, positive_th, negative_th, use_weights, out8, ws, ws_bytes, device, stream_);
 }
 
 int trase_pairhead_backward(int32_t F, int64_t HW, const int32_t* pix, int32_t S, int32_t mode, float positive_th,
@@ -947,23 +979,22 @@ int trase_pairhead_sizes_resized(int32_t S, int32_t Hr, int32_t Wr, int32_t h, i
   return TRASE_OK;
 }
 
-int trase_pairhead_forward_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w,
-                                   const uint8_t* sam_masks, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
-                                   const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
-                                   float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
-                                   int32_t device, trase_stream_t stream_) {
-  if (!feats || !sam_masks || !sampled_mask || !mask_size || !pix || !out8) {
-    set_error("trase_pairhead_forward_resized: null pointer"); return TRASE_ERR_INVALID;
-  }
-  if (int rc = resized_sizes_ok("trase_pairhead_forward_resized", S, Hr, Wr, h, w)) return rc;
-  if (N < 1 || N > PH_MAXN || mode < 0 || mode > 2) { set_error("trase_pairhead_forward_resized: bad arguments"); return TRASE_ERR_INVALID; }
-  if (F != PH_F) { set_error("trase_pairhead_forward_resized: %d feature channels (compiled for %d)", F, PH_F); return TRASE_ERR_INVALID; }
+static int pairhead_forward_resized_impl(const char* who, bool packed, const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h,
+                                         int32_t w, const uint8_t* sam_masks, size_t bits_bytes, int32_t N, const uint8_t* sampled_mask,
+                                         int32_t n_sampled_masks, const uint32_t* mask_size, const int32_t* pix, int32_t S,
+                                         const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
+                                         float* out8, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  if (!feats || !sam_masks || !sampled_mask || !mask_size || !pix || !out8) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  if (int rc = resized_sizes_ok(who, S, Hr, Wr, h, w)) return rc;
+  if (N < 1 || N > PH_MAXN || mode < 0 || mode > 2) { set_error("%s: bad arguments", who); return TRASE_ERR_INVALID; }
+  if (packed) { if (int rc = mask_bits_ok(who, sam_masks, bits_bytes, N, (int64_t)h * w)) return rc; }
+  if (F != PH_F) { set_error("%s: %d feature channels (compiled for %d)", who, F, PH_F); return TRASE_ERR_INVALID; }
   if (n_sampled_masks < 0 || n_sampled_masks > 32 * PH_MAXW) {
-    set_error("trase_pairhead_forward_resized: %d sampled masks (at most %d)", n_sampled_masks, 32 * PH_MAXW); return TRASE_ERR_INVALID;
+    set_error("%s: %d sampled masks (at most %d)", who, n_sampled_masks, 32 * PH_MAXW); return TRASE_ERR_INVALID;
   }
   const ResizeGeom g = resize_geom(Hr, Wr, h, w);
   ResizedWs r;
-  if (!ws || ws_bytes < resized_ws_layout(ws, S, g, r)) { set_error("trase_pairhead_forward_resized: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  if (!ws || ws_bytes < resized_ws_layout(ws, S, g, r)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
   const PairWs& p = r.pair;
   const int HW = h * w;
   hipStream_t stream = (hipStream_t)stream_;
@@ -977,8 +1008,12 @@ int trase_pairhead_forward_resized(const float* feats, int32_t F, int32_t Hr, in
     hipLaunchKernelGGL(ph_tables_kernel, dim3((std::max(Hr, Wr) + 255) / 256), dim3(256), 0, stream, g, r.row_first, r.row_count, r.col_first,
                        r.col_count);
     hipLaunchKernelGGL(ph_slots_kernel, dim3((HW + 255) / 256), dim3(256), 0, stream, pix, S, (const int*)S_dev, HW, r.slot);
-    hipLaunchKernelGGL(ph_gather_kernel<true>, dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, g, sam_masks, N, p.rank,
-                       mask_size, pix, S, (const int*)S_dev, p.fn, p.rinv, p.a, p.bits);
+    if (packed)
+      hipLaunchKernelGGL((ph_gather_kernel<true, true>), dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, g, sam_masks, N, p.rank,
+                         mask_size, pix, S, (const int*)S_dev, p.fn, p.rinv, p.a, p.bits);
+    else
+      hipLaunchKernelGGL((ph_gather_kernel<true, false>), dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, g, sam_masks, N, p.rank,
+                         mask_size, pix, S, (const int*)S_dev, p.fn, p.rinv, p.a, p.bits);
     hipLaunchKernelGGL(ph_consts_kernel, dim3(1), dim3(256), 0, stream, p.a, S, (const int*)S_dev, p.consts);
     hipLaunchKernelGGL(ph_flags_kernel, grid, dim3(256), 0, stream, p.fn, p.bits, S, (const int*)S_dev, positive_th, negative_th, mode, p.colP,
                        p.colN, p.partial);
@@ -989,6 +1024,26 @@ int trase_pairhead_forward_resized(const float* feats, int32_t F, int32_t Hr, in
   }
   TRASE_POST_LAUNCH("pairhead_fwd_resized", stream, 0);
   return TRASE_OK;
+}
+
+int trase_pairhead_forward_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w,
+                                   const uint8_t* sam_masks, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
+                                   const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
+                                   float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
+                                   int32_t device, trase_stream_t stream_) {
+  return pairhead_forward_resized_impl("trase_pairhead_forward_resized", false, feats, F, Hr, Wr, h, w, sam_masks, 0, N, sampled_mask,
+                                       n_sampled_masks, mask_size, pix, S, S_dev, mode, positive_th, negative_th, use_weights, out8, ws,
+                                       ws_bytes, device, stream_);
+}
+
+int trase_pairhead_forward_bits_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const uint8_t* bits,
+                                        size_t bits_bytes, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
+                                        const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
+                                        float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
+                                        int32_t device, trase_stream_t stream_) {
+  return pairhead_forward_resized_impl("trase_pairhead_forward_bits_resized", true, feats, F, Hr, Wr, h, w, bits, bits_bytes, N, sampled_mask,
+                                       n_sampled_masks, mask_size, pix, S, S_dev, mode, positive_th, negative_th, use_weights, out8, ws,
+                                       ws_bytes, device, stream_);
 }
 
 int trase_pairhead_backward_resized(int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const int32_t* pix, int32_t S,

@@ -18,6 +18,14 @@ kernels of ``csrc/pairhead.hip`` evaluate them on the fly:
 the four bilinear taps train.py:283-284's ``interpolate`` would blend -- the resized map is never formed -- and the backward
 writes the full-resolution gradient in one dense pass without atomics; ``with_norm_reg=True`` then is the reference's
 composition: norm at render resolution, pairs at mask resolution.  There is no CPU path.
+
+Wherever ``sam_masks`` is accepted it may be a ``PackedMasks``: the view's masks as the bit stream the reference saves
+(extract_masks.py:91-99), resident on the device at an eighth of the bool bytes and read in place (``csrc/maskbits.hip``) --
+train.py:245-249's per-iteration ``np.array(bitarray.tolist())`` + ``.cuda()`` becomes, once per view,
+
+    sam_masks = PackedMasks.from_saved(torch.load(path), "cuda")
+
+and every result is bitwise what the bool tensor gives.
 """
 from __future__ import annotations
 
@@ -35,6 +43,119 @@ def _dev_index(dev):
     return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
+def _pad16(nbytes: int) -> int:
+    return (nbytes + 15) // 16 * 16
+
+
+_BITREV = None      # 256-entry table: a byte with its bits reversed (a little-endian bitarray's byte -> the stream's)
+
+
+class PackedMasks:
+    """N x H x W bool masks as ``numpy.packbits(masks.reshape(-1))``: stream bit i is bit ``7 - (i & 7)`` of byte ``i >> 3``, mask n
+    starts at stream bit ``n * H * W``, only the last byte is padded.  ``bits`` is a contiguous uint8 tensor whose storage starts
+    on a 16-byte boundary and whose length is a multiple of 16, at least ``ceil(N * H * W / 8)``; what it holds behind bit
+    ``N * H * W`` is never looked at."""
+    __slots__ = ("bits", "N", "H", "W")
+
+    def __init__(self, bits: torch.Tensor, N: int, H: int, W: int):
+        N, H, W = int(N), int(H), int(W)
+        if N < 1 or H < 1 or W < 1:
+            raise ValueError(f"PackedMasks: N, H, W must be >= 1 (got {N}, {H}, {W})")
+        if not torch.is_tensor(bits) or bits.dtype != torch.uint8 or bits.dim() != 1 or not bits.is_contiguous():
+            raise ValueError("PackedMasks: bits must be a contiguous 1-d uint8 tensor")
+        need = (N * H * W + 7) // 8
+        if bits.numel() % 16 or bits.numel() < need:
+            raise ValueError(f"PackedMasks: bits holds {bits.numel()} bytes; need a multiple of 16, at least {need}")
+        if bits.data_ptr() % 16:
+            raise ValueError("PackedMasks: bits must start on a 16-byte boundary")
+        self.bits, self.N, self.H, self.W = bits, N, H, W
+
+    @property
+    def shape(self):
+        return (self.N, self.H, self.W)
+
+    @property
+    def device(self):
+        return self.bits.device
+
+    def _gpu(self):
+        if self.bits.device.type != "cuda":
+            raise RuntimeError("trase_amd.feature_head runs on the GPU only (there is no CPU path)")
+        return self
+
+    @staticmethod
+    @torch.no_grad()
+    def from_bool(masks: torch.Tensor) -> "PackedMasks":
+        """Pack an (N, H, W) bool or byte tensor (any non-zero value is set) on the device."""
+        if masks.device.type != "cuda":
+            raise RuntimeError("trase_amd.feature_head runs on the GPU only (there is no CPU path)")
+        if masks.dim() != 3 or masks.dtype not in (torch.bool, torch.uint8, torch.int8):
+            raise ValueError("masks must be [N, H, W] bool or byte")
+        m = masks.contiguous().view(torch.uint8)
+        N, H, W = m.shape
+        dev = m.device
+        bits = torch.empty(_pad16((N * H * W + 7) // 8), dtype=torch.uint8, device=dev)
+        lib = _lib.load()
+        _lib.check(lib.trase_pack_masks(_lib.ptr(m), N, H * W, _lib.ptr(bits), bits.numel(), _dev_index(dev), _stream(dev)),
+                   "trase_pack_masks")
+        return PackedMasks(bits, N, H, W)
+
+    @torch.no_grad()
+    def to_bool(self) -> torch.Tensor:
+        """The (N, H, W) bool tensor, unpacked on the device."""
+        dev = self._gpu().bits.device
+        out = torch.empty(self.shape, dtype=torch.uint8, device=dev)
+        lib = _lib.load()
+        _lib.check(lib.trase_unpack_masks(_lib.ptr(self.bits), self.bits.numel(), self.N, self.H * self.W, _lib.ptr(out), _dev_index(dev),
+                                          _stream(dev)), "trase_unpack_masks")
+        return out.view(torch.bool)
+
+    @staticmethod
+    def host_stream(obj):
+        """(padded uint8 numpy buffer, N, H, W) of the reference's saved dict ``{'masks', 'N', 'H', 'W'}``: ``'masks'`` is ``bytes``,
+        a uint8 array or tensor, or anything with ``.tobytes()`` (a ``bitarray``; a ``.endian()`` of ``'little'`` is bit-reversed per
+        byte through a 256-entry table).  One copy into the zero-padded buffer; never a list of bools."""
+        import numpy as np
+        global _BITREV
+        N, H, W = int(obj["N"]), int(obj["H"]), int(obj["W"])
+        if N < 1 or H < 1 or W < 1:
+            raise ValueError(f"PackedMasks: N, H, W must be >= 1 (got {N}, {H}, {W})")
+        need = (N * H * W + 7) // 8
+        raw = obj["masks"]
+        little = False
+        if torch.is_tensor(raw):
+            if raw.dtype != torch.uint8:
+                raise ValueError("PackedMasks: a tensor of stream bytes must be uint8")
+            src = raw.detach().cpu().contiguous().reshape(-1).numpy()
+        elif isinstance(raw, np.ndarray):
+            if raw.dtype != np.uint8:
+                raise ValueError("PackedMasks: an array of stream bytes must be uint8")
+            src = raw.reshape(-1)
+        elif isinstance(raw, (bytes, bytearray, memoryview)):
+            src = np.frombuffer(raw, dtype=np.uint8)
+        elif hasattr(raw, "tobytes"):
+            little = hasattr(raw, "endian") and raw.endian() == "little"
+            src = np.frombuffer(raw.tobytes(), dtype=np.uint8)
+        else:
+            raise ValueError(f"PackedMasks: cannot read a mask stream from {type(raw).__name__}")
+        if src.size < need:
+            raise ValueError(f"PackedMasks: {src.size} stream bytes for {N} x {H} x {W} masks (need {need})")
+        buf = np.zeros(_pad16(need), dtype=np.uint8)
+        if little:
+            if _BITREV is None:
+                _BITREV = np.array([int(f"{i:08b}"[::-1], 2) for i in range(256)], dtype=np.uint8)
+            np.take(_BITREV, src[:need], out=buf[:need])
+        else:
+            buf[:need] = src[:need]
+        return buf, N, H, W
+
+    @staticmethod
+    def from_saved(obj, device="cuda") -> "PackedMasks":
+        """The reference's saved masks (extract_masks.py:91-99) on ``device``: one host copy (host_stream), one upload."""
+        buf, N, H, W = PackedMasks.host_stream(obj)
+        return PackedMasks(torch.from_numpy(buf).to(device), N, H, W)
+
+
 def _masks_u8(sam_masks: torch.Tensor) -> torch.Tensor:
     if sam_masks.device.type != "cuda":
         raise RuntimeError("trase_amd.feature_head runs on the GPU only (there is no CPU path)")
@@ -45,9 +166,18 @@ def _masks_u8(sam_masks: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def mask_stats(sam_masks: torch.Tensor):
+def mask_stats(sam_masks):
     """(cover_count [H, W] int32, mask_size [N] int32): ``sam_masks.sum(dim=0)`` and ``sam_masks.sum(-1).sum(-1)``
-    (utils/feature_utils.py:23, :30) in one pass over the masks."""
+    (utils/feature_utils.py:23, :30) in one pass over the masks (a tensor or a PackedMasks)."""
+    if isinstance(sam_masks, PackedMasks):
+        N, H, W = sam_masks._gpu().shape
+        dev = sam_masks.device
+        cover = torch.empty((H, W), dtype=torch.int32, device=dev)
+        size = torch.empty((N,), dtype=torch.int32, device=dev)
+        lib = _lib.load()
+        _lib.check(lib.trase_mask_stats_bits(_lib.ptr(sam_masks.bits), sam_masks.bits.numel(), N, H * W, _lib.ptr(cover), _lib.ptr(size),
+                                             _dev_index(dev), _stream(dev)), "trase_mask_stats_bits")
+        return cover, size
     m = _masks_u8(sam_masks)
     N, H, W = m.shape
     dev = m.device
@@ -60,13 +190,18 @@ def mask_stats(sam_masks: torch.Tensor):
 
 
 @torch.no_grad()
-def get_sample_pixel_and_mask(sam_masks, num_sampled_pixels, num_sampled_masks, cover_count=None, rng="cpu"):
+def get_sample_pixel_and_mask(sam_masks, num_sampled_pixels, num_sampled_masks, cover_count=None, rng="cpu", exclude=None):
     """utils/feature_utils.py:17-26, the non-mask region taken from ``mask_stats`` instead of an int64 N x H x W
     reduction.  ``rng="cpu"`` (default) makes the same draws as the reference -- ``torch.rand`` on the CPU generator, in
     the same order, then copied to the GPU -- which costs ~3.4 ms at 1080p (2 M scalar Mersenne-Twister draws + an 8 MB
-    copy); ``rng="cuda"`` draws the same Bernoulli fields from torch's CUDA generator (~0.03 ms)."""
+    copy); ``rng="cuda"`` draws the same Bernoulli fields from torch's CUDA generator (~0.03 ms).
+    ``exclude``: an (H, W) bool tensor of pixels to leave out of the draw (``black_mask`` of train.py:253-269's
+    ``mask_black_bg``), removed here -- before the count tag is attached -- so that the head stays on its sync-free path; the tag
+    keeps the draw's target count, which is an upper estimate for buffer sizing only."""
     if rng not in ("cpu", "cuda"):
         raise ValueError("rng must be 'cpu' or 'cuda'")
+    if exclude is not None and tuple(exclude.shape) != tuple(sam_masks.shape[-2:]):
+        raise ValueError(f"exclude must be [{sam_masks.shape[-2]}, {sam_masks.shape[-1]}] (got {list(exclude.shape)})")
     if cover_count is None:
         cover_count, _ = mask_stats(sam_masks)
     dev = sam_masks.device
@@ -76,6 +211,8 @@ def get_sample_pixel_and_mask(sam_masks, num_sampled_pixels, num_sampled_masks, 
     pixel_sample_rate = num_sampled_pixels / (sam_masks.shape[-1] * sam_masks.shape[-2])
     sampled_pixel = torch.rand(sam_masks.shape[-2], sam_masks.shape[-1], device=where).to(dev) < pixel_sample_rate
     sampled_pixel = torch.logical_and(sampled_pixel, cover_count != 0)
+    if exclude is not None:
+        sampled_pixel = torch.logical_and(sampled_pixel, torch.logical_not((exclude != 0).to(dev)))
     # (how many pixels the draw aims at: lets contrastive_head size its buffers without reading the count back from the device)
     # tied to THIS tensor's contents: (target count, number of pixels of the draw, version counter) -- an in-place edit afterwards
     # (`sampled_pixel |= ...`) bumps the version and contrastive_head falls back to counting
@@ -126,10 +263,16 @@ class _PairHead(torch.autograd.Function):
         ws = _bytes(nbytes.value, dev)
         out8 = torch.empty(8, device=dev)
         d = _dev_index(dev)
-        _lib.check(lib.trase_pairhead_forward_n(_lib.ptr(f), F, H * W, _lib.ptr(masks_u8), masks_u8.shape[0], _lib.ptr(sampled_mask_u8),
-                                                int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S, _lib.ptr(s_dev), int(mode), float(pth),
-                                                float(nth), int(use_w), _lib.ptr(out8), _lib.ptr(ws), ws.numel(), d, _stream(dev)),
-                   "trase_pairhead_forward")
+        if isinstance(masks_u8, PackedMasks):       # the stream in place of the bool bytes: same workspace, same backward
+            _lib.check(lib.trase_pairhead_forward_bits(_lib.ptr(f), F, H * W, _lib.ptr(masks_u8.bits), masks_u8.bits.numel(), masks_u8.N,
+                                                       _lib.ptr(sampled_mask_u8), int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S,
+                                                       _lib.ptr(s_dev), int(mode), float(pth), float(nth), int(use_w), _lib.ptr(out8),
+                                                       _lib.ptr(ws), ws.numel(), d, _stream(dev)), "trase_pairhead_forward_bits")
+        else:
+            _lib.check(lib.trase_pairhead_forward_n(_lib.ptr(f), F, H * W, _lib.ptr(masks_u8), masks_u8.shape[0], _lib.ptr(sampled_mask_u8),
+                                                    int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S, _lib.ptr(s_dev), int(mode), float(pth),
+                                                    float(nth), int(use_w), _lib.ptr(out8), _lib.ptr(ws), ws.numel(), d, _stream(dev)),
+                       "trase_pairhead_forward")
         ctx.s_dev = s_dev
         sims = out8[4:6].clone()
         ctx.mark_non_differentiable(sims)
@@ -184,10 +327,17 @@ class _PairHeadResized(torch.autograd.Function):
         ws = _bytes(nbytes.value, dev)
         out8 = torch.empty(8, device=dev)
         d = _dev_index(dev)
-        _lib.check(lib.trase_pairhead_forward_resized(_lib.ptr(f), F, Hr, Wr, h, w, _lib.ptr(masks_u8), N, _lib.ptr(sampled_mask_u8),
-                                                      int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S, _lib.ptr(s_dev), int(mode),
-                                                      float(pth), float(nth), int(use_w), _lib.ptr(out8), _lib.ptr(ws), ws.numel(), d,
-                                                      _stream(dev)), "trase_pairhead_forward_resized")
+        if isinstance(masks_u8, PackedMasks):
+            _lib.check(lib.trase_pairhead_forward_bits_resized(_lib.ptr(f), F, Hr, Wr, h, w, _lib.ptr(masks_u8.bits), masks_u8.bits.numel(), N,
+                                                               _lib.ptr(sampled_mask_u8), int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S,
+                                                               _lib.ptr(s_dev), int(mode), float(pth), float(nth), int(use_w), _lib.ptr(out8),
+                                                               _lib.ptr(ws), ws.numel(), d, _stream(dev)),
+                       "trase_pairhead_forward_bits_resized")
+        else:
+            _lib.check(lib.trase_pairhead_forward_resized(_lib.ptr(f), F, Hr, Wr, h, w, _lib.ptr(masks_u8), N, _lib.ptr(sampled_mask_u8),
+                                                          int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S, _lib.ptr(s_dev), int(mode),
+                                                          float(pth), float(nth), int(use_w), _lib.ptr(out8), _lib.ptr(ws), ws.numel(), d,
+                                                          _stream(dev)), "trase_pairhead_forward_resized")
         ctx.s_dev = s_dev
         sims = out8[4:6].clone()
         ctx.mark_non_differentiable(sims)
@@ -262,10 +412,10 @@ def contrastive_head(rendered_features, sam_masks, sampled_pixel, sampled_mask, 
     ``rendered_features`` is (32, Hr, Wr); where (Hr, Wr) is not the masks' (H, W) the sampled columns are those of train.py:284's
     bilinear ``interpolate`` to (H, W), taken as four taps each.  ``with_norm_reg=True`` also returns the regulariser
     ``(1 - rendered_features.norm(dim=0).mean()) ** 2`` (train.py:280-282) of the image as rendered, and shares one dense
-    gradient pass with the pair losses."""
+    gradient pass with the pair losses.  ``sam_masks`` is the (N, H, W) tensor or a PackedMasks (bitwise the same results)."""
     if mode not in _MODES:
         raise ValueError(f"contrastive mode {mode!r} (expected one of {sorted(_MODES)})")
-    m = _masks_u8(sam_masks)
+    m = sam_masks._gpu() if isinstance(sam_masks, PackedMasks) else _masks_u8(sam_masks)
     N, H, W = m.shape
     if rendered_features.dim() != 3 or rendered_features.shape[0] != 32 or min(rendered_features.shape[1:]) < 1:
         raise ValueError("rendered_features must be (32, Hr, Wr)")
