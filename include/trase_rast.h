@@ -497,6 +497,28 @@ int trase_prof_report(char* buf, size_t buf_bytes); /* JSON object {"kernel": {"
  * (DPP reductions, ballots, MFMA fragment layouts).  Returns 0 when all pass. */
 int trase_selftest(int32_t device, trase_stream_t stream, char* msg, size_t msg_bytes);
 
+/* Test entry points of the integer primitives under everything else (binning.hip): the radix sort, the tile ranges and the
+ * zero fill, each driven once on the caller's data.  They allocate for themselves and synchronise; not for any hot path.
+ *
+ * trase_selftest_sort: one radix_sort_pairs call over `cap` items laid out by the library's own sort layout.  keys (cap device
+ * words) and vals (cap device words, or NULL for iota values) are copied into ping-pong buffer `start`; the other pair -- and
+ * vals[start] under iota -- is filled with `sentinel`; the device-side count is n (may exceed cap: the kernels clamp it).
+ * hist_copies 0 = the layout's default rule.  use_flag != 0 passes flag_key and a zeroed flag word.  keys_out / vals_out (cap
+ * device words each) receive the WHOLE result buffers; result[0..2] (host) = {index of the result buffers, flag word, 1 when
+ * the short sort's fused passes ran}. */
+int trase_selftest_sort(const uint32_t* keys, const uint32_t* vals, uint32_t n, uint32_t cap, int32_t bit_lo, int32_t bit_hi,
+                        int32_t digit_bits, int32_t hist_copies, int32_t start, uint32_t flag_key, int32_t use_flag,
+                        uint32_t sentinel, uint32_t* keys_out, uint32_t* vals_out, uint32_t* result, int32_t device,
+                        trase_stream_t stream);
+/* trase_selftest_tile_ranges: launch_tile_ranges on the caller's key pointer AS GIVEN (one that is not 16-byte aligned reaches
+ * the grid-stride kernel; an aligned one must have cap rounded up to 4 readable words) with the device-side count n.  ranges:
+ * T pairs of device words the caller has prefilled (cleared first when clear != 0).  dbg (3 host words) = the out-of-range-key
+ * record {seen, index, key}. */
+int trase_selftest_tile_ranges(const uint32_t* keys, uint32_t n, uint32_t cap, int32_t T, int32_t clear, uint32_t* ranges,
+                               uint32_t* dbg, int32_t device, trase_stream_t stream);
+/* trase_selftest_zero_bytes: launch_zero_bytes(p, bytes) on the caller's device pointer, any alignment. */
+int trase_selftest_zero_bytes(void* p, size_t bytes, int32_t device, trase_stream_t stream);
+
 const char* trase_last_error(void);
 const char* trase_version(void);
 

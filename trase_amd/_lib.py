@@ -303,6 +303,12 @@ SYMBOLS = [
     ("trase_prof_enable", C.c_int, [C.c_int]),
     ("trase_prof_report", C.c_int, [C.c_char_p, C.c_size_t]),
     ("trase_selftest", C.c_int, [C.c_int32, C.c_void_p, C.c_char_p, C.c_size_t]),
+    ("trase_selftest_sort", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_uint32 * 3), C.c_int32, C.c_void_p]),
+    ("trase_selftest_tile_ranges", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.POINTER(C.c_uint32 * 3), C.c_int32, C.c_void_p]),
+    ("trase_selftest_zero_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     ("trase_last_error", C.c_char_p, []),
     ("trase_version", C.c_char_p, []),
 ]

@@ -346,6 +346,10 @@ int launch_split_pair_ids(const LaunchCtx& c, const uint32_t* sorted, int P, uin
 }
 
 int radix_passes(int bit_lo, int bit_hi, int digit_bits) { return (bit_hi - bit_lo + digit_bits - 1) / digit_bits; }
+bool radix_sort_is_short(int nb, int hist_copies, int passes) {
+  static const bool small_off = [] { const char* e = getenv("TRASE_SORT_SMALL"); return e && atoi(e) == 0; }();
+  return nb <= RS_SMALL_NB && hist_copies >= passes && !small_off;
+}
 
 // digit_bits 8 or 9 (SortBufs::hist / digit_total must be laid out for it: sort_layout in common.h);
 // `start`: which of the ping-pong buffers holds the input
@@ -358,8 +362,7 @@ static int radix_sort_pairs_t(const LaunchCtx& c, const SortBufs& t, const uint3
   if (nb > t.nb_max) { set_error("radix_sort_pairs: nb %d > nb_max %d", nb, t.nb_max); return TRASE_ERR_WORKSPACE; }
   const int passes = radix_passes(bit_lo, bit_hi, DB);
   if (passes > RS_MAX_PASSES) return TRASE_ERR_INVALID;
-  static const bool small_off = [] { const char* e = getenv("TRASE_SORT_SMALL"); return e && atoi(e) == 0; }();
-  if (nb <= RS_SMALL_NB && t.hist_copies >= passes && !small_off) {
+  if (radix_sort_is_short(nb, t.hist_copies, passes)) {
     // short sort: 1 + passes launches (see RS_SMALL_NB in common.h)
     const size_t hw = (size_t)ND * t.nb_max;
     for (int p = 0; p < passes; ++p) {

@@ -484,6 +484,9 @@ int launch_label_sums(const float* X, int N, int D, const int32_t* ids, const in
 int launch_evaluate(const TraseEvalFrame& f, const float* final_T, hipStream_t stream);
 int launch_split_pair_ids(const LaunchCtx& c, const uint32_t* sorted, int P, uint32_t* ids0, uint32_t* ids1);
 int radix_passes(int bit_lo, int bit_hi, int digit_bits = 8);
+// whether a sort of nb workgroups over `passes` digits takes the short sorts' fused passes (RS_SMALL_NB; TRASE_SORT_SMALL=0, read
+// once per process, turns them off): the one copy of the condition, for radix_sort_pairs and the sort's test entry point
+bool radix_sort_is_short(int nb, int hist_copies, int passes);
 // The depth sort (round 5).  Default: an order-preserving 27-bit key -- the float32 depth bits ABOVE those of the 0.2 near-cull
 // plane (z > 0.2 for every live Gaussian), saturated at 2^27 - 2 -- in THREE 9-bit passes (9 launches; measured -16 us per view
 // against four 8-bit passes over the raw float bits, point lists bit-identical).  Exact as long as no live Gaussian lies beyond

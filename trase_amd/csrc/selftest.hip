@@ -110,3 +110,93 @@ extern "C" int trase_selftest(int32_t device, trase_stream_t stream_, char* msg,
   }
   return bad;
 }
+
+// ---- test entry points of the radix sort, the tile ranges and the zero fill (binning.hip) ------------------------------------
+namespace {
+struct DevBlock {          // one allocation, freed on every way out
+  void* p = nullptr;
+  ~DevBlock() { if (p) hipFree(p); }
+};
+}  // namespace
+
+extern "C" int trase_selftest_sort(const uint32_t* keys, const uint32_t* vals, uint32_t n, uint32_t cap, int32_t bit_lo,
+                                   int32_t bit_hi, int32_t digit_bits, int32_t hist_copies, int32_t start, uint32_t flag_key,
+                                   int32_t use_flag, uint32_t sentinel, uint32_t* keys_out, uint32_t* vals_out, uint32_t* result,
+                                   int32_t device, trase_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!keys || !keys_out || !vals_out || !result || cap < 1 || (digit_bits != 8 && digit_bits != 9) || bit_lo < 0 ||
+      bit_hi <= bit_lo || bit_hi > 32 || hist_copies < 0 || (start != 0 && start != 1)) {
+    set_error("trase_selftest_sort: bad arguments");
+    return TRASE_ERR_INVALID;
+  }
+  TRASE_CHECK(hipSetDevice(device));
+  // the library's own layout of a sort of `cap` items, then the two device words of the call
+  SortBufs s{};
+  uint32_t *n_dev = nullptr, *flag_dev = nullptr;
+  auto layout = [&](void* ws) {
+    WsCursor w(ws);
+    sort_layout(w, s, cap, SORT_ALL, digit_bits, hist_copies);
+    n_dev = w.take<uint32_t>(1);
+    flag_dev = w.take<uint32_t>(1);
+    return w.bytes();
+  };
+  const size_t bytes = layout(nullptr);
+  DevBlock blk;
+  TRASE_CHECK(hipMalloc(&blk.p, bytes));
+  layout(blk.p);
+  // histograms and digit totals start as garbage: the sort must not rely on what an earlier call left there
+  TRASE_CHECK(hipMemsetAsync(blk.p, 0xCD, bytes, stream));
+  const size_t cb = sizeof(uint32_t) * (size_t)cap;
+  TRASE_CHECK(hipMemsetD32Async((hipDeviceptr_t)s.keys[start ^ 1], (int)sentinel, cap, stream));
+  TRASE_CHECK(hipMemsetD32Async((hipDeviceptr_t)s.vals[start ^ 1], (int)sentinel, cap, stream));
+  TRASE_CHECK(hipMemcpyAsync(s.keys[start], keys, cb, hipMemcpyDeviceToDevice, stream));
+  if (vals) TRASE_CHECK(hipMemcpyAsync(s.vals[start], vals, cb, hipMemcpyDeviceToDevice, stream));
+  else TRASE_CHECK(hipMemsetD32Async((hipDeviceptr_t)s.vals[start], (int)sentinel, cap, stream));
+  TRASE_CHECK(hipMemcpyAsync(n_dev, &n, sizeof(n), hipMemcpyHostToDevice, stream));
+  TRASE_CHECK(hipMemsetAsync(flag_dev, 0, sizeof(uint32_t), stream));
+  const LaunchCtx c{stream, 0, 0};
+  int out_idx = -1;
+  const int rc = radix_sort_pairs(c, s, n_dev, cap, bit_lo, bit_hi, vals == nullptr, &out_idx, digit_bits, start, flag_key,
+                                  use_flag ? flag_dev : nullptr);
+  if (rc != TRASE_OK) { hipStreamSynchronize(stream); return rc; }
+  uint32_t flag = 0;
+  TRASE_CHECK(hipMemcpyAsync(keys_out, s.keys[out_idx], cb, hipMemcpyDeviceToDevice, stream));
+  TRASE_CHECK(hipMemcpyAsync(vals_out, s.vals[out_idx], cb, hipMemcpyDeviceToDevice, stream));
+  TRASE_CHECK(hipMemcpyAsync(&flag, flag_dev, sizeof(flag), hipMemcpyDeviceToHost, stream));
+  TRASE_CHECK(hipStreamSynchronize(stream));
+  result[0] = (uint32_t)out_idx;
+  result[1] = flag;
+  result[2] = radix_sort_is_short(rs_blocks(cap), s.hist_copies, radix_passes(bit_lo, bit_hi, digit_bits)) ? 1u : 0u;
+  return TRASE_OK;
+}
+
+extern "C" int trase_selftest_tile_ranges(const uint32_t* keys, uint32_t n, uint32_t cap, int32_t T, int32_t clear,
+                                          uint32_t* ranges, uint32_t* dbg, int32_t device, trase_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!keys || !ranges || !dbg || T < 1) {
+    set_error("trase_selftest_tile_ranges: bad arguments");
+    return TRASE_ERR_INVALID;
+  }
+  TRASE_CHECK(hipSetDevice(device));
+  DevBlock blk;                                   // {n, dbg[3]}
+  TRASE_CHECK(hipMalloc(&blk.p, 4 * sizeof(uint32_t)));
+  uint32_t* w = (uint32_t*)blk.p;
+  const uint32_t init[4] = {n, 0u, 0u, 0u};
+  TRASE_CHECK(hipMemcpyAsync(w, init, sizeof(init), hipMemcpyHostToDevice, stream));
+  const LaunchCtx c{stream, 0, 0};
+  const int rc = launch_tile_ranges(c, keys, w, cap, (uint2*)ranges, T, w + 1, clear != 0);
+  if (rc != TRASE_OK) { hipStreamSynchronize(stream); return rc; }
+  TRASE_CHECK(hipMemcpyAsync(dbg, w + 1, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  TRASE_CHECK(hipStreamSynchronize(stream));
+  return TRASE_OK;
+}
+
+extern "C" int trase_selftest_zero_bytes(void* p, size_t bytes, int32_t device, trase_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  const int rc = launch_zero_bytes(p, bytes, stream);
+  if (rc != TRASE_OK) return rc;
+  TRASE_CHECK(hipGetLastError());
+  TRASE_CHECK(hipStreamSynchronize(stream));
+  return TRASE_OK;
+}

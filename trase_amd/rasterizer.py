@@ -793,3 +793,44 @@ def selftest(device=None) -> str:
     if rc != 0:
         raise RuntimeError(f"trase_selftest failed ({rc}):\n{msg}\n{_lib.last_error()}")
     return msg
+
+
+def selftest_sort(keys, vals, n, bit_lo, bit_hi, digit_bits=8, hist_copies=0, start=0, flag_key=None, sentinel=0xDEADBEEF):
+    """One radix_sort_pairs call (test entry point).  keys: int32 device tensor of `cap` words (the bit patterns of the uint32
+    keys); vals: the same shape, or None for iota values; n: the device-side count.  Returns (keys_out, vals_out, out_idx,
+    flag_word, short): the WHOLE cap-sized result buffers, which ping-pong pair they were, the saturated-key watch's word (0
+    without flag_key) and whether the short sort's fused passes ran."""
+    assert keys.is_cuda and keys.dtype == torch.int32 and keys.is_contiguous()
+    assert vals is None or (vals.is_cuda and vals.dtype == torch.int32 and vals.is_contiguous() and vals.shape == keys.shape)
+    dev = keys.device
+    d = dev.index if dev.index is not None else torch.cuda.current_device()
+    keys_out, vals_out = torch.empty_like(keys), torch.empty_like(keys)
+    res = (C.c_uint32 * 3)()
+    _lib.check(_lib.load().trase_selftest_sort(
+        _lib.ptr(keys), _lib.ptr(vals), int(n), keys.numel(), int(bit_lo), int(bit_hi), int(digit_bits), int(hist_copies),
+        int(start), 0 if flag_key is None else int(flag_key), 0 if flag_key is None else 1, int(sentinel), _lib.ptr(keys_out),
+        _lib.ptr(vals_out), C.byref(res), d, _stream(dev)), "trase_selftest_sort")
+    return keys_out, vals_out, int(res[0]), int(res[1]), bool(res[2])
+
+
+def selftest_tile_ranges(keys, n, cap, ranges, T, clear=True):
+    """launch_tile_ranges on `keys` as given (test entry point): an int32 device tensor or view whose data pointer decides between
+    the 16-byte and the grid-stride kernel.  ranges: (>= T, 2) int32 device tensor, prefilled by the caller, written in place.
+    Returns the three words of the out-of-range-key record."""
+    assert keys.is_cuda and keys.dtype == torch.int32 and keys.is_contiguous()
+    assert ranges.is_cuda and ranges.dtype == torch.int32 and ranges.is_contiguous() and ranges.numel() >= 2 * T
+    dev = keys.device
+    d = dev.index if dev.index is not None else torch.cuda.current_device()
+    dbg = (C.c_uint32 * 3)()
+    _lib.check(_lib.load().trase_selftest_tile_ranges(_lib.ptr(keys), int(n), int(cap), int(T), int(bool(clear)), _lib.ptr(ranges),
+                                                      C.byref(dbg), d, _stream(dev)), "trase_selftest_tile_ranges")
+    return [int(x) for x in dbg]
+
+
+def selftest_zero_bytes(buf, offset, nbytes):
+    """launch_zero_bytes on buf.data_ptr() + offset for nbytes bytes (test entry point); buf: uint8 device tensor."""
+    assert buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous() and 0 <= offset and offset + nbytes <= buf.numel()
+    dev = buf.device
+    d = dev.index if dev.index is not None else torch.cuda.current_device()
+    _lib.check(_lib.load().trase_selftest_zero_bytes(C.c_void_p(buf.data_ptr() + offset), int(nbytes), d, _stream(dev)),
+               "trase_selftest_zero_bytes")
