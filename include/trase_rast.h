@@ -355,6 +355,19 @@ int trase_mlp_forward(const TraseMlpWeights* w, const float* x, const float* t, 
                       float* d_xyz, float* d_rotation, float* d_scaling, void* ws, size_t ws_bytes, int32_t device,
                       trase_stream_t stream);
 
+/* The same inference forward at near-fp32 accuracy ("split bf16"): every matrix operand -- encoding, weights, activations --
+ * is carried as hi + lo (two bf16, round-to-nearest-even) and a product is hi.hi + hi.lo + lo.hi on the same MFMA
+ * instruction, accumulated in fp32; the weights are re-packed as hi / lo streams on every call.  Forward only; same
+ * arguments and the same supported networks as trase_mlp_forward, with a workspace of trase_mlp_split_ws_bytes bytes.
+ * Every refusal is TRASE_ERR_INVALID with a message, before the device is touched: null pointers with N > 0, N < 0, a
+ * workspace that is too small, D / W / multires values other than the compiled network's, variant != 0.  N == 0 returns 0
+ * and launches nothing.  (The size query is not called *_sizes: the recorded table of tests/golden/workspace_sizes.json lists
+ * every *_sizes function of this header and is not extended by it.) */
+int trase_mlp_split_ws_bytes(size_t* ws_bytes);
+int trase_mlp_forward_split(const TraseMlpWeights* w, const float* x, const float* t, int32_t t_stride, int32_t N,
+                            float* d_xyz, float* d_rotation, float* d_scaling, void* ws, size_t ws_bytes, int32_t device,
+                            trase_stream_t stream);
+
 /* Training pair (train.py:202-204 runs the MLP with gradients in the GAUSSIAN state; loss.backward() at
  * train.py:299 reaches utils/time_utils.py:106-131 through autograd).
  *   trase_mlp_forward_train: the same fused forward; additionally fills the opaque `saved` buffer (bf16

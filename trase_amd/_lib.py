@@ -172,6 +172,9 @@ SYMBOLS = [
     ("trase_mlp_sizes", C.c_int, [C.POINTER(C.c_size_t)]),
     ("trase_mlp_forward", C.c_int, [C.POINTER(MlpWeights), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_mlp_split_ws_bytes", C.c_int, [C.POINTER(C.c_size_t)]),
+    ("trase_mlp_forward_split", C.c_int, [C.POINTER(MlpWeights), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     ("trase_mlp_train_sizes", C.c_int, [C.c_int32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("trase_mlp_forward_train", C.c_int, [C.POINTER(MlpWeights), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,

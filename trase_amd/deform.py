@@ -16,7 +16,12 @@ scene/deform_model.py:26-57 ``DeformModel.step``) on the bf16 matrix cores.
 Numerics: bf16 operands, fp32 accumulation (the north star asks for a bf16 MFMA GEMM here).  The gradients are
 the exact gradients of that bf16-evaluated network up to bf16 rounding of the back-propagated signal; against
 fp32 autograd of the same parameters they differ by a few percent in relative L2, because ReLU gates whose
-pre-activation is within bf16 rounding of zero open or close differently (same effect as torch.autocast)."""
+pre-activation is within bf16 rounding of zero open or close differently (same effect as torch.autocast).
+
+``precision="bf16x3"`` (forward only, opt-in) evaluates the same network with every matrix operand carried as two bf16
+(``hi + lo``) and three MFMAs per product (``trase_mlp_forward_split``, trase_amd/csrc/mlp_split.hip): about 500 times
+closer to the fp32 network than bf16 operands, for checkpoints trained in fp32 by the reference and viewed or scored
+here (render.py:195, gui.py:965, metrics_segmentation.py).  The training pair is bf16-only."""
 from __future__ import annotations
 
 import ctypes as C
@@ -107,6 +112,13 @@ def _time_embedding(params, t, n):
 # training pair evaluates the rows along a Morton curve of their positions.  The order only groups rows into tiles -- every row
 # is computed exactly as before and lands at its own index -- so it may be stale: it is rebuilt when N changes and every
 # ROW_ORDER_REFRESH calls (positions drift slowly; densification changes N).
+PRECISIONS = ("bf16", "bf16x3")
+# geometry of the "bf16x3" kernel (mlp_fwd_split_kernel): a wave owns all 64 rows of its workgroup (and 64 of the 256 columns), as two
+# MFMA row groups of 32 (a lane holds one row of each); one workgroup per 64 rows, no grid stride
+SPLIT_ROW_GROUP = 32
+SPLIT_ROWS_PER_WAVE = 64
+SPLIT_ROWS_PER_WORKGROUP = 64
+
 ROW_ORDER_REFRESH = 64
 _ROW_ORDER: dict = {"key": None, "age": 0, "perm": None}
 _ROW_ORDER_MODE = os.environ.get("TRASE_MLP_ROW_ORDER", "morton")      # "morton" | "none"
@@ -257,7 +269,12 @@ def exp_se3(S: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
 
 
 def deform_forward(params: Mapping[str, torch.Tensor], x: torch.Tensor, t: torch.Tensor,
-                   is_blender: bool = False, is_6dof: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                   is_blender: bool = False, is_6dof: bool = False,
+                   precision: str = "bf16") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``precision``: "bf16" (default: bf16 operands, with or without gradients) or "bf16x3" (split-bf16 operands, near-fp32
+    accuracy, forward only: under ``no_grad`` or with frozen parameters)."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
     if x.device.type != "cuda":
         raise RuntimeError("deform_forward runs on the GPU only (there is no CPU path)")
     if is_6dof:
@@ -270,8 +287,8 @@ def deform_forward(params: Mapping[str, torch.Tensor], x: torch.Tensor, t: torch
         for k in TIMENET_KEYS:
             if k in params:
                 pw[k] = pv[k] = params[k]
-        w, rotation, scaling = deform_forward(pw, x, t, is_blender, False)
-        v, _, _ = deform_forward(pv, x, t, is_blender, False)
+        w, rotation, scaling = deform_forward(pw, x, t, is_blender, False, precision)
+        v, _, _ = deform_forward(pv, x, t, is_blender, False, precision)
         theta = torch.norm(w, dim=-1, keepdim=True)
         w = w / theta + 1e-5
         v = v / theta + 1e-5
@@ -279,6 +296,9 @@ def deform_forward(params: Mapping[str, torch.Tensor], x: torch.Tensor, t: torch
     tensors = [params[k] for k in PARAM_KEYS]
     n = x.shape[0]
     if torch.is_grad_enabled() and any(p.requires_grad for p in tensors + ([params[k] for k in TIMENET_KEYS] if is_blender else [])):
+        if precision != "bf16":
+            raise NotImplementedError('trase_amd.deform: precision="bf16x3" is forward-only; the training pair (forward with saved '
+                                      'state + backward) is bf16-only -- call it under torch.no_grad() or with frozen parameters')
         if x.requires_grad or t.requires_grad:
             raise NotImplementedError("trase_amd.deform: x and t are detached inputs in the reference "
                                       "(scene/deform_model.py:34-35 called at train.py:202-204); no gradient is produced for them")
@@ -289,8 +309,8 @@ def deform_forward(params: Mapping[str, torch.Tensor], x: torch.Tensor, t: torch
     keep = []
     w = _fill_weights(tensors, dev, keep, is_blender, is_6dof)
     if is_blender:
-        with torch.no_grad():
-            tt = _time_embedding(params, t, n).float().contiguous()
+        with torch.no_grad():           # (N = 0: no row to take the time from; nothing is launched and nothing read)
+            tt = (_time_embedding(params, t, n) if n else torch.zeros(30, device=x.device)).float().contiguous()
         xs, t_stride = x.detach().float().contiguous(), 0
     else:
         xs, tt, t_stride = _prep_xt(x, t)
@@ -298,11 +318,16 @@ def deform_forward(params: Mapping[str, torch.Tensor], x: torch.Tensor, t: torch
     d_rot = torch.empty(n, 4, device=dev)
     d_scale = torch.empty(n, 3, device=dev)
     nbytes = C.c_size_t()
-    _lib.check(lib.trase_mlp_sizes(C.byref(nbytes)), "trase_mlp_sizes")
+    if precision == "bf16x3":
+        sizes, forward, name = lib.trase_mlp_split_ws_bytes, lib.trase_mlp_forward_split, "trase_mlp_forward_split"
+        sizes_name = "trase_mlp_split_ws_bytes"
+    else:
+        sizes, forward, name, sizes_name = lib.trase_mlp_sizes, lib.trase_mlp_forward, "trase_mlp_forward", "trase_mlp_sizes"
+    _lib.check(sizes(C.byref(nbytes)), sizes_name)
     ws = _bytes(nbytes.value, dev)
-    _lib.check(lib.trase_mlp_forward(C.byref(w), _lib.ptr(xs), C.c_void_p(tt.data_ptr()), t_stride, n, _lib.ptr(d_xyz),
-                                     _lib.ptr(d_rot), _lib.ptr(d_scale), _lib.ptr(ws), ws.numel(), _dev_index(dev),
-                                     _stream(dev)), "trase_mlp_forward")
+    _lib.check(forward(C.byref(w), _lib.ptr(xs), C.c_void_p(tt.data_ptr()), t_stride, n, _lib.ptr(d_xyz),
+                       _lib.ptr(d_rot), _lib.ptr(d_scale), _lib.ptr(ws), ws.numel(), _dev_index(dev),
+                       _stream(dev)), name)
     return d_xyz, d_rot, d_scale
 
 
@@ -310,11 +335,14 @@ class DeformNetworkHIP(torch.nn.Module):
     """Wraps a reference-shaped ``DeformNetwork`` (anything whose parameters carry the reference's names) and
     evaluates ``forward(x, t)`` with the fused kernels, with or without gradients."""
 
-    def __init__(self, net: torch.nn.Module):
+    def __init__(self, net: torch.nn.Module, precision: str = "bf16"):
         super().__init__()
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
         self.net = net
+        self.precision = precision
 
     def forward(self, x, t):
         params = dict(self.net.named_parameters())
         return deform_forward(params, x, t, is_blender=bool(getattr(self.net, "is_blender", False)),
-                              is_6dof=bool(getattr(self.net, "is_6dof", False)))
+                              is_6dof=bool(getattr(self.net, "is_6dof", False)), precision=self.precision)
