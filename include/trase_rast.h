@@ -192,6 +192,9 @@ int trase_rast_status(const TraseRastWorkspace* ws, int64_t status[3], trase_str
  * depth, the blend-order key), off[4] tiles u32[P], off[5] clamp bits u32[P].  Introspection for parity tests and
  * debugging -- the counterpart of reading the reference's geomBuffer; entries of culled Gaussians are undefined. */
 int trase_rast_geom_layout(int32_t P, int64_t off[6]);
+/* Byte offset, inside the geom workspace, of the (P, 16)-word geometry records ({x, y, first pair slot, radius}, conic + opacity,
+ * colour + depth, ...): introspection for the tests (word 2 is the first emit-order slot of the Gaussian's pairs). */
+int trase_rast_geom_record_offset(int32_t P, int64_t* off);
 
 /* The same for the bin workspace of `capacity` pairs and T 8x8 sub-tiles: off[0] point_list u32[capacity], off[1] pair_slot
  * u32[capacity], off[2] ranges uint2[T + 1] ([begin, end) of every sub-tile's list, row-major over the sub-tile grid, then
@@ -531,6 +534,22 @@ int trase_selftest_tile_ranges(const uint32_t* keys, uint32_t n, uint32_t cap, i
                                uint32_t* dbg, int32_t device, trase_stream_t stream);
 /* trase_selftest_zero_bytes: launch_zero_bytes(p, bytes) on the caller's device pointer, any alignment. */
 int trase_selftest_zero_bytes(void* p, size_t bytes, int32_t device, trase_stream_t stream);
+
+/* trase_selftest_compact_live: launch_compact_live over P Gaussians in a geom + pre workspace carved by the library's own layouts
+ * and filled with 0xCD.  tiles / keys: P device words each (pairs per Gaussian, depth keys).  keys_out / ids_out / live_ids_out (P
+ * device words each) receive the WHOLE arrays: what the kernels did not write still reads 0xCDCDCDCD.  hdr_out (5 host words) =
+ * {HDR_R, HDR_OVERFLOW, HDR_R_EFF, HDR_PACK, the length word}. */
+int trase_selftest_compact_live(const uint32_t* tiles, const uint32_t* keys, int32_t P, uint32_t* keys_out, uint32_t* ids_out,
+                                uint32_t* live_ids_out, uint32_t* hdr_out, int32_t device, trase_stream_t stream);
+/* trase_selftest_scan_tiles: launch_scan_tiles in the same poisoned workspace.  tiles, ids (Gaussian ids in depth-rank order, each
+ * < P), radii: P device words each; xy: P device float pairs; n_live: the length word (depth ranks that exist); cap, pack_bits, gx,
+ * gy (16x16 tiles) as the library passes them; overflow_in: the overflow word before the scan.  offsets_out (P device words) =
+ * the block-local inclusive sums, 0xCDCDCDCD behind n_live; block_sums_out (ceil(P / 1024) device words) = every block's
+ * exclusive prefix; hdr_out as above. */
+int trase_selftest_scan_tiles(const uint32_t* tiles, const uint32_t* ids, const int32_t* radii, const float* xy, int32_t P,
+                              uint32_t n_live, uint32_t cap, int32_t pack_bits, int32_t gx, int32_t gy, uint32_t overflow_in,
+                              uint32_t* offsets_out, uint32_t* block_sums_out, uint32_t* hdr_out, int32_t device,
+                              trase_stream_t stream);
 
 const char* trase_last_error(void);
 const char* trase_version(void);

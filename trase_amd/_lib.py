@@ -137,6 +137,7 @@ SYMBOLS = [
                                         C.POINTER(RastWorkspace), C.c_void_p]),
     ("trase_rast_status", C.c_int, [C.POINTER(RastWorkspace), C.POINTER(C.c_int64 * 3), C.c_void_p]),
     ("trase_rast_geom_layout", C.c_int, [C.c_int32, C.POINTER(C.c_int64 * 6)]),
+    ("trase_rast_geom_record_offset", C.c_int, [C.c_int32, C.POINTER(C.c_int64)]),
     ("trase_rast_bin_layout", C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64 * 3)]),
     ("trase_rast_render", C.c_int, [C.POINTER(RastSettings), C.POINTER(RastInputs), C.POINTER(RastOutputs),
                                     C.POINTER(RastWorkspace), C.c_void_p]),
@@ -312,6 +313,11 @@ SYMBOLS = [
     ("trase_selftest_tile_ranges", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p,
                                              C.POINTER(C.c_uint32 * 3), C.c_int32, C.c_void_p]),
     ("trase_selftest_zero_bytes", C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_selftest_compact_live", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_uint32 * 5), C.c_int32, C.c_void_p]),
+    ("trase_selftest_scan_tiles", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32,
+                                            C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_uint32 * 5), C.c_int32, C.c_void_p]),
     ("trase_last_error", C.c_char_p, []),
     ("trase_version", C.c_char_p, []),
 ]

@@ -57,7 +57,7 @@ ProfScope::~ProfScope() {
 }
 
 // ---- workspace layouts (one walk per workspace, common.h WsCursor; ws == nullptr measures) -----------------
-static size_t geom_layout(void* ws, int P, GeomBuf& g) {
+size_t geom_layout(void* ws, int P, GeomBuf& g) {
   const size_t p = (size_t)P;
   WsCursor w(ws);
   g.hdr = w.take<uint32_t>(HDR_WORDS);
@@ -83,7 +83,7 @@ static size_t img_layout(void* ws, int W, int H, ImgBuf& im) {
   im.n_contrib = w.take<uint32_t>((size_t)W * H);
   return w.bytes();
 }
-static size_t pre_layout(void* ws, int P, PreBuf& t) {
+size_t pre_layout(void* ws, int P, PreBuf& t) {
   const size_t p = (size_t)(P > 0 ? P : 1), partials = p / 1024 + 2;
   WsCursor w(ws);
   sort_layout(w, t.sort, p, SORT_KEYS | SORT_VALS);
@@ -445,6 +445,15 @@ int trase_rast_geom_layout(int32_t P, int64_t off[6]) {
   geom_layout((void*)base, P, g);
   const void* const field[6] = {g.hdr, g.xy, g.conic_o, g.rgbd, g.tiles, g.clamped};
   for (int i = 0; i < 6; ++i) off[i] = (int64_t)((uintptr_t)field[i] - base);
+  return TRASE_OK;
+}
+
+int trase_rast_geom_record_offset(int32_t P, int64_t* off) {
+  if (P < 0 || !off) { set_error("trase_rast_geom_record_offset: bad arguments"); return TRASE_ERR_INVALID; }
+  const uintptr_t base = 256;      // as above
+  GeomBuf g;
+  geom_layout((void*)base, P, g);
+  *off = (int64_t)((uintptr_t)g.geo - base);
   return TRASE_OK;
 }
 

@@ -399,6 +399,9 @@ struct PreBuf {            // stage-1 scratch (P-sized), read again by stage 2
   uint32_t* live_ids;      // (P) tile-row strips: the ids of the Gaussians with a pair in the strip, ASCENDING (the sorted list in
                            // sort.vals[0] visits memory in depth order: scattered rows; this one walks it monotonically)
 };
+// the layouts of the geom and the pre workspace (api.hip), also carved by the scan's and the compaction's test entry points
+size_t geom_layout(void* ws, int P, GeomBuf& g);
+size_t pre_layout(void* ws, int P, PreBuf& t);
 struct PairBuf {           // stage-2 scratch (capacity-sized)
   SortBufs sort;           // vals[] = {spare, bin.pair_slot} arranged by the caller
   uint32_t* spare_vals;

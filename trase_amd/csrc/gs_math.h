@@ -301,7 +301,10 @@ TRASE_HD void subtile_row_live(const SubtileCull& s, int sy, int W, int H, int s
   if (s.dy_xmax >= da && s.dy_xmax <= db) hi = s.xmax;       // rightmost point of the ellipse inside the band
   if (-s.dy_xmax >= da && -s.dy_xmax <= db) lo = -s.xmax;    // leftmost point inside the band
   const float xr = s.gx + hi + pad, xl = s.gx + lo - pad;
-  // block sx holds the pixel centres 8 sx .. 8 sx + 7: it meets [xl, xr] iff 8 sx <= xr and 8 sx + 7 >= xl
+  // block sx holds the pixel centres 8 sx .. min(8 sx + 7, W - 1): it meets [xl, xr] iff 8 sx <= xr and that last centre >= xl.
+  // Only the last column of an image whose width is no multiple of 8 is narrower, and it is the rightmost: an interval that
+  // begins right of the last pixel centre meets no block at all (it used to keep that column for pixels that do not exist)
+  if (xl > (float)(W - 1)) { c1 = c0; return; }
   const float f1 = floorf(xr * (1.0f / (float)SUB));
   const float f0 = ceilf((xl - (float)(SUB - 1)) * (1.0f / (float)SUB));
   // clamp in float first: the products can exceed the int range for degenerate splats

@@ -200,3 +200,85 @@ extern "C" int trase_selftest_zero_bytes(void* p, size_t bytes, int32_t device, 
   TRASE_CHECK(hipStreamSynchronize(stream));
   return TRASE_OK;
 }
+
+// ---- test entry points of the live compaction and the tile scan (binning.hip) ---------------------------------------------------
+namespace {
+// the geom and the pre workspace of P Gaussians in one allocation, carved by the library's own walks
+struct ScanWs {
+  GeomBuf g{};
+  PreBuf t{};
+  size_t geom_b = 0, bytes = 0;
+  void carve(void* base, int P) {
+    geom_b = geom_layout(base, P, g);
+    bytes = geom_b + pre_layout(base ? (void*)((uintptr_t)base + geom_b) : nullptr, P, t);
+  }
+};
+int copy_header(const uint32_t* hdr, uint32_t* out5, hipStream_t stream) {
+  uint32_t h[HDR_WORDS];
+  TRASE_CHECK(hipMemcpyAsync(h, hdr, sizeof(h), hipMemcpyDeviceToHost, stream));
+  TRASE_CHECK(hipStreamSynchronize(stream));
+  out5[0] = h[HDR_R]; out5[1] = h[HDR_OVERFLOW]; out5[2] = h[HDR_R_EFF]; out5[3] = h[HDR_PACK]; out5[4] = h[HDR_WORDS - 1];
+  return TRASE_OK;
+}
+}  // namespace
+
+extern "C" int trase_selftest_compact_live(const uint32_t* tiles, const uint32_t* keys, int32_t P, uint32_t* keys_out,
+                                           uint32_t* ids_out, uint32_t* live_ids_out, uint32_t* hdr_out, int32_t device,
+                                           trase_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!tiles || !keys || !keys_out || !ids_out || !live_ids_out || !hdr_out || P < 1) {
+    set_error("trase_selftest_compact_live: bad arguments");
+    return TRASE_ERR_INVALID;
+  }
+  TRASE_CHECK(hipSetDevice(device));
+  ScanWs w;
+  w.carve(nullptr, P);
+  DevBlock blk;
+  TRASE_CHECK(hipMalloc(&blk.p, w.bytes));
+  w.carve(blk.p, P);
+  // everything starts as garbage: the block counts, the header, the three result arrays
+  TRASE_CHECK(hipMemsetAsync(blk.p, 0xCD, w.bytes, stream));
+  const size_t pb = sizeof(uint32_t) * (size_t)P;
+  TRASE_CHECK(hipMemcpyAsync(w.g.tiles, tiles, pb, hipMemcpyDeviceToDevice, stream));
+  TRASE_CHECK(hipMemcpyAsync(w.t.sort.keys[1], keys, pb, hipMemcpyDeviceToDevice, stream));
+  const LaunchCtx c{stream, 0, 0};
+  const int rc = launch_compact_live(c, w.g, P, w.t, w.t.sort.keys[1], w.t.sort.keys[0], w.t.sort.vals[0]);
+  if (rc != TRASE_OK) { hipStreamSynchronize(stream); return rc; }
+  TRASE_CHECK(hipMemcpyAsync(keys_out, w.t.sort.keys[0], pb, hipMemcpyDeviceToDevice, stream));
+  TRASE_CHECK(hipMemcpyAsync(ids_out, w.t.sort.vals[0], pb, hipMemcpyDeviceToDevice, stream));
+  TRASE_CHECK(hipMemcpyAsync(live_ids_out, w.t.live_ids, pb, hipMemcpyDeviceToDevice, stream));
+  return copy_header(w.g.hdr, hdr_out, stream);
+}
+
+extern "C" int trase_selftest_scan_tiles(const uint32_t* tiles, const uint32_t* ids, const int32_t* radii, const float* xy,
+                                         int32_t P, uint32_t n_live, uint32_t cap, int32_t pack_bits, int32_t gx, int32_t gy,
+                                         uint32_t overflow_in, uint32_t* offsets_out, uint32_t* block_sums_out,
+                                         uint32_t* hdr_out, int32_t device, trase_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!tiles || !ids || !radii || !xy || !offsets_out || !block_sums_out || !hdr_out || P < 1 || pack_bits < 0 || pack_bits > 31 ||
+      gx < 1 || gy < 1) {
+    set_error("trase_selftest_scan_tiles: bad arguments");
+    return TRASE_ERR_INVALID;
+  }
+  TRASE_CHECK(hipSetDevice(device));
+  ScanWs w;
+  w.carve(nullptr, P);
+  DevBlock blk;
+  TRASE_CHECK(hipMalloc(&blk.p, w.bytes));
+  w.carve(blk.p, P);
+  TRASE_CHECK(hipMemsetAsync(blk.p, 0xCD, w.bytes, stream));
+  const size_t pb = sizeof(uint32_t) * (size_t)P;
+  TRASE_CHECK(hipMemcpyAsync(w.g.tiles, tiles, pb, hipMemcpyDeviceToDevice, stream));
+  TRASE_CHECK(hipMemcpyAsync(w.t.sort.vals[0], ids, pb, hipMemcpyDeviceToDevice, stream));
+  TRASE_CHECK(hipMemcpyAsync(w.g.xy, xy, 2 * sizeof(float) * (size_t)P, hipMemcpyDeviceToDevice, stream));
+  // the two header words the scan reads: the length (depth ranks that exist) and the overflow word, whose bit 1 it must keep
+  TRASE_CHECK(hipMemcpyAsync(w.g.hdr + (HDR_WORDS - 1), &n_live, sizeof(n_live), hipMemcpyHostToDevice, stream));
+  TRASE_CHECK(hipMemcpyAsync(w.g.hdr + HDR_OVERFLOW, &overflow_in, sizeof(overflow_in), hipMemcpyHostToDevice, stream));
+  const LaunchCtx c{stream, 0, 0};
+  const int rc = launch_scan_tiles(c, w.g, w.t.sort.vals[0], P, w.t, cap, radii, gx, gy, pack_bits);
+  if (rc != TRASE_OK) { hipStreamSynchronize(stream); return rc; }
+  const int nblocks = (P + 1023) / 1024;
+  TRASE_CHECK(hipMemcpyAsync(offsets_out, w.t.offsets, pb, hipMemcpyDeviceToDevice, stream));
+  TRASE_CHECK(hipMemcpyAsync(block_sums_out, w.t.block_sums, sizeof(uint32_t) * (size_t)nblocks, hipMemcpyDeviceToDevice, stream));
+  return copy_header(w.g.hdr, hdr_out, stream);
+}

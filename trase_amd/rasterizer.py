@@ -834,3 +834,88 @@ def selftest_zero_bytes(buf, offset, nbytes):
     d = dev.index if dev.index is not None else torch.cuda.current_device()
     _lib.check(_lib.load().trase_selftest_zero_bytes(C.c_void_p(buf.data_ptr() + offset), int(nbytes), d, _stream(dev)),
                "trase_selftest_zero_bytes")
+
+
+def _hdr5(res) -> dict:
+    return {"R": int(res[0]), "overflow": int(res[1]), "R_eff": int(res[2]), "pack": int(res[3]), "length": int(res[4])}
+
+
+def selftest_compact_live(tiles, keys):
+    """launch_compact_live over P Gaussians (test entry point) in a workspace filled with 0xCD.  tiles, keys: int32 device
+    tensors of P words (uint32 bit patterns).  Returns (keys_out, ids_out, live_ids, header): the WHOLE P-word arrays -- what no
+    kernel wrote still reads 0xCDCDCDCD -- and the header words {R, overflow, R_eff, pack, length}."""
+    for t in (tiles, keys):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.shape == tiles.shape and t.dim() == 1
+    dev = tiles.device
+    d = dev.index if dev.index is not None else torch.cuda.current_device()
+    outs = [torch.empty_like(tiles) for _ in range(3)]
+    res = (C.c_uint32 * 5)()
+    _lib.check(_lib.load().trase_selftest_compact_live(_lib.ptr(tiles), _lib.ptr(keys), tiles.numel(), _lib.ptr(outs[0]),
+                                                       _lib.ptr(outs[1]), _lib.ptr(outs[2]), C.byref(res), d, _stream(dev)),
+               "trase_selftest_compact_live")
+    return outs[0], outs[1], outs[2], _hdr5(res)
+
+
+def selftest_scan_tiles(tiles, ids, radii, xy, n_live, cap, pack_bits, gx, gy, overflow_in=0):
+    """launch_scan_tiles (test entry point) in a workspace filled with 0xCD.  tiles, ids, radii: int32 device tensors of P words
+    (ids: Gaussian ids in depth-rank order, each < P); xy: (P, 2) float32; n_live: the length word; gx, gy: 16x16 tiles.
+    Returns (offsets, block_sums, header): the P block-local inclusive sums (0xCDCDCDCD behind n_live), every block's exclusive
+    prefix (ceil(P / 1024) words) and the header words {R, overflow, R_eff, pack, length}."""
+    P = tiles.numel()
+    for t in (tiles, ids, radii):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.shape == (P,)
+    assert xy.is_cuda and xy.dtype == torch.float32 and xy.is_contiguous() and xy.shape == (P, 2)
+    assert P >= 1 and 0 <= int(ids.min()) and int(ids.max()) < P, "an id outside [0, P) would be read out of bounds"
+    dev = tiles.device
+    d = dev.index if dev.index is not None else torch.cuda.current_device()
+    offsets = torch.empty_like(tiles)
+    sums = torch.empty((P + 1023) // 1024, dtype=torch.int32, device=dev)
+    res = (C.c_uint32 * 5)()
+    _lib.check(_lib.load().trase_selftest_scan_tiles(
+        _lib.ptr(tiles), _lib.ptr(ids), _lib.ptr(radii), _lib.ptr(xy), P, int(n_live), int(cap), int(pack_bits), int(gx), int(gy),
+        int(overflow_in), _lib.ptr(offsets), _lib.ptr(sums), C.byref(res), d, _stream(dev)), "trase_selftest_scan_tiles")
+    return offsets, sums, _hdr5(res)
+
+
+def last_sub_tile_lists(P: int) -> dict:
+    """The finished per-sub-tile lists of the most recent forward (introspection for the tests, beside last_tile_row_loads;
+    synchronises).  CPU int64 tensors:
+    ranges  (T + 1, 2)  [start, end) of every 8x8 sub-tile, row-major, and of the sentinel sub-tile T
+    ids     (n,)        the Gaussian id at every list position, n = min(R_eff, capacity): the packed list value >> jb, or -- slot
+                        lists -- the owner of the emit-order slot the list holds, through the first slot emit_pairs recorded in
+                        every Gaussian's geometry record and tiles[id] (the id array itself is no complete record: the forward
+                        fills it chunk by chunk and stops where a sub-tile's pixels are all saturated)
+    index   (n,)        packed lists: the index of the pair among its Gaussian's own pairs; None for slot lists
+    header  dict        R, overflow, R_eff, pack (jb; 0 = slot lists), capacity, length (depth ranks that exist)"""
+    if _Policy.last_bin is None or _Policy.last_hw is None or _Policy.last_geom is None:
+        raise RuntimeError("no forward has run yet")
+    H, W = _Policy.last_hw
+    T = ((W + 7) // 8) * ((H + 7) // 8)
+    off = (C.c_int64 * 3)()              # point_list | pair_slot | ranges
+    _lib.check(_lib.load().trase_rast_bin_layout(int(_Policy.last_capacity), T, C.byref(off)), "trase_rast_bin_layout")
+    torch.cuda.synchronize(_Policy.last_bin.device)
+    h = (_Policy.last_geom[:256].view(torch.int32).cpu().to(torch.int64) & 0xffffffff).tolist()
+    header = {"R": h[0], "overflow": h[1], "R_eff": h[2], "pack": h[3], "capacity": h[62], "length": h[63]}
+    if P == 0:      # an empty scene: stage 2 clears the ranges and emits nothing
+        header["capacity"] = int(_Policy.last_capacity)
+    n = min(header["R_eff"], int(_Policy.last_capacity))
+
+    def words(o, count):
+        return _Policy.last_bin[o:o + 4 * count].view(torch.int32).cpu().to(torch.int64) & 0xffffffff
+    ranges = words(off[2], 2 * (T + 1)).reshape(T + 1, 2)
+    vals = words(off[1], n)
+    jb = header["pack"]
+    if jb:
+        return {"ranges": ranges, "ids": vals >> jb, "index": vals & ((1 << jb) - 1), "header": header}
+    # slot lists: Gaussian id owns the slots [first, first + tiles[id]); `first` is word 2 of its 64-byte geometry record
+    roff = C.c_int64()
+    _lib.check(_lib.load().trase_rast_geom_record_offset(int(P), C.byref(roff)), "trase_rast_geom_record_offset")
+    rec = int(roff.value)
+    first = _Policy.last_geom[rec:rec + 64 * P].view(torch.int32).reshape(P, 16)[:, 2].cpu().to(torch.int64) & 0xffffffff
+    tiles = geom_view(_Policy.last_geom, P)["tiles"].cpu().to(torch.int64) & 0xffffffff
+    owners = torch.nonzero(tiles > 0).reshape(-1)
+    owners = owners[torch.argsort(first[owners], stable=True)]
+    k = torch.searchsorted(first[owners].contiguous(), vals, right=True) - 1
+    if n and (int(k.min()) < 0 or bool((vals >= (first + tiles)[owners][k]).any())):
+        raise RuntimeError("last_sub_tile_lists: a list holds a slot that no Gaussian owns")
+    return {"ranges": ranges, "ids": owners[k] if n else vals, "index": None, "header": header}
