@@ -106,7 +106,8 @@ typedef enum TraseVariant {
                                               * row written, zeros included) */
   /* -- diagnostics: compiled only into `make AB=1` builds of the library (-DTRASE_AB), ignored otherwise -- */
   TRASE_VARIANT_AB_TIMING = 0x1000,          /* phase cycle counters of the MFMA backward (geom header words 32..39) */
-  TRASE_VARIANT_AB_COUNT = 0x8000,           /* lane-utilisation counters of the MFMA backward (header words 40..47) */
+  TRASE_VARIANT_AB_COUNT = 0x8000,           /* lane-utilisation counters of the MFMA backward (header words 40..47) and K-step
+                                              * counters of the MFMA forward (header words 48..49) */
   TRASE_VARIANT_AB_ORDER_IMAGE = 0x40000,    /* compositing kernels visit the sub-tiles in image order ... */
   TRASE_VARIANT_AB_ORDER_8 = 0x80000         /* ... in 8x8 blocks (default: 16x16 blocks) */
 } TraseVariant;

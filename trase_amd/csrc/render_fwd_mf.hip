@@ -12,7 +12,10 @@
 // running product P_u = prod_{v<=u} (1 - alpha_v) of its eight entries, the two halves exchange their totals with one
 // v_permlane32_swap, and w_u = (P_{u-1} - P_u) * T_in.  The stop rule (T (1 - alpha) < 1e-4: the pixel is finished and
 // this entry is NOT blended) is a monotone threshold on those products; only a step in which some pixel of the wave
-// crosses it takes the masked path.
+// crosses it takes the masked path.  A wave leaves the K-step loop of a chunk at the first step it enters with no live
+// pixel (wave-uniform test on Tin): such a step has all-zero weights, adds +0 to every accumulator and touches neither
+// final_T nor n_contrib, so nothing but the work is dropped; the wave still stages its half of the following chunks for
+// the other wave until that one is finished too.
 //   * why two waves per sub-tile: the accumulators of 64 pixels x 64 channel columns are 64 registers; with 32 pixels
 //     per wave the kernel needs ~100 VGPRs instead of ~150 and twice as many waves are resident to cover the dependent
 //     load chain slot -> id -> geometry / feature rows at every chunk start (PMC: the one-wave version spent 52 % of its
@@ -45,6 +48,11 @@ constexpr int FM_WAVES = 2;       // waves per sub-tile (= workgroup)
 #define FM_G_ 64
 #endif
 constexpr int FM_G = FM_G_;       // list entries per chunk
+#ifndef FM_KSTEP_EXIT_
+#define FM_KSTEP_EXIT_ 1
+#endif
+constexpr bool FM_KSTEP_EXIT = FM_KSTEP_EXIT_ != 0;   // leave a chunk's K-step loop once the wave has no live pixel (0: the A/B baseline,
+                                                      // which tests that once per chunk only)
 constexpr int FM_P = 48;          // tile row pitch in bf16: 32 features, r g b depth, 12 zeros (96 B: the transposing reads
                                   // of a 16-lane group -- 4 rows x 4 eight-byte chunks -- then fall on 16 different bank pairs)
 
@@ -73,6 +81,9 @@ struct FwdMfArgs {
   int order_mode;        // 0: image order; 8 / 16: blocks of 8x8 / 16x16 sub-tiles (common.h blocked_tile)
   int lineage;           // variant bits TRASE_VARIANT_FEATS_BG / TRASE_VARIANT_DEPTH_NORM (0 = public lineage)
   float feat_bg;
+#ifdef TRASE_AB
+  uint32_t* prof;        // header words 48..49: K-step counters of the COUNT build
+#endif
 };
 
 typedef float f2v __attribute__((ext_vector_type(2)));
@@ -105,8 +116,11 @@ __device__ __forceinline__ bf16x8 frag_tr(const __bf16* __restrict__ p) {
   return __builtin_bit_cast(bf16x8, r);
 }
 
-__global__ __launch_bounds__(FM_WAVES* WAVE) __attribute__((amdgpu_waves_per_eu(5, 5)))
-void render_fwd_mf_kernel(FwdMfArgs a) {
+// COUNT (TRASE_VARIANT_AB_COUNT, `make AB=1` builds only): K-steps of the launch, a K-step being a loop iteration that reaches
+// the MFMAs.  Header words, summed over all waves:
+//   48 K-steps executed      49 ... of those, K-steps the wave entered with a live pixel
+template <bool COUNT>
+__device__ __forceinline__ void render_fwd_mf_body(const FwdMfArgs& a) {
   constexpr int F = 32;
   __shared__ __attribute__((aligned(16))) FmLds L;
   const int wv = threadIdx.x >> 6;                       // pixel block of this wave: rows 4 wv .. 4 wv + 3
@@ -142,6 +156,7 @@ void render_fwd_mf_kernel(FwdMfArgs a) {
   // finished; Tc = the value final_T reports; lastc = n_contrib
   float Tin = inside ? 1.0f : 0.0f, Tc = 1.0f;
   uint32_t lastc = 0;
+  uint32_t cnt[2] = {0u, 0u};                            // COUNT only
   float dacc = 0.f;                                      // fp32 depth of this lane's half of every K-step
   // this lane's chunk address in the transposing B-fragment reads: entry (lane & 15) >> 2 of the four, channel chunk
   // 16 * ((lane >> 4) & 1) + 4 * (lane & 3) of the block (block 1 = channels 32..47: r g b depth and zeros)
@@ -214,10 +229,14 @@ void render_fwd_mf_kernel(FwdMfArgs a) {
     }
     wg_lds_barrier();
     // ---- K-steps of 16 entries ---------------------------------------------------------------------------------
-    if (__any(Tin > 0.0f)) {
+    if (FM_KSTEP_EXIT || __any(Tin > 0.0f)) {
 #pragma unroll 1
       for (int t = 0; t < FM_G / 16; ++t) {
         if ((uint32_t)(16 * t) >= n) break;
+        // every pixel of the wave is finished: the remaining steps of the chunk would blend zeros
+        const bool wave_live = (FM_KSTEP_EXIT || COUNT) ? __any(Tin > 0.0f) : true;
+        if (FM_KSTEP_EXIT && !wave_live) break;
+        if constexpr (COUNT) { cnt[0] += 1; cnt[1] += wave_live ? 1u : 0u; }
         const int e0 = 16 * t + 8 * h;                   // this lane's eight entries
         float Pu[8];
         float P = 1.0f;
@@ -314,6 +333,11 @@ void render_fwd_mf_kernel(FwdMfArgs a) {
     wg_lds_barrier();                                    // the tile may be overwritten; both waves see both flags
   }
 
+#ifdef TRASE_AB
+  if constexpr (COUNT) {
+    if (lane == 0 && a.prof) { atomicAdd(a.prof, cnt[0]); atomicAdd(a.prof + 1, cnt[1]); }
+  }
+#endif
   // ---- outputs -----------------------------------------------------------------------------------------------
   const size_t hw = (size_t)a.H * a.W;
   const int x0 = tx * SUB, y0 = ty * SUB;
@@ -370,6 +394,13 @@ void render_fwd_mf_kernel(FwdMfArgs a) {
   }
 }
 
+__global__ __launch_bounds__(FM_WAVES* WAVE) __attribute__((amdgpu_waves_per_eu(5, 5)))
+void render_fwd_mf_kernel(FwdMfArgs a) { render_fwd_mf_body<false>(a); }
+#ifdef TRASE_AB
+__global__ __launch_bounds__(FM_WAVES* WAVE) __attribute__((amdgpu_waves_per_eu(5, 5)))
+void render_fwd_mf_count_kernel(FwdMfArgs a) { render_fwd_mf_body<true>(a); }
+#endif
+
 int launch_render_fwd_mf(const LaunchCtx& c, const TraseRastSettings& s, const TraseRastInputs& in, const TraseRastOutputs& out,
                          const GeomBuf& g, const BinBuf& b, const ImgBuf& im, const uint32_t* pair_gauss, uint32_t cap) {
   FwdMfArgs a;
@@ -390,6 +421,11 @@ int launch_render_fwd_mf(const LaunchCtx& c, const TraseRastSettings& s, const T
   if (a.ntiles <= 0) return TRASE_OK;                    // an empty strip
   {
     ProfScope ps("render_fwd", c.stream);
+#ifdef TRASE_AB                                          // diagnostic instantiation: `make AB=1`
+    a.prof = g.hdr + 48;
+    if (c.variant & TRASE_VARIANT_AB_COUNT) hipLaunchKernelGGL(render_fwd_mf_count_kernel, dim3(a.ntiles), dim3(FM_WAVES * WAVE), 0, c.stream, a);
+    else
+#endif
     hipLaunchKernelGGL(render_fwd_mf_kernel, dim3(a.ntiles), dim3(FM_WAVES * WAVE), 0, c.stream, a);
   }
   TRASE_POST_LAUNCH("render_fwd", c.stream, c.debug);
