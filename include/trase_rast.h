@@ -690,6 +690,43 @@ int trase_pack_masks(const uint8_t* sam_masks, int32_t N, int64_t HW, uint8_t* b
 int trase_unpack_masks(const uint8_t* bits, size_t bits_bytes, int32_t N, int64_t HW, uint8_t* sam_masks, int32_t device,
                        trase_stream_t stream);
 
+/* ---- ground truth as bytes: the planar 8-bit frame and the photometric heads that read it --------------------------------------
+ * A ground-truth frame of the reference is always the image of a byte array (PILtoTorch, utils/general_utils.py:22-28: every
+ * pixel is float32(b) / float32(255)).  The frame: `planes`, 16-byte aligned, 3 planes (r, g, b) of H rows, `pitch` bytes from
+ * row to row, pitch = the smallest multiple of 16 >= W; 3 * H * pitch bytes.  No consumer reads a byte of the row padding or
+ * anything at or past 3 * H * pitch.  Every refusal is TRASE_ERR_INVALID (a workspace that is too small:
+ * TRASE_ERR_WORKSPACE) with a message, before a device is touched: null pointers, H or W < 1, channels other than 3 or 4, a
+ * background with 3 channels, a pitch that is no multiple of 16 or below W, planes that are not 16-byte aligned.
+ * trase_frame_pack: hwc = (H, W, channels) bytes on the device, what np.array(pil_image) is -> the planes, padding written as 0;
+ *   a fourth channel is dropped (utils/camera_utils.py:51).  background (three HOST floats, or null): with 4 channels the
+ *   composite of train.py:221-228 per channel, byte = trunc(((v / 255.0) * (a / 255.0) + bg * (1 - a / 255.0)) * 255.0) in float64,
+ *   every operation rounded on its own, the fp32 background promoted to double, the result taken modulo 256 as numpy's
+ *   conversion to np.byte does.
+ * trase_frame_unpack: the planes -> (3, H, W) fp32, each value the true fp32 quotient b / 255: bit for bit the reference's
+ *   original_image.
+ * trase_frame_black_mask: mask (h, w) bytes of 0 / 1.  h == H and w == W: 1 where r | g | b == 0 (train.py:232).  Otherwise
+ *   train.py:267-268: 1 where the frame resized to (h, w) (bilinear, align_corners = False) sums to 0 over the channels, i.e.
+ *   where every tap of non-zero weight is 0 in all three planes (all terms are non-negative); integer logic only.
+ * trase_loss_*_u8: the four loss entry points above with the planes in place of gt (C = 3; same workspace, same kernels' bodies,
+ *   same reduction: the outputs are bitwise those of the float entry points on trase_frame_unpack's tensor).  flags:
+ *   TRASE_FRAME_MASK_BLACK fuses train.py:231-234 -- where the frame's pixel is black the rendered value counts as 0 (also in
+ *   the window's halo) and receives gradient 0; a non-finite rendered value there is ignored (the reference's image * 0 is NaN). */
+#define TRASE_FRAME_MASK_BLACK 1u
+int trase_frame_pack(const uint8_t* hwc, int32_t H, int32_t W, int32_t channels, const float* background, uint8_t* planes, int32_t pitch,
+                     int32_t device, trase_stream_t stream);
+int trase_frame_unpack(const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, float* chw, int32_t device, trase_stream_t stream);
+int trase_frame_black_mask(const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, int32_t h, int32_t w, uint8_t* mask, int32_t device,
+                           trase_stream_t stream);
+int trase_loss_l1_ssim_forward_u8(const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags, float* out2,
+                                  void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+int trase_loss_l1_ssim_backward_u8(const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags,
+                                   const float* g2, const void* ws, size_t ws_bytes, float* dL_dimg, int32_t device, trase_stream_t stream);
+int trase_loss_photometric_forward_u8(const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags,
+                                      double lambda_dssim, float* out3, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+int trase_loss_photometric_backward_u8(const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags,
+                                       double lambda_dssim, const float* g, const void* ws, size_t ws_bytes, float* dL_dimg, int32_t device,
+                                       trase_stream_t stream);
+
 /* ---- segmentation after training: K-means and query masks (gui.py:248-270, render.py:97-105 + :334-345) ------------------
  * trase_kmeans_steps: n_steps Lloyd steps of kmeans_pytorch.kmeans(X, K, distance='euclidean') (gui.py:248-270,
  *   gui_standalone.py:685-707; 0.3's loop, see trase_amd/segment.py), entirely on the device.  X (N,D) fp32, centres_inout

@@ -255,6 +255,19 @@ SYMBOLS = [
                                                       C.c_size_t, C.c_int32, C.c_void_p]),
     ("trase_pack_masks", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     ("trase_unpack_masks", C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_frame_pack", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float * 3), C.c_void_p, C.c_int32, C.c_int32,
+                                   C.c_void_p]),
+    ("trase_frame_unpack", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_frame_black_mask", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                         C.c_void_p]),
+    ("trase_loss_l1_ssim_forward_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_loss_l1_ssim_backward_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                 C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_loss_photometric_forward_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_double,
+                                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    ("trase_loss_photometric_backward_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_double,
+                                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p]),
     ("trase_nnfm_sizes", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     ("trase_nnfm_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_int32, C.c_void_p]),

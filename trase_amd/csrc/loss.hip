@@ -22,6 +22,32 @@ __device__ __forceinline__ float tile_load(const float* __restrict__ p, int H, i
   return (x >= 0 && x < W && y >= 0 && y < H) ? p[(size_t)y * W + x] : 0.f;    // conv2d zero padding
 }
 
+// Where the ground truth comes from.  The kernels below are ONE body per direction, instantiated per loader: GtFloat is the fp32
+// (C,H,W) tensor; GtBytes the planar 8-bit frame of trase_frame_pack (3 planes of H rows, `pitch` bytes apart), converted with the
+// true fp32 division the reference's `torch.from_numpy(bytes) / 255.0` performs (a multiplication by 1/255 is off by an ulp for
+// 126 of the 256 values) -- so both loaders hand the SAME floats to the SAME arithmetic, and the results are bitwise equal.
+// GtBytes<true> also fuses train.py:231-234 (mask_black_bg): where the frame's pixel is black in all three planes the rendered
+// value is taken as 0 (in the tile and in its halo) and its gradient is 0.
+struct GtFloat {
+  static constexpr bool MASK = false;
+  const float* gt;
+  __device__ __forceinline__ float at(int c, int H, int W, int y, int x) const { return gt[(size_t)c * H * W + (size_t)y * W + x]; }
+  __device__ __forceinline__ bool black(int, int, int) const { return false; }
+};
+template <bool MASK_>
+struct GtBytes {
+  static constexpr bool MASK = MASK_;
+  const uint8_t* planes;
+  int pitch;
+  __device__ __forceinline__ float at(int c, int H, int, int y, int x) const {
+    return (float)planes[((size_t)c * H + y) * pitch + x] / 255.0f;
+  }
+  __device__ __forceinline__ bool black(int H, int y, int x) const {
+    const size_t o = (size_t)y * pitch + x, pl = (size_t)H * pitch;
+    return (planes[o] | planes[pl + o] | planes[2 * pl + o]) == 0;
+  }
+};
+
 // Round 5: a thread owns FOUR consecutive outputs along the filtered direction and slides the window over the 14 inputs they
 // share -- 28 + 70 LDS reads per four pixels instead of 88 + 220 -- with every output's eleven fused multiply-adds in the same
 // order as before (k ascending).  Measured (profiles/r5_ab_experiments.txt): forward 0.075 -> 0.072 ms, backward unchanged at
@@ -29,7 +55,8 @@ __device__ __forceinline__ float tile_load(const float* __restrict__ p, int H, i
 // intermediate rows: the two row groups of a wave (4 rows apart) land 32 banks apart.
 constexpr int HP = 40;
 
-__global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__ img, const float* __restrict__ gt, int H, int W,
+template <class GT>
+__global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__ img, const GT gt, int H, int W,
                                                        LossWin win, float* __restrict__ dmaps /* [3][C][H][W] */,
                                                        float* __restrict__ partial /* [blocks][2] */) {
   __shared__ float sx[LH][LH + 1], sy[LH][LH + 1];
@@ -38,7 +65,6 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
   const int c = blockIdx.z;
   const size_t plane = (size_t)H * W;
   const float* X = img + c * plane;
-  const float* Y = gt + c * plane;
   const int x0 = blockIdx.x * LT, y0 = blockIdx.y * LT;
   {
     // the tile + halo in registers first: all of a thread's loads in flight at once (as a loop of load -> LDS store the
@@ -48,9 +74,11 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
       const int i = threadIdx.x + 256 * k, r = i / LH, q = i % LH;
-      const bool in = i < LH * LH;
-      vx[k] = in ? tile_load(X, H, W, y0 + r - LR, x0 + q - LR) : 0.f;
-      vy[k] = in ? tile_load(Y, H, W, y0 + r - LR, x0 + q - LR) : 0.f;
+      const int y = y0 + r - LR, x = x0 + q - LR;
+      const bool in = i < LH * LH && x >= 0 && x < W && y >= 0 && y < H;    // outside the image: conv2d zero padding
+      vx[k] = in ? X[(size_t)y * W + x] : 0.f;
+      vy[k] = in ? gt.at(c, H, W, y, x) : 0.f;
+      if (GT::MASK && in && gt.black(H, y, x)) vx[k] = 0.f;
     }
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
@@ -168,7 +196,8 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
   }
 }
 
-__global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__ img, const float* __restrict__ gt, int H, int W,
+template <class GT>
+__global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__ img, const GT gt, int H, int W,
                                                        LossWin win, const float* __restrict__ dmaps,
                                                        const float* __restrict__ g2 /* dL/dl1, dL/dssim */, float inv_count,
                                                        float* __restrict__ d_img, int g_stride, float s_l1, float s_ssim) {
@@ -245,10 +274,14 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
       const int y = y0 + r0 + j, x = x0 + q;
       if (y >= H || x >= W) continue;
       const size_t o = c * plane + (size_t)y * W + x;
-      const float xv = img[o], yv = gt[o];
+      if (GT::MASK && gt.black(H, y, x)) { d_img[o] = 0.f; continue; }      // the blend's factor (1 - black_mask)
+      const float xv = img[o], yv = gt.at(c, H, W, y, x);
       const float d = xv - yv;
       const float sgn = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);
-      d_img[o] = ws * (acc[j][0] + 2.f * xv * acc[j][1] + yv * acc[j][2]) + wl * sgn;
+      // ws * (acc0 + 2 x acc1 + y acc2) + wl * sgn with its roundings pinned (the sum of two products leaves the compiler a choice of
+      // which one to fuse, and it chose differently per loader): two fmas for the bracket, the product with ws rounded, then one fma
+      const float inner = fmaf(yv, acc[j][2], fmaf(2.f * xv, acc[j][1], acc[j][0]));
+      d_img[o] = fmaf(wl, sgn, ws * inner);
     }
   }
 }
@@ -278,18 +311,9 @@ static size_t loss_layout(void* ws, int C, int H, int W, LossWs& w) {
 
 using namespace trase;
 
-extern "C" {
-
-int trase_loss_sizes(int32_t C, int32_t H, int32_t W, size_t* ws_bytes) {
-  if (!ws_bytes || C < 1 || H < 1 || W < 1) { set_error("trase_loss_sizes: bad arguments"); return TRASE_ERR_INVALID; }
-  LossWs w;
-  *ws_bytes = loss_layout(nullptr, C, H, W, w);
-  return TRASE_OK;
-}
-
-static int loss_forward(const char* who, const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float* out2, double lambda_dssim,
-                        void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
-  if (!img || !gt || !out2 || C < 1 || H < 1 || W < 1) { set_error("%s: bad arguments", who); return TRASE_ERR_INVALID; }
+template <class GT>
+static int loss_forward_launch(const char* who, const float* img, const GT& gt, int32_t C, int32_t H, int32_t W, float* out2,
+                               double lambda_dssim, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
   LossWs w;
   if (!ws || ws_bytes < loss_layout(ws, C, H, W, w)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
@@ -297,7 +321,7 @@ static int loss_forward(const char* who, const float* img, const float* gt, int3
   const dim3 grid((W + LT - 1) / LT, (H + LT - 1) / LT, C);
   {
     ProfScope ps("ssim_fwd", stream);
-    hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(256), 0, stream, img, gt, H, W, make_window(), w.dmaps, w.partial);
+    hipLaunchKernelGGL(ssim_fwd_kernel<GT>, grid, dim3(256), 0, stream, img, gt, H, W, make_window(), w.dmaps, w.partial);
   }
   TRASE_POST_LAUNCH("ssim_fwd", stream, 0);
   {
@@ -306,6 +330,77 @@ static int loss_forward(const char* who, const float* img, const float* gt, int3
                        (float)lambda_dssim, (float)(1.0 - lambda_dssim));
   }
   TRASE_POST_LAUNCH("loss_reduce", stream, 0);
+  return TRASE_OK;
+}
+
+static int loss_forward(const char* who, const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float* out2, double lambda_dssim,
+                        void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  if (!img || !gt || !out2 || C < 1 || H < 1 || W < 1) { set_error("%s: bad arguments", who); return TRASE_ERR_INVALID; }
+  return loss_forward_launch(who, img, GtFloat{gt}, C, H, W, out2, lambda_dssim, ws, ws_bytes, device, stream_);
+}
+
+// what every *_u8 entry point refuses before a device is touched: the frame contract of trase_frame_pack
+static int frame_args_ok(const char* who, const void* img, const uint8_t* planes, const void* out, const void* ws, int32_t H, int32_t W, int32_t pitch) {
+  if (!img || !planes || !out || !ws) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  if (H < 1 || W < 1) { set_error("%s: need H, W >= 1 (got %d x %d)", who, H, W); return TRASE_ERR_INVALID; }
+  if (pitch < W || (pitch & 15) != 0) { set_error("%s: pitch must be a multiple of 16 and at least W (got pitch %d, W %d)", who, pitch, W); return TRASE_ERR_INVALID; }
+  if (((size_t)planes & 15) != 0) { set_error("%s: the planes must be 16-byte aligned", who); return TRASE_ERR_INVALID; }
+  return TRASE_OK;
+}
+
+static int loss_forward_u8(const char* who, const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags,
+                           float* out2, double lambda_dssim, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  if (int rc = frame_args_ok(who, img, planes, out2, ws, H, W, pitch)) return rc;
+  if (flags & ~(uint32_t)TRASE_FRAME_MASK_BLACK) { set_error("%s: unknown flag bits 0x%x", who, flags); return TRASE_ERR_INVALID; }
+  if (flags & TRASE_FRAME_MASK_BLACK)
+    return loss_forward_launch(who, img, GtBytes<true>{planes, pitch}, 3, H, W, out2, lambda_dssim, ws, ws_bytes, device, stream_);
+  return loss_forward_launch(who, img, GtBytes<false>{planes, pitch}, 3, H, W, out2, lambda_dssim, ws, ws_bytes, device, stream_);
+}
+
+template <class GT>
+static int loss_backward_launch(const char* who, const float* img, const GT& gt, int32_t C, int32_t H, int32_t W, const float* g2,
+                                int g_stride, float s_l1, float s_ssim, const void* ws, size_t ws_bytes, float* dL_dimg, int32_t device,
+                                trase_stream_t stream_) {
+  LossWs w;
+  if (!ws || ws_bytes < loss_layout(const_cast<void*>(ws), C, H, W, w)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  const dim3 grid((W + LT - 1) / LT, (H + LT - 1) / LT, C);
+  {
+    ProfScope ps("ssim_bwd", stream);
+    hipLaunchKernelGGL(ssim_bwd_kernel<GT>, grid, dim3(256), 0, stream, img, gt, H, W, make_window(), w.dmaps, g2,
+                       1.0f / ((float)C * H * W), dL_dimg, g_stride, s_l1, s_ssim);
+  }
+  TRASE_POST_LAUNCH("ssim_bwd", stream, 0);
+  return TRASE_OK;
+}
+
+static int loss_backward(const char* who, const float* img, const float* gt, int32_t C, int32_t H, int32_t W, const float* g2, int g_stride,
+                         float s_l1, float s_ssim, const void* ws, size_t ws_bytes, float* dL_dimg, int32_t device,
+                         trase_stream_t stream_) {
+  if (!img || !gt || !g2 || !dL_dimg || C < 1 || H < 1 || W < 1) { set_error("%s: bad arguments", who); return TRASE_ERR_INVALID; }
+  return loss_backward_launch(who, img, GtFloat{gt}, C, H, W, g2, g_stride, s_l1, s_ssim, ws, ws_bytes, dL_dimg, device, stream_);
+}
+
+static int loss_backward_u8(const char* who, const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags,
+                            const float* g2, int g_stride, float s_l1, float s_ssim, const void* ws, size_t ws_bytes, float* dL_dimg,
+                            int32_t device, trase_stream_t stream_) {
+  if (int rc = frame_args_ok(who, img, planes, dL_dimg, ws, H, W, pitch)) return rc;
+  if (!g2) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  if (flags & ~(uint32_t)TRASE_FRAME_MASK_BLACK) { set_error("%s: unknown flag bits 0x%x", who, flags); return TRASE_ERR_INVALID; }
+  if (flags & TRASE_FRAME_MASK_BLACK)
+    return loss_backward_launch(who, img, GtBytes<true>{planes, pitch}, 3, H, W, g2, g_stride, s_l1, s_ssim, ws, ws_bytes, dL_dimg, device,
+                                stream_);
+  return loss_backward_launch(who, img, GtBytes<false>{planes, pitch}, 3, H, W, g2, g_stride, s_l1, s_ssim, ws, ws_bytes, dL_dimg, device,
+                              stream_);
+}
+
+extern "C" {
+
+int trase_loss_sizes(int32_t C, int32_t H, int32_t W, size_t* ws_bytes) {
+  if (!ws_bytes || C < 1 || H < 1 || W < 1) { set_error("trase_loss_sizes: bad arguments"); return TRASE_ERR_INVALID; }
+  LossWs w;
+  *ws_bytes = loss_layout(nullptr, C, H, W, w);
   return TRASE_OK;
 }
 
@@ -320,24 +415,6 @@ int trase_loss_photometric_forward(const float* img, const float* gt, int32_t C,
   return loss_forward("trase_loss_photometric_forward", img, gt, C, H, W, out3, lambda_dssim, ws, ws_bytes, device, stream_);
 }
 
-static int loss_backward(const char* who, const float* img, const float* gt, int32_t C, int32_t H, int32_t W, const float* g2, int g_stride,
-                         float s_l1, float s_ssim, const void* ws, size_t ws_bytes, float* dL_dimg, int32_t device,
-                         trase_stream_t stream_) {
-  if (!img || !gt || !g2 || !dL_dimg || C < 1 || H < 1 || W < 1) { set_error("%s: bad arguments", who); return TRASE_ERR_INVALID; }
-  LossWs w;
-  if (!ws || ws_bytes < loss_layout(const_cast<void*>(ws), C, H, W, w)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
-  hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(device));
-  const dim3 grid((W + LT - 1) / LT, (H + LT - 1) / LT, C);
-  {
-    ProfScope ps("ssim_bwd", stream);
-    hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(256), 0, stream, img, gt, H, W, make_window(), w.dmaps, g2,
-                       1.0f / ((float)C * H * W), dL_dimg, g_stride, s_l1, s_ssim);
-  }
-  TRASE_POST_LAUNCH("ssim_bwd", stream, 0);
-  return TRASE_OK;
-}
-
 int trase_loss_l1_ssim_backward(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, const float* g2,
                                 const void* ws, size_t ws_bytes, float* dL_dimg, int32_t device, trase_stream_t stream_) {
   return loss_backward("trase_loss_l1_ssim_backward", img, gt, C, H, W, g2, 1, 1.0f, 1.0f, ws, ws_bytes, dL_dimg, device, stream_);
@@ -348,6 +425,30 @@ int trase_loss_photometric_backward(const float* img, const float* gt, int32_t C
                                     trase_stream_t stream_) {
   return loss_backward("trase_loss_photometric_backward", img, gt, C, H, W, g, 0, (float)(1.0 - lambda_dssim), -(float)lambda_dssim, ws, ws_bytes, dL_dimg,
                        device, stream_);
+}
+
+int trase_loss_l1_ssim_forward_u8(const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags, float* out2,
+                                  void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  return loss_forward_u8("trase_loss_l1_ssim_forward_u8", img, planes, H, W, pitch, flags, out2, -1.0, ws, ws_bytes, device, stream_);
+}
+
+int trase_loss_l1_ssim_backward_u8(const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags,
+                                   const float* g2, const void* ws, size_t ws_bytes, float* dL_dimg, int32_t device, trase_stream_t stream_) {
+  return loss_backward_u8("trase_loss_l1_ssim_backward_u8", img, planes, H, W, pitch, flags, g2, 1, 1.0f, 1.0f, ws, ws_bytes, dL_dimg, device,
+                          stream_);
+}
+
+int trase_loss_photometric_forward_u8(const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags,
+                                      double lambda_dssim, float* out3, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  if (!(lambda_dssim >= 0.0 && lambda_dssim <= 1.0)) { set_error("trase_loss_photometric_forward_u8: lambda_dssim outside [0, 1]"); return TRASE_ERR_INVALID; }
+  return loss_forward_u8("trase_loss_photometric_forward_u8", img, planes, H, W, pitch, flags, out3, lambda_dssim, ws, ws_bytes, device, stream_);
+}
+
+int trase_loss_photometric_backward_u8(const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags,
+                                       double lambda_dssim, const float* g, const void* ws, size_t ws_bytes, float* dL_dimg, int32_t device,
+                                       trase_stream_t stream_) {
+  return loss_backward_u8("trase_loss_photometric_backward_u8", img, planes, H, W, pitch, flags, g, 0, (float)(1.0 - lambda_dssim),
+                          -(float)lambda_dssim, ws, ws_bytes, dL_dimg, device, stream_);
 }
 
 }  // extern "C"

@@ -5,7 +5,10 @@
 ``l1_ssim(img, gt)`` returns both scalars from ONE forward kernel (separable 11-tap window from LDS tiles instead
 of the reference's five depthwise 11x11 convolutions) and back-propagates both with ONE backward kernel.
 ``ssim(img1, img2)`` and ``l1_loss(x, gt)`` keep the reference signatures; when they are called on the same pair of
-tensors (as train.py does) the second call reuses the first call's fused result."""
+tensors (as train.py does) the second call reuses the first call's fused result.
+
+The ground truth may also be a ``trase_amd.frames.ByteFrame`` (the frame as bytes): the same kernel bodies read the planes and
+convert with the exact division, so every result is bitwise that of the fp32 tensor ``frame.to_float()``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,25 +17,41 @@ import weakref
 import torch
 
 from . import _lib
+from .frames import ByteFrame
 from .rasterizer import _bytes, _stream
+
+MASK_BLACK = 1          # include/trase_rast.h TRASE_FRAME_MASK_BLACK
+
+
+def _gt_operand(gt, mask_black=False):
+    """(the tensor the kernels read, None | (pitch, flags)) of a ground truth given as a tensor or as a ByteFrame"""
+    if isinstance(gt, ByteFrame):
+        return gt.data, (gt.pitch, MASK_BLACK if mask_black else 0)
+    return gt, None
 
 
 class _L1SSIM(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, img, gt):
+    def forward(ctx, img, gt, u8=None):
+        # u8: None = gt is the (C,H,W) tensor; (pitch, flags) = gt is a ByteFrame's planes
         lib = _lib.load()
         dev = img.device
         x = img.detach().float().contiguous()
-        y = gt.detach().float().contiguous()
+        y = gt.detach().float().contiguous() if u8 is None else gt
         c, h, w = x.shape
         nbytes = C.c_size_t()
         _lib.check(lib.trase_loss_sizes(c, h, w, C.byref(nbytes)), "trase_loss_sizes")
         ws = _bytes(nbytes.value, dev)
         out2 = torch.empty(2, device=dev)
         d = dev.index if dev.index is not None else torch.cuda.current_device()
-        _lib.check(lib.trase_loss_l1_ssim_forward(_lib.ptr(x), _lib.ptr(y), c, h, w, _lib.ptr(out2), _lib.ptr(ws), ws.numel(),
-                                                  d, _stream(dev)), "trase_loss_l1_ssim_forward")
+        if u8 is None:
+            _lib.check(lib.trase_loss_l1_ssim_forward(_lib.ptr(x), _lib.ptr(y), c, h, w, _lib.ptr(out2), _lib.ptr(ws), ws.numel(),
+                                                      d, _stream(dev)), "trase_loss_l1_ssim_forward")
+        else:
+            _lib.check(lib.trase_loss_l1_ssim_forward_u8(_lib.ptr(x), _lib.ptr(y), h, w, u8[0], u8[1], _lib.ptr(out2), _lib.ptr(ws),
+                                                         ws.numel(), d, _stream(dev)), "trase_loss_l1_ssim_forward_u8")
         ctx.save_for_backward(x, y, ws)
+        ctx.u8 = u8
         return out2[0], out2[1]
 
     @staticmethod
@@ -48,29 +67,39 @@ class _L1SSIM(torch.autograd.Function):
         g2 = torch.stack([g_l1 if g_l1 is not None else z, g_ssim if g_ssim is not None else z]).float().contiguous()
         d_img = torch.empty_like(x)
         d = dev.index if dev.index is not None else torch.cuda.current_device()
-        _lib.check(lib.trase_loss_l1_ssim_backward(_lib.ptr(x), _lib.ptr(y), c, h, w, _lib.ptr(g2), _lib.ptr(ws), ws.numel(),
-                                                   _lib.ptr(d_img), d, _stream(dev)), "trase_loss_l1_ssim_backward")
-        return d_img, None
+        if ctx.u8 is None:
+            _lib.check(lib.trase_loss_l1_ssim_backward(_lib.ptr(x), _lib.ptr(y), c, h, w, _lib.ptr(g2), _lib.ptr(ws), ws.numel(),
+                                                       _lib.ptr(d_img), d, _stream(dev)), "trase_loss_l1_ssim_backward")
+        else:
+            _lib.check(lib.trase_loss_l1_ssim_backward_u8(_lib.ptr(x), _lib.ptr(y), h, w, ctx.u8[0], ctx.u8[1], _lib.ptr(g2), _lib.ptr(ws),
+                                                          ws.numel(), _lib.ptr(d_img), d, _stream(dev)), "trase_loss_l1_ssim_backward_u8")
+        return d_img, None, None
 
 
 class _Photometric(torch.autograd.Function):
     """One scalar out, one cotangent in: the combination of train.py:235-238 inside the two loss launches."""
 
     @staticmethod
-    def forward(ctx, img, gt, lambda_dssim):
+    def forward(ctx, img, gt, lambda_dssim, u8=None):
         lib = _lib.load()
         dev = img.device
         x = img.detach().float().contiguous()
-        y = gt.detach().float().contiguous()
+        y = gt.detach().float().contiguous() if u8 is None else gt          # u8: see _L1SSIM.forward
         c, h, w = x.shape
         nbytes = C.c_size_t()
         _lib.check(lib.trase_loss_sizes(c, h, w, C.byref(nbytes)), "trase_loss_sizes")
         ws = _bytes(nbytes.value, dev)
         out3 = torch.empty(3, device=dev)
         d = dev.index if dev.index is not None else torch.cuda.current_device()
-        _lib.check(lib.trase_loss_photometric_forward(_lib.ptr(x), _lib.ptr(y), c, h, w, float(lambda_dssim), _lib.ptr(out3),
-                                                      _lib.ptr(ws), ws.numel(), d, _stream(dev)), "trase_loss_photometric_forward")
+        if u8 is None:
+            _lib.check(lib.trase_loss_photometric_forward(_lib.ptr(x), _lib.ptr(y), c, h, w, float(lambda_dssim), _lib.ptr(out3),
+                                                          _lib.ptr(ws), ws.numel(), d, _stream(dev)), "trase_loss_photometric_forward")
+        else:
+            _lib.check(lib.trase_loss_photometric_forward_u8(_lib.ptr(x), _lib.ptr(y), h, w, u8[0], u8[1], float(lambda_dssim),
+                                                             _lib.ptr(out3), _lib.ptr(ws), ws.numel(), d, _stream(dev)),
+                       "trase_loss_photometric_forward_u8")
         ctx.save_for_backward(x, y, ws)
+        ctx.u8 = u8
         ctx.lam = float(lambda_dssim)
         ctx.mark_non_differentiable(out3)
         return out3[2], out3
@@ -85,33 +114,46 @@ class _Photometric(torch.autograd.Function):
             g = g.float().contiguous()
         d_img = torch.empty_like(x)
         d = dev.index if dev.index is not None else torch.cuda.current_device()
-        _lib.check(lib.trase_loss_photometric_backward(_lib.ptr(x), _lib.ptr(y), c, h, w, ctx.lam, _lib.ptr(g), _lib.ptr(ws), ws.numel(),
-                                                       _lib.ptr(d_img), d, _stream(dev)), "trase_loss_photometric_backward")
-        return d_img, None, None
+        if ctx.u8 is None:
+            _lib.check(lib.trase_loss_photometric_backward(_lib.ptr(x), _lib.ptr(y), c, h, w, ctx.lam, _lib.ptr(g), _lib.ptr(ws), ws.numel(),
+                                                           _lib.ptr(d_img), d, _stream(dev)), "trase_loss_photometric_backward")
+        else:
+            _lib.check(lib.trase_loss_photometric_backward_u8(_lib.ptr(x), _lib.ptr(y), h, w, ctx.u8[0], ctx.u8[1], ctx.lam, _lib.ptr(g),
+                                                              _lib.ptr(ws), ws.numel(), _lib.ptr(d_img), d, _stream(dev)),
+                       "trase_loss_photometric_backward_u8")
+        return d_img, None, None, None
 
 
-def photometric_loss(img: torch.Tensor, gt: torch.Tensor, lambda_dssim: float = 0.2, with_parts: bool = False):
+def photometric_loss(img: torch.Tensor, gt, lambda_dssim: float = 0.2, with_parts: bool = False, *, mask_black: bool = False):
     """``(1 - lambda_dssim) * l1_loss(img, gt) + lambda_dssim * (1 - ssim(img, gt))`` (train.py:235-238) as ONE autograd node: the
     scalar composition happens inside the loss kernels (forward: in the reduction kernel; backward: the cotangent is scaled
     in the SSIM backward kernel), so the ~10 one-element kernels PyTorch launches for the reference's two lines are gone.
-    with_parts: also return the detached (l1, ssim) scalars (train.py logs Ll1, :303)."""
-    _check(img, gt)
-    loss, parts = _Photometric.apply(img, gt, lambda_dssim)
+    with_parts: also return the detached (l1, ssim) scalars (train.py logs Ll1, :303).
+    gt: the (3,H,W) tensor or a ByteFrame.  mask_black (ByteFrame only): train.py:231-234 fused -- where the frame's pixel is black
+    the rendered value counts as 0, in the window too, and receives no gradient (a non-finite rendered value there is ignored,
+    where the reference's ``image * 0`` gives NaN)."""
+    _check(img, gt, mask_black)
+    y, u8 = _gt_operand(gt, mask_black)
+    loss, parts = _Photometric.apply(img, y, lambda_dssim, u8)
     return (loss, parts[0], parts[1]) if with_parts else loss
 
 
-def _check(img, gt):
+def _check(img, gt, mask_black=False):
+    if mask_black and not isinstance(gt, ByteFrame):
+        raise TypeError("mask_black=True needs the ground truth as a trase_amd.frames.ByteFrame (ByteFrame.from_float(gt) makes one)")
     if img.device.type != "cuda":
         raise RuntimeError("trase_amd.losses runs on the GPU only (there is no CPU path)")
-    if img.dim() != 3 or img.shape != gt.shape:
+    if img.dim() != 3 or tuple(img.shape) != tuple(gt.shape):
         raise ValueError(f"expected two (C,H,W) images of equal shape, got {tuple(img.shape)} and {tuple(gt.shape)}")
+    if isinstance(gt, ByteFrame) and gt.device != img.device:
+        raise ValueError(f"the ByteFrame is on {gt.device}, the image on {img.device}")
 
 
-def l1_ssim(img: torch.Tensor, gt: torch.Tensor):
+def l1_ssim(img: torch.Tensor, gt, *, mask_black: bool = False):
     """(mean |img - gt|, mean SSIM(img, gt)) -- one fused forward, one fused backward (gradient w.r.t. img only,
-    the reference's gt is a constant)."""
-    _check(img, gt)
-    return _L1SSIM.apply(img, gt)
+    the reference's gt is a constant).  gt: the tensor or a ByteFrame; mask_black as in photometric_loss."""
+    _check(img, gt, mask_black)
+    return _L1SSIM.apply(img, *_gt_operand(gt, mask_black))
 
 
 _last = {"img": None, "gt": None, "ver": None, "val": None}
