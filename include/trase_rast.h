@@ -324,10 +324,46 @@ int trase_knn_dist2(const float* points, int32_t N, float* out, void* ws, size_t
 
 /* pytorch3d.ops.knn_points replacement (scene/gaussian_model.py:88-92 K=16 self-KNN for feature
  * smoothing; render.py:222, gui.py:1048, utils/loss_utils.py:141,192 cross-KNN): for every point of
- * p1 the K (<= 16) nearest points of p2, ascending; idx int64 (N1,K), squared distances (N1,K).
- * Workspace: trase_knn_sizes(N2). */
+ * p1 the K (1 <= K <= 256) nearest points of p2, ascending by (squared distance, index); idx int64 (N1,K),
+ * squared distances (N1,K); idx 0 / distance 0 where p2 has fewer than K points.  K <= 16 runs one thread
+ * per query, a larger K one wave per query with its list in LDS.  Workspace: trase_knn_sizes(N2) for every K. */
 int trase_knn_points(const float* p1, int32_t N1, const float* p2, int32_t N2, int32_t K, int64_t* idx,
                      float* dists, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+
+/* ---- losses over a k-NN graph (utils/loss_utils.py:132-152 loss_reg_3d_feature, :179-221
+ * loss_rigid_body_motion_reg_loss) without N x k x ... edge tensors --------------------------------------------
+ * A graph is idx (N,k) int32: edge e = i*k + slot runs from row i to row idx[e]; N*k < 2^31.  An id outside [0,N)
+ * is an edge to nowhere (it contributes nothing and is never dereferenced).
+ * trase_graph_reverse transposes it: rev_edges (N*k) holds the edge numbers sorted stably by their target (so
+ * ascending among the edges of one target), rev_ranges (N,2) the [begin,end) positions of every target's edges.
+ * The backward passes gather over it instead of using float atomics, so they are bitwise reproducible. */
+/* (named *_ws_bytes like trase_mlp_split_ws_bytes: the recorded table of the *_sizes functions, tests/golden/workspace_sizes.json,
+ * pins the layouts that existed when it was written) */
+int trase_graph_reverse_ws_bytes(int32_t N, int32_t k, size_t* ws_bytes);
+int trase_graph_reverse(const int32_t* idx, int32_t N, int32_t k, int32_t* rev_ranges, int32_t* rev_edges, void* ws,
+                        size_t ws_bytes, int32_t device, trase_stream_t stream);
+/* loss = mean over (i,slot,d) of s_i (log(s_i + 1e-10) - log(s_j + 1e-10)), s = sigmoid(feats), feats (N,D), D <= 64.
+ * The forward writes the tables s_tab, l_tab (N,D each) that the backward reads; loss and g_loss are device scalars.
+ * Workspace: trase_feat3d_ws_bytes(N, D). */
+int trase_feat3d_ws_bytes(int32_t N, int32_t D, size_t* ws_bytes);
+int trase_feat3d_forward(const float* feats, const int32_t* idx, int32_t N, int32_t D, int32_t k, float* s_tab, float* l_tab,
+                         float* loss, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+int trase_feat3d_backward(const float* s_tab, const float* l_tab, const int32_t* idx, const int32_t* rev_ranges,
+                          const int32_t* rev_edges, int32_t N, int32_t D, int32_t k, const float* g_loss, float* g_feats,
+                          int32_t device, trase_stream_t stream);
+/* With e1 = p1[i] - p1[j], e2 = p2[i] - p2[j], j = idx[i,slot]:  S (N,3,3) = sum_slot e1 e2^T;
+ * out (N) = sum_slot |e1 - R[i] e2|^2 with R (N,3,3).  The backward passes take the cotangents gS (N,3,3) / g (N)
+ * and write g1, g2 (N,3) and gR (N,3,3). */
+int trase_edge_moments_forward(const float* p1, const float* p2, const int32_t* idx, int32_t N, int32_t k, float* S,
+                               int32_t device, trase_stream_t stream);
+int trase_edge_moments_backward(const float* p1, const float* p2, const int32_t* idx, const int32_t* rev_ranges,
+                                const int32_t* rev_edges, int32_t N, int32_t k, const float* gS, float* g1, float* g2,
+                                int32_t device, trase_stream_t stream);
+int trase_edge_residual_forward(const float* p1, const float* p2, const int32_t* idx, const float* R, int32_t N, int32_t k,
+                                float* out, int32_t device, trase_stream_t stream);
+int trase_edge_residual_backward(const float* p1, const float* p2, const int32_t* idx, const int32_t* rev_ranges,
+                                 const int32_t* rev_edges, const float* R, int32_t N, int32_t k, const float* g, float* g1,
+                                 float* g2, float* gR, int32_t device, trase_stream_t stream);
 
 /* Deformation MLP (utils/time_utils.py:60-131 DeformNetwork.forward, reached through
  * scene/deform_model.py:34-35 DeformModel.step at train.py:202-204, render.py:195, gui.py:965).

@@ -71,7 +71,8 @@ __global__ __launch_bounds__(256) void knn_bbox_kernel(const float* __restrict__
   }
 }
 
-__global__ void knn_params_kernel(KnnParams* p) {
+// occ: target points per cell (4 for the register-list kernels; the wide k-NN asks for cells that hold about K points)
+__global__ void knn_params_kernel(KnnParams* p, float occ) {
   float e[3];
   for (int k = 0; k < 3; ++k) {
     p->origin[k] = ord2f(p->bb[k]);
@@ -83,7 +84,6 @@ __global__ void knn_params_kernel(KnnParams* p) {
   if (b < c) { float t = b; b = c; c = t; }
   if (a < b) { float t = a; a = b; b = t; }
   const float n = (float)(p->n > 0 ? p->n : 1);
-  const float occ = 4.0f;                       // target points per cell
   const float h1 = occ * a / n;
   const float h2 = sqrtf(occ * a * b / n);
   const float h3 = cbrtf(occ * a * b * c / n);
@@ -248,6 +248,125 @@ __global__ __launch_bounds__(256) void knn_points_kernel(const float* __restrict
   }
 }
 
+// ---- wide k-NN: 17 <= K <= 256 ---------------------------------------------------------------------------------------
+// knn_walk's sorted register list cannot hold that many entries, so here ONE WAVE serves a query and the list lives in LDS.
+// The wave walks the cube shells in knn_walk's order; its lanes take the entries of a bucket, apply the same true-cell
+// filter and evaluate dx*dx + dy*dy + dz*dz (in float64, rounded once to fp32).  A candidate is the 64-bit key (float bits of d) << 32 | id: d >= 0, so
+// its bits order like its value and the key order IS knn_walk's total order (distance, then lower index).  Keys below the
+// current K-th are appended behind the kept K through a ballot prefix; when that staging area cannot take another 64 the
+// whole array (a power of two, at most 512 keys) is sorted in LDS by the wave and the threshold drops to the new K-th.
+// The walk ends by the narrow kernel's rule.  No workgroup barrier anywhere: the four waves of a block are independent.
+constexpr int KW_WAVES = 4;
+constexpr int KW_KEYS = 512;                      // kept K (<= 256) + staging (>= 64)
+constexpr int KW_MAX_K = 256;
+constexpr uint64_t KW_NONE = ~0ull;               // above every key of a finite distance
+
+// LDS written by some lanes of the wave is read by others: order the accesses (for the compiler and the counters)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ascending bitonic sort of keys[0, n) by one wave; n a power of two, 128 <= n <= KW_KEYS
+__device__ __forceinline__ void kw_sort(uint64_t* keys, int n, int lane) {
+  for (int size = 2; size <= n; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = lane; t < (n >> 1); t += WAVE) {
+        const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1));     // t with a 0 inserted at the stride's bit
+        const int hi = lo | stride;
+        const bool up = (lo & size) == 0;
+        const uint64_t a = keys[lo], b = keys[hi];
+        if ((a > b) == up) { keys[lo] = b; keys[hi] = a; }
+      }
+      wave_lds_sync();
+    }
+}
+
+// total: keys of LDS this K uses, a power of two with 128 <= total <= KW_KEYS and total - K >= 64
+__global__ __launch_bounds__(WAVE * KW_WAVES) void knn_points_wide_kernel(const float* __restrict__ qpts, int nq,
+                                                                          const float* __restrict__ pts, int n, int K, int total,
+                                                                          const KnnParams* pp, uint32_t mask,
+                                                                          const uint32_t* __restrict__ sorted_ids,
+                                                                          const uint2* __restrict__ buckets,
+                                                                          int64_t* __restrict__ idx_out, float* __restrict__ dist_out) {
+  __shared__ uint64_t lds[KW_WAVES][KW_KEYS];
+  const int lane = (int)(threadIdx.x & (WAVE - 1));
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int i = blockIdx.x * KW_WAVES + wv;
+  if (i >= nq) return;
+  uint64_t* keys = lds[wv];
+  const KnnParams p = *pp;
+  const float x = qpts[3 * (size_t)i], y = qpts[3 * (size_t)i + 1], z = qpts[3 * (size_t)i + 2];
+  for (int t = lane; t < total; t += WAVE) keys[t] = KW_NONE;
+  wave_lds_sync();
+  const int cap = total - K;          // room behind the kept K
+  int staged = 0;
+  uint64_t thr = KW_NONE;             // the K-th key so far: a candidate must be below it
+  // sort kept + staged, keep the K smallest
+  auto merge = [&]() {
+    const int used = K + staged;
+    int ns = 128;
+    while (ns < used) ns <<= 1;
+    for (int t = used + lane; t < ns; t += WAVE) keys[t] = KW_NONE;
+    wave_lds_sync();
+    kw_sort(keys, ns, lane);
+    thr = keys[K - 1];
+    staged = 0;
+  };
+  if (fabsf(x) < 3.0e38f && fabsf(y) < 3.0e38f && fabsf(z) < 3.0e38f) {     // a NaN / inf query finds nothing
+    int cx, cy, cz;
+    cell_of(p, x, y, z, cx, cy, cz);
+    const int rmax = max(p.dims[0], max(p.dims[1], p.dims[2]));
+    for (int r = 0; r <= rmax; ++r) {
+      const int z0 = max(cz - r, 0), z1 = min(cz + r, p.dims[2] - 1);
+      const int y0 = max(cy - r, 0), y1 = min(cy + r, p.dims[1] - 1);
+      const int x0 = max(cx - r, 0), x1 = min(cx + r, p.dims[0] - 1);
+      for (int zz = z0; zz <= z1; ++zz)
+        for (int yy = y0; yy <= y1; ++yy) {
+          const bool face = (abs(zz - cz) == r) || (abs(yy - cy) == r);
+          const int step = face ? 1 : max(1, 2 * r);
+          for (int xx = face ? x0 : cx - r; xx <= (face ? x1 : cx + r); xx += step) {
+            if (xx < 0 || xx >= p.dims[0]) continue;
+            const uint2 bk = buckets[cell_hash(xx, yy, zz, mask)];
+            for (uint32_t k0 = bk.x; k0 < bk.y; k0 += WAVE) {
+              if (staged + WAVE > cap) merge();
+              const uint32_t k = k0 + (uint32_t)lane;
+              uint64_t key = KW_NONE;
+              if (k < bk.y) {
+                const uint32_t j = sorted_ids[k];
+                const float qx = pts[3 * (size_t)j], qy = pts[3 * (size_t)j + 1], qz = pts[3 * (size_t)j + 2];
+                int ox, oy, oz;
+                cell_of(p, qx, qy, qz, ox, oy, oz);
+                // differences and squares in float64 are exact, so d is the squared distance rounded ONCE (three roundings
+                // of the sum, each far below an fp32 ulp, aside): within 2^-24 relative where knn_walk's all-fp32 expression
+                // can be 5 * 2^-24 off.  Where that expression is exact -- coordinates on a grid -- the two agree bit for bit.
+                const double dx = (double)qx - (double)x, dy = (double)qy - (double)y, dz = (double)qz - (double)z;
+                const float d = (float)(dx * dx + dy * dy + dz * dz);
+                // (a hash collision belongs to another cell; a NaN or overflowed distance is never a neighbour, as in knn_walk)
+                if (ox == xx && oy == yy && oz == zz && d < 3.0e38f) key = ((uint64_t)__float_as_uint(d) << 32) | j;
+              }
+              const bool pass = key < thr;
+              const unsigned long long m = __ballot(pass);
+              if (pass) keys[K + staged + __popcll(m & lanemask_lt())] = key;
+              staged += __popcll(m);
+            }
+          }
+        }
+      if (staged > 0) merge();
+      const float kd = thr == KW_NONE ? 3.0e38f : __uint_as_float((uint32_t)(thr >> 32));
+      const float bound = (float)r * p.h;
+      if (kd <= bound * bound && r > 0) break;
+    }
+  }
+  wave_lds_sync();
+  for (int k = lane; k < K; k += WAVE) {
+    const uint64_t key = keys[k];
+    const bool have = key != KW_NONE;      // fewer than K points in the cloud: pad like pytorch3d (idx 0, dist 0)
+    idx_out[(size_t)i * K + k] = have ? (int64_t)(uint32_t)key : 0;
+    dist_out[(size_t)i * K + k] = have ? __uint_as_float((uint32_t)(key >> 32)) : 0.0f;
+  }
+}
+
 // ---- prompt lift: 2D prompts to cluster votes (render.py:208-229, gui.py:1039-1064; one clicked pixel: gui.py:786-800) ----
 // One thread per pixel of a 16 x 16 tile (mask form) or per listed pixel (click form): read the mask and the depth,
 // un-project, walk the hash for the nearest point (knn_walk<1>, everything in registers), read its cluster id, vote.
@@ -373,14 +492,15 @@ int trase_knn_sizes(int32_t N, size_t* ws_bytes) {
   return TRASE_OK;
 }
 
-static int knn_build(const LaunchCtx& c, const float* points, int32_t N, KnnWs& w, uint32_t mask, int bits, int* idx_out) {
+static int knn_build(const LaunchCtx& c, const float* points, int32_t N, KnnWs& w, uint32_t mask, int bits, int* idx_out,
+                     float occ = 4.0f) {
   hipStream_t stream = c.stream;
   const int blocks = (N + 255) / 256;
   {
     ProfScope ps("knn_bbox", stream);
     hipLaunchKernelGGL(knn_init_kernel, dim3(1), dim3(1), 0, stream, w.prm, (uint32_t)N);
     hipLaunchKernelGGL(knn_bbox_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, stream, points, N, w.prm);
-    hipLaunchKernelGGL(knn_params_kernel, dim3(1), dim3(1), 0, stream, w.prm);
+    hipLaunchKernelGGL(knn_params_kernel, dim3(1), dim3(1), 0, stream, w.prm, occ);
     hipLaunchKernelGGL(knn_keys_kernel, dim3(blocks), dim3(256), 0, stream, points, N, w.prm, mask, w.sort.keys[0]);
   }
   TRASE_POST_LAUNCH("knn_keys", stream, 0);
@@ -415,9 +535,13 @@ int trase_knn_dist2(const float* points, int32_t N, float* out, void* ws, size_t
 // pytorch3d.ops.knn_points replacement (call sites scene/gaussian_model.py:88-92 K=16 self-KNN,
 // render.py:222 / gui.py:1048 / utils/loss_utils.py:141,192 cross-KNN): the K nearest points of
 // p2 for every point of p1, ascending, squared distances; a query that is itself in p2 finds itself.
+// K <= 16: one thread per query (knn_points_kernel); 17 <= K <= 256: one wave per query (knn_points_wide_kernel).
 int trase_knn_points(const float* p1, int32_t N1, const float* p2, int32_t N2, int32_t K, int64_t* idx_out,
                      float* dist_out, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
-  if (N1 < 0 || N2 < 0 || K < 1 || K > 16) { set_error("trase_knn_points: need 1 <= K <= 16 (got %d)", K); return TRASE_ERR_INVALID; }
+  if (N1 < 0 || N2 < 0 || K < 1 || K > KW_MAX_K) {
+    set_error("trase_knn_points: need N1, N2 >= 0 and 1 <= K <= %d (got N1 %d, N2 %d, K %d)", KW_MAX_K, N1, N2, K);
+    return TRASE_ERR_INVALID;
+  }
   if (N1 == 0) return TRASE_OK;
   if (!p1 || !idx_out || !dist_out || (N2 > 0 && !p2)) { set_error("trase_knn_points: null pointer"); return TRASE_ERR_INVALID; }
   if (!ws || ws_bytes < knn_ws_bytes(N2)) { set_error("trase_knn_points: workspace too small"); return TRASE_ERR_WORKSPACE; }
@@ -434,8 +558,21 @@ int trase_knn_points(const float* p1, int32_t N1, const float* p2, int32_t N2, i
   const int bits = knn_bits(N2);
   const uint32_t mask = (1u << bits) - 1u;
   int idx = 0;
-  int rc = knn_build(c, p2, N2, w, mask, bits, &idx);
+  const bool wide = K > 16;
+  // wide: cells of about 3 K / 4 points, so that the ball the first shell guarantees usually holds the K nearest
+  int rc = knn_build(c, p2, N2, w, mask, bits, &idx, wide ? 0.75f * (float)K : 4.0f);
   if (rc) return rc;
+  if (wide) {
+    int total = 128;
+    while (total < 2 * K + WAVE && total < KW_KEYS) total <<= 1;
+    {
+      ProfScope ps("knn_points_wide", stream);
+      hipLaunchKernelGGL(knn_points_wide_kernel, dim3((N1 + KW_WAVES - 1) / KW_WAVES), dim3(WAVE * KW_WAVES), 0, stream, p1, N1,
+                         p2, N2, K, total, w.prm, mask, w.sort.vals[idx], w.buckets, idx_out, dist_out);
+    }
+    TRASE_POST_LAUNCH("knn_points_wide", stream, 0);
+    return TRASE_OK;
+  }
   {
     ProfScope ps("knn_points_query", stream);
 #define TRASE_KQ(KT) hipLaunchKernelGGL((knn_points_kernel<KT>), dim3(blocks), dim3(256), 0, stream, p1, N1, p2, N2, K, w.prm, mask, w.sort.vals[idx], w.buckets, idx_out, dist_out)

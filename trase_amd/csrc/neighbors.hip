@@ -1,0 +1,453 @@
+// neighbors.hip -- losses over a k-NN graph without N x k x ... edge tensors (utils/loss_utils.py:132-152 loss_reg_3d_feature,
+// :179-221 loss_rigid_body_motion_reg_loss).
+//
+// A graph is idx (N, k) int32: edge number e = i * k + slot runs from row i (the "+" end) to row idx[e] (the "-" end).  A loss
+// over the edges sends gradient to BOTH ends.  The "+" end is a loop over the row's own slots; the "-" end needs every edge
+// that points AT a row.  Like every other backward of this library it is a gather, not a float atomic: the graph is transposed
+// once (trase_graph_reverse: the stable radix sort of binning.hip over the targets with iota values, then launch_tile_ranges) and
+// each row walks its incoming edges in ascending edge order, so every sum has one fixed order and is bitwise reproducible.
+// An id outside [0, N) (a caller's own index tensor) is an edge to nowhere: it lands in no range and is never dereferenced.
+#include "common.h"
+
+namespace trase {
+
+// ---- the transposed graph ---------------------------------------------------------------------------------------------
+struct RevWs { uint32_t* n; SortBufs sort; uint2* ranges; };
+static int rev_bits(int N) {
+  int bits = 1;
+  while ((1u << bits) < (uint32_t)N + 1u) ++bits;      // keys 0 .. N (N = "no such row")
+  return bits;
+}
+static size_t rev_layout(void* ws, int N, int k, RevWs& w) {
+  WsCursor c(ws);
+  const size_t M = (size_t)N * (size_t)k;
+  w.n = c.take<uint32_t>(1);
+  sort_layout(c, w.sort, M > 0 ? M : 1, SORT_ALL, 8, 1);
+  w.ranges = c.take<uint2>((size_t)N + 1);
+  return c.bytes();
+}
+
+__global__ __launch_bounds__(256) void rev_keys_kernel(const int32_t* __restrict__ idx, uint32_t M, uint32_t N,
+                                                       uint32_t* __restrict__ keys, uint32_t* __restrict__ n_word) {
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  if (e == 0) *n_word = M;
+  if (e >= M) return;
+  const uint32_t t = (uint32_t)idx[e];
+  keys[e] = t < N ? t : N;
+}
+
+__global__ __launch_bounds__(256) void rev_finish_kernel(const uint32_t* __restrict__ vals, const uint2* __restrict__ ranges,
+                                                         uint32_t M, uint32_t N, int32_t* __restrict__ rev_edges,
+                                                         int32_t* __restrict__ rev_ranges) {
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  if (e < M) rev_edges[e] = (int32_t)vals[e];
+  if (e < N) { const uint2 r = ranges[e]; rev_ranges[2 * (size_t)e] = (int32_t)r.x; rev_ranges[2 * (size_t)e + 1] = (int32_t)r.y; }
+}
+
+// ---- loss_reg_3d_feature ------------------------------------------------------------------------------------------------
+//   loss = mean over (i, slot, d) of s_i (log(s_i + eps) - log(s_j + eps)),  s = sigmoid(f),  j = idx[i, slot]
+constexpr float F3_EPS = 1e-10f;
+constexpr int F3_MAX_D = 64;
+
+__global__ __launch_bounds__(256) void f3_table_kernel(const float* __restrict__ f, uint32_t n, float* __restrict__ s_tab,
+                                                       float* __restrict__ l_tab) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= n) return;
+  const float s = 1.0f / (1.0f + expf(-f[t]));
+  s_tab[t] = s;
+  l_tab[t] = logf(s + F3_EPS);
+}
+
+// A[i, d] = sum over the row's slots, in slot order, of (l[i, d] - l[j, d]); an edge to nowhere adds nothing
+__device__ __forceinline__ float f3_row_sum(const float* __restrict__ l_tab, const int32_t* __restrict__ idx, uint32_t i, uint32_t d,
+                                            uint32_t N, uint32_t D, uint32_t k) {
+  const float li = l_tab[(size_t)i * D + d];
+  float a = 0.f;
+  for (uint32_t slot = 0; slot < k; ++slot) {
+    const uint32_t j = (uint32_t)idx[(size_t)i * k + slot];
+    if (j < N) a += li - l_tab[(size_t)j * D + d];
+  }
+  return a;
+}
+
+// sum of the 256 values of a block in one fixed order (a tree over LDS); valid in thread 0
+__device__ __forceinline__ double block_sum_256(double v, double* sh) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < (unsigned)s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// one thread per (i, d), d fastest: the gathered rows of l are read D contiguous floats at a time
+__global__ __launch_bounds__(256) void f3_forward_kernel(const float* __restrict__ s_tab, const float* __restrict__ l_tab,
+                                                         const int32_t* __restrict__ idx, uint32_t N, uint32_t D, uint32_t k,
+                                                         double* __restrict__ partial) {
+  __shared__ double sh[256];
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  float v = 0.f;
+  if (t < N * D) {
+    const uint32_t i = t / D, d = t - i * D;
+    v = s_tab[t] * f3_row_sum(l_tab, idx, i, d, N, D, k);
+  }
+  const double tot = block_sum_256((double)v, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+// second stage: one block, every thread a strided share in ascending order, then the tree; out = sum * scale
+__global__ __launch_bounds__(256) void f3_reduce_kernel(const double* __restrict__ partial, uint32_t n, double scale,
+                                                        float* __restrict__ out) {
+  __shared__ double sh[256];
+  double v = 0.0;
+  for (uint32_t b = threadIdx.x; b < n; b += 256u) v += partial[b];
+  const double tot = block_sum_256(v, sh);
+  if (threadIdx.x == 0) *out = (float)(tot * scale);
+}
+
+// d loss / d f[i, d] = g c [ A + (k s - R) / (s + eps) ] s (1 - s),  c = 1 / (N k D),
+// R[i, d] = sum over the edges that point at i, in ascending edge order, of s[source row, d]
+__global__ __launch_bounds__(256) void f3_backward_kernel(const float* __restrict__ s_tab, const float* __restrict__ l_tab,
+                                                          const int32_t* __restrict__ idx, const int32_t* __restrict__ rev_ranges,
+                                                          const int32_t* __restrict__ rev_edges, uint32_t N, uint32_t D, uint32_t k,
+                                                          const float* __restrict__ g_loss, float c, float* __restrict__ g_f) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= N * D) return;
+  const uint32_t i = t / D, d = t - i * D;
+  const float s = s_tab[t];
+  const float a = f3_row_sum(l_tab, idx, i, d, N, D, k);
+  uint32_t valid = 0;
+  for (uint32_t slot = 0; slot < k; ++slot) valid += ((uint32_t)idx[(size_t)i * k + slot] < N) ? 1u : 0u;
+  float r = 0.f;
+  const uint32_t e0 = (uint32_t)rev_ranges[2 * (size_t)i], e1 = (uint32_t)rev_ranges[2 * (size_t)i + 1];
+  for (uint32_t q = e0; q < e1; ++q) {
+    const uint32_t src = (uint32_t)rev_edges[q] / k;
+    r += s_tab[(size_t)src * D + d];
+  }
+  const float dl = ((float)valid * s - r) / (s + F3_EPS);
+  g_f[t] = (*g_loss * c) * ((a + dl) * (s * (1.0f - s)));
+}
+
+// ---- edge ops of the rigid-motion loss -----------------------------------------------------------------------------------
+//   e1 = p1[i] - p1[j], e2 = p2[i] - p2[j], j = idx[i, slot]
+//   edge_moments:  S[i] = sum_slot e1 e2^T (3 x 3, row index from e1)
+//   edge_residual: r[i] = sum_slot |e1 - R[i] e2|^2
+struct V3 { float x, y, z; };
+__device__ __forceinline__ V3 ld3(const float* __restrict__ p, uint32_t i) { return {p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]}; }
+__device__ __forceinline__ V3 sub3(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+struct M3 { float m[9]; };
+__device__ __forceinline__ M3 ldm(const float* __restrict__ p, uint32_t i) {
+  M3 r;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) r.m[q] = p[9 * (size_t)i + q];
+  return r;
+}
+__device__ __forceinline__ V3 mul_mv(const M3& a, V3 v) {       // a v
+  return {a.m[0] * v.x + a.m[1] * v.y + a.m[2] * v.z, a.m[3] * v.x + a.m[4] * v.y + a.m[5] * v.z,
+          a.m[6] * v.x + a.m[7] * v.y + a.m[8] * v.z};
+}
+__device__ __forceinline__ V3 mul_tv(const M3& a, V3 v) {       // a^T v
+  return {a.m[0] * v.x + a.m[3] * v.y + a.m[6] * v.z, a.m[1] * v.x + a.m[4] * v.y + a.m[7] * v.z,
+          a.m[2] * v.x + a.m[5] * v.y + a.m[8] * v.z};
+}
+
+__global__ __launch_bounds__(256) void edge_moments_fwd_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                               const int32_t* __restrict__ idx, uint32_t N, uint32_t k,
+                                                               float* __restrict__ S) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= N) return;
+  const V3 a1 = ld3(p1, i), a2 = ld3(p2, i);
+  float s[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (uint32_t slot = 0; slot < k; ++slot) {
+    const uint32_t j = (uint32_t)idx[(size_t)i * k + slot];
+    if (j >= N) continue;
+    const V3 e1 = sub3(a1, ld3(p1, j)), e2 = sub3(a2, ld3(p2, j));
+    s[0] += e1.x * e2.x; s[1] += e1.x * e2.y; s[2] += e1.x * e2.z;
+    s[3] += e1.y * e2.x; s[4] += e1.y * e2.y; s[5] += e1.y * e2.z;
+    s[6] += e1.z * e2.x; s[7] += e1.z * e2.y; s[8] += e1.z * e2.z;
+  }
+#pragma unroll
+  for (int q = 0; q < 9; ++q) S[9 * (size_t)i + q] = s[q];
+}
+
+// g1[i] = sum_slot G_i e2 - sum_{edges at i} G_src e2,   g2[i] = sum_slot G_i^T e1 - sum_{edges at i} G_src^T e1
+__global__ __launch_bounds__(256) void edge_moments_bwd_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                               const int32_t* __restrict__ idx, const int32_t* __restrict__ rev_ranges,
+                                                               const int32_t* __restrict__ rev_edges, uint32_t N, uint32_t k,
+                                                               const float* __restrict__ gS, float* __restrict__ g1,
+                                                               float* __restrict__ g2) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= N) return;
+  const V3 a1 = ld3(p1, i), a2 = ld3(p2, i);
+  V3 s1 = {0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f};     // the sums of e1, e2 over the row's own edges: G_i is common to them
+  for (uint32_t slot = 0; slot < k; ++slot) {
+    const uint32_t j = (uint32_t)idx[(size_t)i * k + slot];
+    if (j >= N) continue;
+    const V3 e1 = sub3(a1, ld3(p1, j)), e2 = sub3(a2, ld3(p2, j));
+    s1.x += e1.x; s1.y += e1.y; s1.z += e1.z;
+    s2.x += e2.x; s2.y += e2.y; s2.z += e2.z;
+  }
+  const M3 G = ldm(gS, i);
+  V3 o1 = mul_mv(G, s2), o2 = mul_tv(G, s1);
+  const uint32_t q0 = (uint32_t)rev_ranges[2 * (size_t)i], q1 = (uint32_t)rev_ranges[2 * (size_t)i + 1];
+  for (uint32_t q = q0; q < q1; ++q) {
+    const uint32_t src = (uint32_t)rev_edges[q] / k;
+    const V3 e1 = sub3(ld3(p1, src), a1), e2 = sub3(ld3(p2, src), a2);
+    const M3 Gs = ldm(gS, src);
+    const V3 u = mul_mv(Gs, e2), v = mul_tv(Gs, e1);
+    o1.x -= u.x; o1.y -= u.y; o1.z -= u.z;
+    o2.x -= v.x; o2.y -= v.y; o2.z -= v.z;
+  }
+  g1[3 * (size_t)i] = o1.x; g1[3 * (size_t)i + 1] = o1.y; g1[3 * (size_t)i + 2] = o1.z;
+  g2[3 * (size_t)i] = o2.x; g2[3 * (size_t)i + 1] = o2.y; g2[3 * (size_t)i + 2] = o2.z;
+}
+
+__global__ __launch_bounds__(256) void edge_residual_fwd_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                                const int32_t* __restrict__ idx, const float* __restrict__ R,
+                                                                uint32_t N, uint32_t k, float* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= N) return;
+  const V3 a1 = ld3(p1, i), a2 = ld3(p2, i);
+  const M3 Ri = ldm(R, i);
+  float acc = 0.f;
+  for (uint32_t slot = 0; slot < k; ++slot) {
+    const uint32_t j = (uint32_t)idx[(size_t)i * k + slot];
+    if (j >= N) continue;
+    const V3 e1 = sub3(a1, ld3(p1, j)), e2 = sub3(a2, ld3(p2, j));
+    const V3 v = sub3(e1, mul_mv(Ri, e2));
+    acc += v.x * v.x + v.y * v.y + v.z * v.z;
+  }
+  out[i] = acc;
+}
+
+// with v = e1 - R e2 and the cotangent g of r:  d/de1 = 2 g v,  d/de2 = -2 g R^T v,  d/dR = -2 g sum v e2^T
+__global__ __launch_bounds__(256) void edge_residual_bwd_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                                const int32_t* __restrict__ idx, const int32_t* __restrict__ rev_ranges,
+                                                                const int32_t* __restrict__ rev_edges, const float* __restrict__ R,
+                                                                uint32_t N, uint32_t k, const float* __restrict__ g,
+                                                                float* __restrict__ g1, float* __restrict__ g2, float* __restrict__ gR) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= N) return;
+  const V3 a1 = ld3(p1, i), a2 = ld3(p2, i);
+  const M3 Ri = ldm(R, i);
+  V3 sv = {0.f, 0.f, 0.f};
+  float m[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (uint32_t slot = 0; slot < k; ++slot) {
+    const uint32_t j = (uint32_t)idx[(size_t)i * k + slot];
+    if (j >= N) continue;
+    const V3 e1 = sub3(a1, ld3(p1, j)), e2 = sub3(a2, ld3(p2, j));
+    const V3 v = sub3(e1, mul_mv(Ri, e2));
+    sv.x += v.x; sv.y += v.y; sv.z += v.z;
+    m[0] += v.x * e2.x; m[1] += v.x * e2.y; m[2] += v.x * e2.z;
+    m[3] += v.y * e2.x; m[4] += v.y * e2.y; m[5] += v.y * e2.z;
+    m[6] += v.z * e2.x; m[7] += v.z * e2.y; m[8] += v.z * e2.z;
+  }
+  const float gi = 2.0f * g[i];
+  const V3 rt = mul_tv(Ri, sv);
+  V3 o1 = {gi * sv.x, gi * sv.y, gi * sv.z}, o2 = {-gi * rt.x, -gi * rt.y, -gi * rt.z};
+#pragma unroll
+  for (int q = 0; q < 9; ++q) gR[9 * (size_t)i + q] = -gi * m[q];
+  const uint32_t q0 = (uint32_t)rev_ranges[2 * (size_t)i], q1 = (uint32_t)rev_ranges[2 * (size_t)i + 1];
+  for (uint32_t q = q0; q < q1; ++q) {
+    const uint32_t src = (uint32_t)rev_edges[q] / k;
+    const V3 e1 = sub3(ld3(p1, src), a1), e2 = sub3(ld3(p2, src), a2);
+    const M3 Rs = ldm(R, src);
+    const V3 v = sub3(e1, mul_mv(Rs, e2));
+    const V3 w = mul_tv(Rs, v);
+    const float gs = 2.0f * g[src];
+    o1.x -= gs * v.x; o1.y -= gs * v.y; o1.z -= gs * v.z;
+    o2.x += gs * w.x; o2.y += gs * w.y; o2.z += gs * w.z;
+  }
+  g1[3 * (size_t)i] = o1.x; g1[3 * (size_t)i + 1] = o1.y; g1[3 * (size_t)i + 2] = o1.z;
+  g2[3 * (size_t)i] = o2.x; g2[3 * (size_t)i + 1] = o2.y; g2[3 * (size_t)i + 2] = o2.z;
+}
+
+// the size rules every entry point shares: N >= 0, 1 <= k, N * k < 2^31
+static int graph_dims_ok(const char* who, int32_t N, int32_t k) {
+  if (N < 0 || k < 1 || (int64_t)N * (int64_t)k >= ((int64_t)1 << 31)) {
+    set_error("%s: need N >= 0, k >= 1 and N * k < 2^31 (got N %d, k %d)", who, N, k);
+    return TRASE_ERR_INVALID;
+  }
+  return TRASE_OK;
+}
+static inline int blocks_of(uint32_t n) { return (int)((n + 255u) / 256u); }
+
+}  // namespace trase
+
+using namespace trase;
+
+extern "C" {
+
+int trase_graph_reverse_ws_bytes(int32_t N, int32_t k, size_t* ws_bytes) {
+  if (!ws_bytes) { set_error("trase_graph_reverse_ws_bytes: null pointer"); return TRASE_ERR_INVALID; }
+  if (int rc = graph_dims_ok("trase_graph_reverse_ws_bytes", N, k)) return rc;
+  RevWs w;
+  *ws_bytes = rev_layout(nullptr, N, k, w);
+  return TRASE_OK;
+}
+
+int trase_graph_reverse(const int32_t* idx, int32_t N, int32_t k, int32_t* rev_ranges, int32_t* rev_edges, void* ws,
+                        size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  if (int rc = graph_dims_ok("trase_graph_reverse", N, k)) return rc;
+  if (N == 0) return TRASE_OK;
+  if (!idx || !rev_ranges || !rev_edges) { set_error("trase_graph_reverse: null pointer"); return TRASE_ERR_INVALID; }
+  RevWs w;
+  if (!ws || ws_bytes < rev_layout(nullptr, N, k, w)) { set_error("trase_graph_reverse: workspace too small"); return TRASE_ERR_WORKSPACE; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  rev_layout(ws, N, k, w);
+  LaunchCtx c{stream, 0, 0};
+  const uint32_t M = (uint32_t)N * (uint32_t)k;
+  {
+    ProfScope ps("graph_rev_keys", stream);
+    hipLaunchKernelGGL(rev_keys_kernel, dim3(blocks_of(M)), dim3(256), 0, stream, idx, M, (uint32_t)N, w.sort.keys[0], w.n);
+  }
+  TRASE_POST_LAUNCH("graph_rev_keys", stream, 0);
+  int out = 0;
+  int rc = radix_sort_pairs(c, w.sort, w.n, M, 0, rev_bits(N), true, &out);
+  if (rc) return rc;
+  rc = launch_tile_ranges(c, w.sort.keys[out], w.n, M, w.ranges, N + 1);
+  if (rc) return rc;
+  {
+    ProfScope ps("graph_rev_finish", stream);
+    hipLaunchKernelGGL(rev_finish_kernel, dim3(blocks_of(M > (uint32_t)N ? M : (uint32_t)N)), dim3(256), 0, stream, w.sort.vals[out],
+                       w.ranges, M, (uint32_t)N, rev_edges, rev_ranges);
+  }
+  TRASE_POST_LAUNCH("graph_rev_finish", stream, 0);
+  return TRASE_OK;
+}
+
+static int f3_dims_ok(const char* who, int32_t N, int32_t D, int32_t k) {
+  if (int rc = graph_dims_ok(who, N, k)) return rc;
+  if (D < 1 || D > F3_MAX_D || (int64_t)N * (int64_t)D >= ((int64_t)1 << 31)) {
+    set_error("%s: need 1 <= D <= %d and N * D < 2^31 (got N %d, D %d)", who, F3_MAX_D, N, D);
+    return TRASE_ERR_INVALID;
+  }
+  return TRASE_OK;
+}
+
+int trase_feat3d_ws_bytes(int32_t N, int32_t D, size_t* ws_bytes) {
+  if (!ws_bytes) { set_error("trase_feat3d_ws_bytes: null pointer"); return TRASE_ERR_INVALID; }
+  if (int rc = f3_dims_ok("trase_feat3d_ws_bytes", N, D, 1)) return rc;
+  double* p;
+  *ws_bytes = array_layout<double>(nullptr, (size_t)blocks_of((uint32_t)N * (uint32_t)D) + 1, p);
+  return TRASE_OK;
+}
+
+int trase_feat3d_forward(const float* feats, const int32_t* idx, int32_t N, int32_t D, int32_t k, float* s_tab, float* l_tab,
+                         float* loss, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  if (int rc = f3_dims_ok("trase_feat3d_forward", N, D, k)) return rc;
+  if (N < 1) { set_error("trase_feat3d_forward: need N >= 1 (the mean of nothing)"); return TRASE_ERR_INVALID; }
+  if (!feats || !idx || !s_tab || !l_tab || !loss) { set_error("trase_feat3d_forward: null pointer"); return TRASE_ERR_INVALID; }
+  const uint32_t ND = (uint32_t)N * (uint32_t)D;
+  double* partial;
+  if (!ws || ws_bytes < array_layout<double>(nullptr, (size_t)blocks_of(ND) + 1, partial)) {
+    set_error("trase_feat3d_forward: workspace too small"); return TRASE_ERR_WORKSPACE;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  array_layout<double>(ws, (size_t)blocks_of(ND) + 1, partial);
+  {
+    ProfScope ps("feat3d_forward", stream);
+    hipLaunchKernelGGL(f3_table_kernel, dim3(blocks_of(ND)), dim3(256), 0, stream, feats, ND, s_tab, l_tab);
+    hipLaunchKernelGGL(f3_forward_kernel, dim3(blocks_of(ND)), dim3(256), 0, stream, s_tab, l_tab, idx, (uint32_t)N, (uint32_t)D,
+                       (uint32_t)k, partial);
+    hipLaunchKernelGGL(f3_reduce_kernel, dim3(1), dim3(256), 0, stream, partial, (uint32_t)blocks_of(ND),
+                       1.0 / ((double)N * (double)k * (double)D), loss);
+  }
+  TRASE_POST_LAUNCH("feat3d_forward", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_feat3d_backward(const float* s_tab, const float* l_tab, const int32_t* idx, const int32_t* rev_ranges,
+                          const int32_t* rev_edges, int32_t N, int32_t D, int32_t k, const float* g_loss, float* g_feats,
+                          int32_t device, trase_stream_t stream_) {
+  if (int rc = f3_dims_ok("trase_feat3d_backward", N, D, k)) return rc;
+  if (N == 0) return TRASE_OK;
+  if (!s_tab || !l_tab || !idx || !rev_ranges || !rev_edges || !g_loss || !g_feats) {
+    set_error("trase_feat3d_backward: null pointer"); return TRASE_ERR_INVALID;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  const uint32_t ND = (uint32_t)N * (uint32_t)D;
+  {
+    ProfScope ps("feat3d_backward", stream);
+    hipLaunchKernelGGL(f3_backward_kernel, dim3(blocks_of(ND)), dim3(256), 0, stream, s_tab, l_tab, idx, rev_ranges, rev_edges,
+                       (uint32_t)N, (uint32_t)D, (uint32_t)k, g_loss, (float)(1.0 / ((double)N * (double)k * (double)D)), g_feats);
+  }
+  TRASE_POST_LAUNCH("feat3d_backward", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_edge_moments_forward(const float* p1, const float* p2, const int32_t* idx, int32_t N, int32_t k, float* S,
+                               int32_t device, trase_stream_t stream_) {
+  if (int rc = graph_dims_ok("trase_edge_moments_forward", N, k)) return rc;
+  if (N == 0) return TRASE_OK;
+  if (!p1 || !p2 || !idx || !S) { set_error("trase_edge_moments_forward: null pointer"); return TRASE_ERR_INVALID; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    ProfScope ps("edge_moments_fwd", stream);
+    hipLaunchKernelGGL(edge_moments_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, idx, (uint32_t)N,
+                       (uint32_t)k, S);
+  }
+  TRASE_POST_LAUNCH("edge_moments_fwd", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_edge_moments_backward(const float* p1, const float* p2, const int32_t* idx, const int32_t* rev_ranges,
+                                const int32_t* rev_edges, int32_t N, int32_t k, const float* gS, float* g1, float* g2,
+                                int32_t device, trase_stream_t stream_) {
+  if (int rc = graph_dims_ok("trase_edge_moments_backward", N, k)) return rc;
+  if (N == 0) return TRASE_OK;
+  if (!p1 || !p2 || !idx || !rev_ranges || !rev_edges || !gS || !g1 || !g2) {
+    set_error("trase_edge_moments_backward: null pointer"); return TRASE_ERR_INVALID;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    ProfScope ps("edge_moments_bwd", stream);
+    hipLaunchKernelGGL(edge_moments_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, idx, rev_ranges,
+                       rev_edges, (uint32_t)N, (uint32_t)k, gS, g1, g2);
+  }
+  TRASE_POST_LAUNCH("edge_moments_bwd", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_edge_residual_forward(const float* p1, const float* p2, const int32_t* idx, const float* R, int32_t N, int32_t k,
+                                float* out, int32_t device, trase_stream_t stream_) {
+  if (int rc = graph_dims_ok("trase_edge_residual_forward", N, k)) return rc;
+  if (N == 0) return TRASE_OK;
+  if (!p1 || !p2 || !idx || !R || !out) { set_error("trase_edge_residual_forward: null pointer"); return TRASE_ERR_INVALID; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    ProfScope ps("edge_residual_fwd", stream);
+    hipLaunchKernelGGL(edge_residual_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, idx, R, (uint32_t)N,
+                       (uint32_t)k, out);
+  }
+  TRASE_POST_LAUNCH("edge_residual_fwd", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_edge_residual_backward(const float* p1, const float* p2, const int32_t* idx, const int32_t* rev_ranges,
+                                 const int32_t* rev_edges, const float* R, int32_t N, int32_t k, const float* g, float* g1,
+                                 float* g2, float* gR, int32_t device, trase_stream_t stream_) {
+  if (int rc = graph_dims_ok("trase_edge_residual_backward", N, k)) return rc;
+  if (N == 0) return TRASE_OK;
+  if (!p1 || !p2 || !idx || !rev_ranges || !rev_edges || !R || !g || !g1 || !g2 || !gR) {
+    set_error("trase_edge_residual_backward: null pointer"); return TRASE_ERR_INVALID;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    ProfScope ps("edge_residual_bwd", stream);
+    hipLaunchKernelGGL(edge_residual_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, idx, rev_ranges,
+                       rev_edges, R, (uint32_t)N, (uint32_t)k, g, g1, g2, gR);
+  }
+  TRASE_POST_LAUNCH("edge_residual_bwd", stream, 0);
+  return TRASE_OK;
+}
+
+}  // extern "C"

@@ -341,3 +341,7 @@ def loss_nnfm_style(feat1: torch.Tensor, feats2: torch.Tensor) -> torch.Tensor:
 
 
 _NNFM_WARNED = False
+
+
+# the two k-NN graph losses of utils/loss_utils.py (:132-152, :179-221) live in trase_amd/neighbors.py
+from .neighbors import loss_reg_3d_feature, loss_rigid_body_motion_reg_loss  # noqa: E402,F401

@@ -1,0 +1,255 @@
+"""Losses over a k-NN graph without N x k x ... edge tensors (trase_amd/csrc/neighbors.hip).
+
+The reference's ``loss_reg_3d_feature`` (utils/loss_utils.py:132-152) and ``loss_rigid_body_motion_reg_loss`` (:179-221) call
+``pytorch3d.ops.knn_points`` with k + 1 and 129 neighbours and then form ``feats[aux_ids]`` / ``p[aux_ids] - p[ijs]`` tensors of
+N x k rows, once more for autograd.  Here the graph is an (N, k) int32 index plus its transpose (``NeighborGraph``), the
+forward passes are gather-sums over ``idx`` and the backward passes gather over the transpose for the gradient that flows to
+the *neighbour* end of an edge -- no float atomics, so two calls give the same bits.
+
+``edge_moments`` and ``edge_residual`` are the two edge sums of the rigid loss; the 3 x 3 SVD between them stays
+``torch.svd`` with its own autograd, as in the reference."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .rasterizer import _bytes, _stream, knn_points
+
+MAX_FEATURE_DIM = 64
+
+
+def _dev_index(dev):
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def _need_gpu(t, what):
+    if t.device.type != "cuda":
+        raise RuntimeError(f"{what} runs on the GPU only (there is no CPU path)")
+
+
+class NeighborGraph:
+    """idx (N, k) int32 and its transpose: rev_edges (N * k) holds the edge numbers i * k + slot sorted by the row they point at,
+    ascending among the edges of one row; rev_ranges (N, 2) the [begin, end) positions of every row's incoming edges.  An id
+    outside [0, N) is an edge to nowhere: it is in no range and contributes to no sum."""
+
+    def __init__(self, idx, rev_ranges, rev_edges):
+        self.idx, self.rev_ranges, self.rev_edges = idx, rev_ranges, rev_edges
+
+    @property
+    def N(self):
+        return self.idx.shape[0]
+
+    @property
+    def k(self):
+        return self.idx.shape[1]
+
+    @classmethod
+    def from_idx(cls, idx: torch.Tensor) -> "NeighborGraph":
+        _need_gpu(idx, "NeighborGraph")
+        if idx.dim() != 2 or idx.shape[1] < 1:
+            raise ValueError("NeighborGraph: idx must be (N, k) with k >= 1")
+        N, k = idx.shape
+        if N * k >= 2 ** 31:
+            raise ValueError(f"NeighborGraph: need N * k < 2^31 (got N {N}, k {k})")
+        if idx.dtype != torch.int32:
+            big = torch.iinfo(torch.int32).max
+            idx = idx.detach().clamp(-1, big).to(torch.int32)       # what does not fit is out of range either way
+        idx = idx.detach().contiguous()
+        dev = idx.device
+        rev_ranges = torch.empty(N, 2, dtype=torch.int32, device=dev)
+        rev_edges = torch.empty(N * k, dtype=torch.int32, device=dev)
+        lib = _lib.load()
+        nbytes = C.c_size_t()
+        _lib.check(lib.trase_graph_reverse_ws_bytes(N, k, C.byref(nbytes)), "trase_graph_reverse_ws_bytes")
+        ws = _bytes(nbytes.value, dev)
+        _lib.check(lib.trase_graph_reverse(_lib.ptr(idx), N, k, _lib.ptr(rev_ranges), _lib.ptr(rev_edges), _lib.ptr(ws),
+                                           ws.numel(), _dev_index(dev), _stream(dev)), "trase_graph_reverse")
+        return cls(idx, rev_ranges, rev_edges)
+
+    @classmethod
+    def build(cls, points: torch.Tensor, k: int, *, drop_first: bool = True) -> "NeighborGraph":
+        """The self-k-NN of ``points`` (N, 3) with K = k + drop_first; drop_first removes column 0 as the reference's
+        ``[:, 1:]`` does (with coincident points column 0 is the lowest index among them, not necessarily the point itself)."""
+        _need_gpu(points, "NeighborGraph")
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("NeighborGraph.build expects points (N, 3)")
+        with torch.no_grad():
+            p = points.detach().unsqueeze(0)
+            idx = knn_points(p, p, K=int(k) + int(bool(drop_first))).idx[0]
+            if drop_first:
+                idx = idx[:, 1:]
+        return cls.from_idx(idx)
+
+
+def _f32(t):
+    return t.detach().float().contiguous()
+
+
+class _Feat3D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feats, graph):
+        lib = _lib.load()
+        dev = feats.device
+        N, D = feats.shape
+        f = _f32(feats)
+        s_tab, l_tab = torch.empty(N, D, device=dev), torch.empty(N, D, device=dev)
+        loss = torch.empty((), device=dev)
+        nbytes = C.c_size_t()
+        _lib.check(lib.trase_feat3d_ws_bytes(N, D, C.byref(nbytes)), "trase_feat3d_ws_bytes")
+        ws = _bytes(nbytes.value, dev)
+        _lib.check(lib.trase_feat3d_forward(_lib.ptr(f), _lib.ptr(graph.idx), N, D, graph.k, _lib.ptr(s_tab), _lib.ptr(l_tab),
+                                            _lib.ptr(loss), _lib.ptr(ws), ws.numel(), _dev_index(dev), _stream(dev)),
+                   "trase_feat3d_forward")
+        ctx.save_for_backward(s_tab, l_tab, graph.idx, graph.rev_ranges, graph.rev_edges)
+        ctx.meta = (N, D, graph.k, feats.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        lib = _lib.load()
+        s_tab, l_tab, idx, rev_ranges, rev_edges = ctx.saved_tensors
+        N, D, k, dtype = ctx.meta
+        dev = s_tab.device
+        g = _f32(g_loss).reshape(1)
+        g_f = torch.empty(N, D, device=dev)
+        _lib.check(lib.trase_feat3d_backward(_lib.ptr(s_tab), _lib.ptr(l_tab), _lib.ptr(idx), _lib.ptr(rev_ranges),
+                                             _lib.ptr(rev_edges), N, D, k, _lib.ptr(g), _lib.ptr(g_f), _dev_index(dev),
+                                             _stream(dev)), "trase_feat3d_backward")
+        return g_f.to(dtype), None
+
+
+def _check_graph(graph, n, what):
+    if not isinstance(graph, NeighborGraph):
+        raise TypeError(f"{what}: graph must be a NeighborGraph")
+    if graph.N != n:
+        raise ValueError(f"{what}: the graph has {graph.N} rows, the input {n}")
+
+
+def loss_reg_3d_feature(gaussian_feats, gaussian_xyz, k, max_points=-1, *, graph=None):
+    """utils/loss_utils.py:132-152: mean over (i, slot, d) of s_i (log(s_i + 1e-10) - log(s_j + 1e-10)), s = sigmoid(feats),
+    j the k nearest neighbours of i (column 0 of the k + 1 dropped).  The gradient goes to the features only.  ``graph``: a
+    NeighborGraph of the rows actually used (after ``max_points``), to skip the k-NN."""
+    _need_gpu(gaussian_feats, "loss_reg_3d_feature")
+    if gaussian_feats.dim() != 2 or not 1 <= gaussian_feats.shape[1] <= MAX_FEATURE_DIM:
+        raise ValueError(f"loss_reg_3d_feature: features must be (N, D) with 1 <= D <= {MAX_FEATURE_DIM}")
+    if gaussian_feats.size(0) > max_points and max_points != -1:
+        indices = torch.randperm(gaussian_feats.size(0))[:max_points].to(gaussian_feats.device)
+        feats, xyz = gaussian_feats[indices], gaussian_xyz[indices]
+    else:
+        feats, xyz = gaussian_feats, gaussian_xyz
+    if feats.shape[0] < 1:
+        raise ValueError("loss_reg_3d_feature: no points")
+    if graph is None:
+        graph = NeighborGraph.build(xyz, k)
+    _check_graph(graph, feats.shape[0], "loss_reg_3d_feature")
+    return _Feat3D.apply(feats, graph)
+
+
+class _EdgeMoments(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p1, p2, graph):
+        lib = _lib.load()
+        dev = p1.device
+        N = p1.shape[0]
+        a, b = _f32(p1), _f32(p2)
+        S = torch.empty(N, 3, 3, device=dev)
+        _lib.check(lib.trase_edge_moments_forward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(graph.idx), N, graph.k, _lib.ptr(S),
+                                                  _dev_index(dev), _stream(dev)), "trase_edge_moments_forward")
+        ctx.save_for_backward(a, b, graph.idx, graph.rev_ranges, graph.rev_edges)
+        ctx.meta = (N, graph.k, p1.dtype, p2.dtype)
+        return S
+
+    @staticmethod
+    def backward(ctx, gS):
+        lib = _lib.load()
+        a, b, idx, rev_ranges, rev_edges = ctx.saved_tensors
+        N, k, t1, t2 = ctx.meta
+        dev = a.device
+        g = _f32(gS)
+        g1, g2 = torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev)
+        _lib.check(lib.trase_edge_moments_backward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(idx), _lib.ptr(rev_ranges),
+                                                   _lib.ptr(rev_edges), N, k, _lib.ptr(g), _lib.ptr(g1), _lib.ptr(g2),
+                                                   _dev_index(dev), _stream(dev)), "trase_edge_moments_backward")
+        return g1.to(t1), g2.to(t2), None
+
+
+class _EdgeResidual(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p1, p2, R, graph):
+        lib = _lib.load()
+        dev = p1.device
+        N = p1.shape[0]
+        a, b, r = _f32(p1), _f32(p2), _f32(R)
+        out = torch.empty(N, device=dev)
+        _lib.check(lib.trase_edge_residual_forward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(graph.idx), _lib.ptr(r), N, graph.k,
+                                                   _lib.ptr(out), _dev_index(dev), _stream(dev)), "trase_edge_residual_forward")
+        ctx.save_for_backward(a, b, r, graph.idx, graph.rev_ranges, graph.rev_edges)
+        ctx.meta = (N, graph.k, p1.dtype, p2.dtype, R.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        lib = _lib.load()
+        a, b, r, idx, rev_ranges, rev_edges = ctx.saved_tensors
+        N, k, t1, t2, tr = ctx.meta
+        dev = a.device
+        g = _f32(g_out)
+        g1, g2, gR = torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 3, 3, device=dev)
+        _lib.check(lib.trase_edge_residual_backward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(idx), _lib.ptr(rev_ranges),
+                                                    _lib.ptr(rev_edges), _lib.ptr(r), N, k, _lib.ptr(g), _lib.ptr(g1),
+                                                    _lib.ptr(g2), _lib.ptr(gR), _dev_index(dev), _stream(dev)),
+                   "trase_edge_residual_backward")
+        return g1.to(t1), g2.to(t2), gR.to(tr), None
+
+
+def _check_points(p1, p2, what):
+    _need_gpu(p1, what)
+    if p1.dim() != 2 or p1.shape[1] != 3 or p2.shape != p1.shape or p2.device != p1.device:
+        raise ValueError(f"{what}: p1 and p2 must both be (N, 3) on one device")
+
+
+def edge_moments(p1, p2, graph):
+    """S (N, 3, 3) = sum over the slots of e1 e2^T with e = p[i] - p[idx[i, slot]]; differentiable in p1 and p2."""
+    _check_points(p1, p2, "edge_moments")
+    _check_graph(graph, p1.shape[0], "edge_moments")
+    return _EdgeMoments.apply(p1, p2, graph)
+
+
+def edge_residual(p1, p2, graph, R):
+    """(N,) sum over the slots of |e1 - R_i e2|^2; differentiable in p1, p2 and R (N, 3, 3)."""
+    _check_points(p1, p2, "edge_residual")
+    _check_graph(graph, p1.shape[0], "edge_residual")
+    if R.shape != (p1.shape[0], 3, 3) or R.device != p1.device:
+        raise ValueError("edge_residual: R must be (N, 3, 3) on the points' device")
+    return _EdgeResidual.apply(p1, p2, R, graph)
+
+
+def loss_rigid_body_motion_reg_loss(xyz1, xyz2, cluster_ids, num_neighbors=128, max_points=-1):
+    """utils/loss_utils.py:179-221: per cluster, the edges to the num_neighbors nearest points at time 1, the best rotation of
+    every point's edge set (SVD of the 3 x 3 moment matrix, R = V U^T) and the mean residual; summed over the clusters and
+    divided by their number.  A cluster with fewer points than num_neighbors + 1 gets the k-NN's padding (edges to row 0), as the
+    reference would.  One deviation: a cluster whose loss is NaN adds 0 on the device -- no host read, no print."""
+    _check_points(xyz1, xyz2, "loss_rigid_body_motion_reg_loss")
+    loss = 0
+    valid_cluster_ids = torch.unique(cluster_ids)
+    for cls in valid_cluster_ids:
+        sel = cluster_ids == cls
+        p1, p2 = xyz1[sel], xyz2[sel]
+        if max_points != -1 and p1.size(0) > max_points:
+            indices = torch.randperm(p1.size(0))[:max_points].to(p1.device)
+            p1, p2 = p1[indices], p2[indices]
+        graph = NeighborGraph.build(p1, num_neighbors)
+        S_i = edge_moments(p1, p2, graph)
+        U_i, _, V_i = torch.svd(S_i)
+        R_i = torch.bmm(V_i, U_i.transpose(1, 2))
+        loss_i = edge_residual(p1, p2, graph, R_i).mean()
+        bad = torch.isnan(loss_i.detach())
+        loss = loss + torch.where(bad, torch.zeros_like(loss_i), loss_i)
+        # the zero cotangent of a dropped cluster meets NaN on its way back (0 * NaN); the reference leaves such a cluster out
+        # of the autograd graph, so its rows get a zero gradient here too
+        for p in (p1, p2):
+            if p.requires_grad:
+                p.register_hook(lambda g, bad=bad: torch.where(bad, torch.zeros_like(g), g))
+    return loss / valid_cluster_ids.shape[0]
