@@ -8,12 +8,17 @@ render.py:334-345.
 * ``reseed_row``: cluster k empty in iteration i (from 0) takes row splitmix64(key ^ (i << 32 | k)) mod N.
 * ``query_mask``: the fp16 scoring of postprocessing -- rows and query normalised, both rounded to fp16, the dot product
   exact (float64 of fp16 operands) then rounded to fp32 and to fp16, compared with fp16(threshold).
+* ``lattice_rows`` / ``lattice_start`` / ``lattice_step``: one Lloyd step on small-integer rows, where fp32 is exact in any
+  order, so the device's ids and centres have one right answer bit for bit; ``SHAPE_PLAN`` lists the (K, D, N) at which
+  tests/test_gpu_segment_shapes.py takes that step, ``LOCKSTEP_CASES`` / ``BLOB_CASES`` the real-valued cases of the same file.
 * ``library_kmeans`` / ``render_masks_torch``: the library's own torch composition (an N x K x D broadcast per iteration,
   one ``nonzero`` per cluster) and the render.py loop as torch ops, for timing on the same device.
 
 A plain module (no HIP library): it runs on whatever device its tensors live on.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -141,6 +146,145 @@ def render_frames(features: torch.Tensor, ids: torch.Tensor, id_lists, threshold
                 normalised = True
         masks.append(mask)
     return masks
+
+
+# ---- one exact Lloyd step on an integer lattice ----------------------------------------------------------------------------
+#
+# Rows drawn from {-span..span}^D and start centres that are rows: every product, every partial sum of |c|^2 and x.c and
+# |c|^2 - 2 x.c is an integer of magnitude <= 3 * 64 * span^2 < 2^24, so the device's fp32 distances are exact and its argmin
+# is THE argmin, ties to the lowest k.  Every per-cluster sum is an integer of magnitude <= N * span < 2^24 (N <= 200 000,
+# span = 4), exact in fp32 whatever the order of the additions, and the count is too; sum / count is one correctly rounded
+# fp32 division.  Nothing is left to a tolerance but center_shift (a sum of square roots).
+
+def lattice_rows(n: int, d: int, seed: int, span: int = 4) -> torch.Tensor:
+    """(n, d) fp32 rows of integers drawn uniformly from {-span..span}."""
+    return torch.from_numpy(np.random.default_rng(seed).integers(-span, span + 1, (n, d)).astype(np.float32))
+
+
+class ShapeCase(NamedTuple):
+    K: int
+    D: int
+    N: int
+    dup: bool = False         # start centres K-1 and (K >= 4) 2 repeat centres 0 and 1: tie families, then empty clusters
+    offset: bool = False      # also run on a copy of X that starts 4 bytes into its storage (the scalar row loads)
+
+    @property
+    def id(self) -> str:
+        return f"K{self.K}-D{self.D}-N{self.N}" + ("-dup" if self.dup else "") + ("-offset" if self.offset else "")
+
+
+def _tail_cases():
+    # (K, D) with wacc = 3, 5, 6, 7 accumulating waves, i.e. sub-ranges of 171, 103, 86, 74 rows: one tile of a sub-range
+    # - 1, + 0, + 1 rows, and blocks of 512 + r rows (N = 256 (512 + r) - s: second tiles of r rows, r - s in the last block)
+    out = []
+    for K, D, per in ((128, 64, 171), (80, 64, 103), (72, 64, 86), (64, 64, 74)):
+        out += [ShapeCase(K, D, per + e) for e in (-1, 0, 1)]
+        out += [ShapeCase(K, D, 256 * 514 - 1), ShapeCase(K, D, 256 * 517 - 2)]
+    return out
+
+
+SHAPE_PLAN = [
+    # every D class and K class against the 512-row tile
+    ShapeCase(1, 1, 1), ShapeCase(2, 3, 511), ShapeCase(3, 4, 512, offset=True), ShapeCase(3, 8, 513), ShapeCase(2, 9, 1024),
+    ShapeCase(3, 12, 1025), ShapeCase(127, 16, 127), ShapeCase(3, 17, 16 * 512 + 1), ShapeCase(4, 20, 16 * 512),
+    ShapeCase(127, 31, 1025), ShapeCase(128, 32, 128, offset=True), ShapeCase(2, 33, 513), ShapeCase(3, 36, 511),
+    ShapeCase(127, 63, 512), ShapeCase(2, 64, 513, offset=True), ShapeCase(96, 64, 1024), ShapeCase(64, 64, 64),
+    # 256 blocks: one full tile each; a second tile of one row and a short last block; chunk = 782
+    ShapeCase(128, 64, 131072), ShapeCase(5, 8, 131073), ShapeCase(128, 64, 131073), ShapeCase(1, 64, 200_000),
+    ShapeCase(128, 8, 200_000),
+    # duplicate start centres in every padded width, and at K = 128
+    ShapeCase(8, 5, 600, dup=True), ShapeCase(16, 12, 700, dup=True), ShapeCase(9, 31, 1500, dup=True),
+    ShapeCase(128, 64, 1025, dup=True),
+] + _tail_cases()
+
+
+def lattice_start(X: torch.Tensor, case: ShapeCase) -> torch.Tensor:
+    """(K, D) start centres for a plan case: K distinct rows of X (all of them, permuted, when N == K), with the duplicates
+    ``case.dup`` asks for."""
+    g = np.random.default_rng(1000 * case.K + case.D)
+    C = X[torch.from_numpy(g.choice(case.N, case.K, replace=False))].clone()
+    if case.dup:
+        C[case.K - 1] = C[0]
+        if case.K >= 4:
+            C[2] = C[1]
+    return C
+
+
+def lattice_case(case: ShapeCase):
+    """-> (rows, start centres) of a plan case, on the CPU."""
+    X = lattice_rows(case.N, case.D, seed=1000 * case.D + case.K)
+    return X, lattice_start(X, case)
+
+
+def lattice_step(X: torch.Tensor, C: torch.Tensor, iteration: int, key: int):
+    """One Lloyd step from integer centres C on integer rows X, as fp32 arithmetic must give it whatever its order
+    -> (ids int64 (N,), new centres fp32 (K, D), empty bool (K,), center_shift in float64 of those fp32 centres).
+
+    The (N, K) scores |c_k|^2 - 2 x.c_k come from float64 matrix products in row chunks (exact on these integers)."""
+    x = X.cpu().double()
+    c = C.cpu().double()
+    N, K = x.shape[0], c.shape[0]
+    assert bool((x == x.round()).all()) and bool((c == c.round()).all()), "lattice_step: integer rows and centres only"
+    cc = (c * c).sum(1)
+    assert float(3 * torch.maximum((x * x).sum(1).max(), cc.max())) < 2 ** 24
+    ids = torch.empty(N, dtype=torch.int64)
+    for a in range(0, N, 1 << 16):
+        score = cc[None, :] - 2.0 * (x[a:a + (1 << 16)] @ c.T)
+        ids[a:a + score.shape[0]] = torch.from_numpy(np.argmin(score.numpy(), axis=1))      # the first of equal minima
+    sums = torch.zeros(K, x.shape[1], dtype=F64).index_add_(0, ids, x)
+    counts = torch.bincount(ids, minlength=K)
+    assert float(sums.abs().max()) < 2 ** 24 and N < 2 ** 24
+    empty = counts == 0
+    new = torch.from_numpy(sums.numpy().astype(np.float32) / np.maximum(counts.numpy(), 1).astype(np.float32)[:, None])
+    for k in torch.nonzero(empty).flatten().tolist():
+        new[k] = X.cpu()[reseed_row(key, iteration, k, N)]
+    shift = float(torch.sqrt(((new.double() - c) ** 2).sum(1)).sum())
+    return ids, new, empty, shift
+
+
+# ---- real-valued cases away from D = 32 -------------------------------------------------------------------------------------
+
+LOCKSTEP_N, LOCKSTEP_ITERS = 5000, 6
+LOCKSTEP_CASES = [(128, 64, True), (127, 63, True), (128, 8, True), (17, 5, True), (2, 3, True), (3, 1, False)]   # K, D, unit rows
+
+
+def lockstep_rows(K: int, D: int, unit: bool):
+    """-> (rows fp32 (LOCKSTEP_N, D) on the CPU, start row indices) of a lockstep case."""
+    x = torch.randn(LOCKSTEP_N, D, generator=torch.Generator().manual_seed(1000 * K + D))
+    if unit:
+        x = torch.nn.functional.normalize(x, dim=-1)
+    return x, init_indices(LOCKSTEP_N, K, seed=7)
+
+
+def near_tie_gap(X: torch.Tensor) -> float:
+    """The squared-distance gap below which the fp32 assignment may differ from the float64 one: the device forms
+    |c|^2 - 2 x.c from two D-term fmaf chains and one more fma, each with a relative error of at most D 2^-24 on terms
+    bounded by M^2 (M the largest row norm, which also bounds every centre); two such distances are compared:
+    8 (D + 1) 2^-24 M^2.  1.6e-5 for unit rows at D = 32."""
+    M = float(X.double().norm(dim=-1).max())
+    return 8.0 * (X.shape[1] + 1) * 2.0 ** -24 * M * M
+
+
+def near_tie_cap(n: int) -> int:
+    """Rows an iteration may leave out of the id comparison as near ties."""
+    return max(2, int(1e-3 * n))
+
+
+BLOB_N = 4000
+BLOB_CASES = [(5, 3, 0.05, 3), (128, 64, 0.05, 3)]        # K, D, noise, seed
+
+
+def blob_rows(n: int, k: int, d: int, noise: float, seed: int):
+    """n rows around k unit-norm blob centres; the start rows numpy will draw for ``seed`` lie in k distinct blobs
+    -> (rows fp32 on the CPU, blob labels, start row indices)."""
+    start = init_indices(n, k, seed)
+    g = np.random.default_rng(seed)
+    centres = g.standard_normal((k, d))
+    centres /= np.linalg.norm(centres, axis=1, keepdims=True)
+    labels = g.integers(0, k, n)
+    labels[start] = np.arange(k)
+    rows = centres[labels] + noise * g.standard_normal((n, d))
+    return torch.from_numpy(rows.astype(np.float32)), labels, start
 
 
 # ---- the library's torch composition, for timing ------------------------------------------------------------------------
