@@ -364,6 +364,22 @@ int trase_edge_residual_forward(const float* p1, const float* p2, const int32_t*
 int trase_edge_residual_backward(const float* p1, const float* p2, const int32_t* idx, const int32_t* rev_ranges,
                                  const int32_t* rev_edges, const float* R, int32_t N, int32_t k, const float* g, float* g1,
                                  float* g2, float* gR, int32_t device, trase_stream_t stream);
+/* The rotation between the two edge sums without leaving the device code (trase_amd/csrc/rigid_math.h).
+ * polar3: R (N,3,3) = V U^T of S (N,3,3) = U Sigma V^T, the orthogonal polar factor of S^T, det R = sign(det S) (+1 where det S
+ * evaluates to 0); a non-finite S gives a NaN R.  The backward takes the cotangent gR and writes gS: the closed form through
+ * (tr(H) I - H)^-1, H = R^T S^T, and ZERO for a degenerate row (sigma_2 + sigma_3 <= 12 * 2^-24 |S|_F).
+ * rigid_fit: out (N) = sum_slot |e1 - R[i] e2|^2 with R[i] = polar3(sum_slot e1 e2^T) in one launch; R is written too, and
+ * state (N, TRASE_RIGID_STATE_FLOATS) is what the backward reads: it takes the cotangent g (N) of out and writes g1, g2 (N,3),
+ * the gradient through the rotation included.  A row is degenerate there when sigma_2 + sigma_3 <= 4 (k + 2) 2^-24 sum_slot |e1| |e2|. */
+#define TRASE_RIGID_STATE_FLOATS 16
+int trase_polar3_forward(const float* S, int32_t N, float* R, int32_t device, trase_stream_t stream);
+int trase_polar3_backward(const float* S, const float* R, const float* gR, int32_t N, float* gS, int32_t device,
+                          trase_stream_t stream);
+int trase_rigid_fit_forward(const float* p1, const float* p2, const int32_t* idx, int32_t N, int32_t k, float* out, float* R,
+                            float* state, int32_t device, trase_stream_t stream);
+int trase_rigid_fit_backward(const float* p1, const float* p2, const int32_t* idx, const int32_t* rev_ranges,
+                             const int32_t* rev_edges, const float* R, const float* state, const float* g, int32_t N, int32_t k,
+                             float* g1, float* g2, int32_t device, trase_stream_t stream);
 
 /* Deformation MLP (utils/time_utils.py:60-131 DeformNetwork.forward, reached through
  * scene/deform_model.py:34-35 DeformModel.step at train.py:202-204, render.py:195, gui.py:965).

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRASE_RAST_LIB") or os.path.join(_HERE, "lib", "libtrase_rast.so")   # override: A/B builds
 
 c_float_p = C.POINTER(C.c_float)
+RIGID_STATE_FLOATS = 16     # TRASE_RIGID_STATE_FLOATS of include/trase_rast.h: floats per row between the rigid fit's two passes
 
 
 class RastSettings(C.Structure):
@@ -186,6 +187,12 @@ SYMBOLS = [
                                               C.c_int32, C.c_void_p]),
     ("trase_edge_residual_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_polar3_forward", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_polar3_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_rigid_fit_forward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_rigid_fit_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("trase_mlp_sizes", C.c_int, [C.POINTER(C.c_size_t)]),
     ("trase_mlp_forward", C.c_int, [C.POINTER(MlpWeights), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),

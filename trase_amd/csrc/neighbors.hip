@@ -8,6 +8,7 @@
 // each row walks its incoming edges in ascending edge order, so every sum has one fixed order and is bitwise reproducible.
 // An id outside [0, N) (a caller's own index tensor) is an edge to nowhere: it lands in no range and is never dereferenced.
 #include "common.h"
+#include "rigid_math.h"
 
 namespace trase {
 
@@ -263,6 +264,123 @@ __global__ __launch_bounds__(256) void edge_residual_bwd_kernel(const float* __r
   g2[3 * (size_t)i] = o2.x; g2[3 * (size_t)i + 1] = o2.y; g2[3 * (size_t)i + 2] = o2.z;
 }
 
+// ---- the rotation of a moment matrix and the fused rigid fit (rigid_math.h) -------------------------------------------------
+//   polar3:     R[i] = V U^T of S[i] = U Sigma V^T, and gS for a cotangent of R, one matrix per thread
+//   rigid_fit:  r[i] = sum_slot |e1 - R_i e2|^2 with R_i = polar3(S_i), S_i = sum_slot e1 e2^T, in one launch; the backward is one
+//               launch too.  With v = e1 - R e2, T = sum_slot v e2^T and Z = polar3_bwd(S, R, -2 T) (so d r / d S = Z):
+//                   d r / d e1 = 2 v + Z e2,      d r / d e2 = -2 R^T v + Z^T e1
+//               The forward keeps, per row, Z and the two sums of these over the row's own edges (RIGID_STATE floats); the
+//               backward scales them by g_i and gathers the incoming edges with R_src, Z_src and -g_src.
+__global__ __launch_bounds__(256) void polar3_fwd_kernel(const float* __restrict__ S, uint32_t N, float* __restrict__ R) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= N) return;
+  const M3 s = ldm(S, i);
+  M3 r;
+  polar3(s.m, r.m);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) R[9 * (size_t)i + q] = r.m[q];
+}
+
+__global__ __launch_bounds__(256) void polar3_bwd_kernel(const float* __restrict__ S, const float* __restrict__ R,
+                                                         const float* __restrict__ gR, uint32_t N, float* __restrict__ gS) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= N) return;
+  const M3 s = ldm(S, i), r = ldm(R, i), g = ldm(gR, i);
+  M3 o;
+  polar3_row_bwd(s.m, r.m, g.m, o.m);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) gS[9 * (size_t)i + q] = o.m[q];
+}
+
+constexpr int RIGID_STATE = TRASE_RIGID_STATE_FLOATS;      // Z (9), d r / d p1[i] and d r / d p2[i] over the own edges (3 + 3), 1 unused
+
+__global__ __launch_bounds__(256) void rigid_fit_fwd_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                            const int32_t* __restrict__ idx, uint32_t N, uint32_t k,
+                                                            float* __restrict__ out, float* __restrict__ R, float* __restrict__ state) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= N) return;
+  const V3 a1 = ld3(p1, i), a2 = ld3(p2, i);
+  // the first walk: edge_moments_fwd_kernel's statements in its order, and the edge scale of the degenerate rule beside them
+  float s[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float scale = 0.f;
+  for (uint32_t slot = 0; slot < k; ++slot) {
+    const uint32_t j = (uint32_t)idx[(size_t)i * k + slot];
+    if (j >= N) continue;
+    const V3 e1 = sub3(a1, ld3(p1, j)), e2 = sub3(a2, ld3(p2, j));
+    s[0] += e1.x * e2.x; s[1] += e1.x * e2.y; s[2] += e1.x * e2.z;
+    s[3] += e1.y * e2.x; s[4] += e1.y * e2.y; s[5] += e1.y * e2.z;
+    s[6] += e1.z * e2.x; s[7] += e1.z * e2.y; s[8] += e1.z * e2.z;
+    scale += sqrtf(e1.x * e1.x + e1.y * e1.y + e1.z * e1.z) * sqrtf(e2.x * e2.x + e2.y * e2.y + e2.z * e2.z);
+  }
+  M3 Ri;
+  const double s23 = polar3(s, Ri.m);
+  const bool degenerate = polar3_is_degenerate(s23, (double)k, (double)scale);
+  // the second walk (the edges are in L2 by now): edge_residual_fwd_kernel's statements, and the sums of the backward
+  float acc = 0.f;
+  V3 sv = {0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f};
+  float t[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (uint32_t slot = 0; slot < k; ++slot) {
+    const uint32_t j = (uint32_t)idx[(size_t)i * k + slot];
+    if (j >= N) continue;
+    const V3 e1 = sub3(a1, ld3(p1, j)), e2 = sub3(a2, ld3(p2, j));
+    const V3 v = sub3(e1, mul_mv(Ri, e2));
+    acc += v.x * v.x + v.y * v.y + v.z * v.z;
+    sv.x += v.x; sv.y += v.y; sv.z += v.z;
+    s1.x += e1.x; s1.y += e1.y; s1.z += e1.z;
+    s2.x += e2.x; s2.y += e2.y; s2.z += e2.z;
+    t[0] += v.x * e2.x; t[1] += v.x * e2.y; t[2] += v.x * e2.z;
+    t[3] += v.y * e2.x; t[4] += v.y * e2.y; t[5] += v.y * e2.z;
+    t[6] += v.z * e2.x; t[7] += v.z * e2.y; t[8] += v.z * e2.z;
+  }
+  M3 Z;
+  if (degenerate) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) Z.m[q] = 0.f;
+  } else {
+    float G[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) G[q] = -2.0f * t[q];
+    polar3_bwd(s, Ri.m, G, Z.m);
+  }
+  const V3 ze = mul_mv(Z, s2), zt = mul_tv(Z, s1), rt = mul_tv(Ri, sv);
+  out[i] = acc;
+  float* st = state + (size_t)RIGID_STATE * i;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) { R[9 * (size_t)i + q] = Ri.m[q]; st[q] = Z.m[q]; }
+  st[9] = 2.0f * sv.x + ze.x; st[10] = 2.0f * sv.y + ze.y; st[11] = 2.0f * sv.z + ze.z;
+  st[12] = zt.x - 2.0f * rt.x; st[13] = zt.y - 2.0f * rt.y; st[14] = zt.z - 2.0f * rt.z;
+  st[15] = 0.f;
+}
+
+__global__ __launch_bounds__(256) void rigid_fit_bwd_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                            const int32_t* __restrict__ rev_ranges, const int32_t* __restrict__ rev_edges,
+                                                            const float* __restrict__ R, const float* __restrict__ state,
+                                                            const float* __restrict__ g, uint32_t N, uint32_t k,
+                                                            float* __restrict__ g1, float* __restrict__ g2) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= N) return;
+  const V3 a1 = ld3(p1, i), a2 = ld3(p2, i);
+  const float* st = state + (size_t)RIGID_STATE * i;
+  const float gi = g[i];
+  V3 o1 = {gi * st[9], gi * st[10], gi * st[11]}, o2 = {gi * st[12], gi * st[13], gi * st[14]};
+  const uint32_t q0 = (uint32_t)rev_ranges[2 * (size_t)i], q1 = (uint32_t)rev_ranges[2 * (size_t)i + 1];
+  for (uint32_t q = q0; q < q1; ++q) {
+    const uint32_t src = (uint32_t)rev_edges[q] / k;
+    const V3 e1 = sub3(ld3(p1, src), a1), e2 = sub3(ld3(p2, src), a2);
+    const M3 Rs = ldm(R, src);
+    M3 Zs;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) Zs.m[c] = state[(size_t)RIGID_STATE * src + c];
+    const V3 v = sub3(e1, mul_mv(Rs, e2));
+    const V3 w = mul_tv(Rs, v), ze = mul_mv(Zs, e2), zt = mul_tv(Zs, e1);
+    const float gs = g[src];
+    o1.x -= gs * (2.0f * v.x + ze.x); o1.y -= gs * (2.0f * v.y + ze.y); o1.z -= gs * (2.0f * v.z + ze.z);
+    o2.x -= gs * (zt.x - 2.0f * w.x); o2.y -= gs * (zt.y - 2.0f * w.y); o2.z -= gs * (zt.z - 2.0f * w.z);
+  }
+  g1[3 * (size_t)i] = o1.x; g1[3 * (size_t)i + 1] = o1.y; g1[3 * (size_t)i + 2] = o1.z;
+  g2[3 * (size_t)i] = o2.x; g2[3 * (size_t)i + 1] = o2.y; g2[3 * (size_t)i + 2] = o2.z;
+}
+
 // the size rules every entry point shares: N >= 0, 1 <= k, N * k < 2^31
 static int graph_dims_ok(const char* who, int32_t N, int32_t k) {
   if (N < 0 || k < 1 || (int64_t)N * (int64_t)k >= ((int64_t)1 << 31)) {
@@ -447,6 +565,71 @@ int trase_edge_residual_backward(const float* p1, const float* p2, const int32_t
                        rev_edges, R, (uint32_t)N, (uint32_t)k, g, g1, g2, gR);
   }
   TRASE_POST_LAUNCH("edge_residual_bwd", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_polar3_forward(const float* S, int32_t N, float* R, int32_t device, trase_stream_t stream_) {
+  if (N < 0) { set_error("trase_polar3_forward: need N >= 0 (got %d)", N); return TRASE_ERR_INVALID; }
+  if (N == 0) return TRASE_OK;
+  if (!S || !R) { set_error("trase_polar3_forward: null pointer"); return TRASE_ERR_INVALID; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    ProfScope ps("polar3_fwd", stream);
+    hipLaunchKernelGGL(polar3_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, S, (uint32_t)N, R);
+  }
+  TRASE_POST_LAUNCH("polar3_fwd", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_polar3_backward(const float* S, const float* R, const float* gR, int32_t N, float* gS, int32_t device,
+                          trase_stream_t stream_) {
+  if (N < 0) { set_error("trase_polar3_backward: need N >= 0 (got %d)", N); return TRASE_ERR_INVALID; }
+  if (N == 0) return TRASE_OK;
+  if (!S || !R || !gR || !gS) { set_error("trase_polar3_backward: null pointer"); return TRASE_ERR_INVALID; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    ProfScope ps("polar3_bwd", stream);
+    hipLaunchKernelGGL(polar3_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, S, R, gR, (uint32_t)N, gS);
+  }
+  TRASE_POST_LAUNCH("polar3_bwd", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_rigid_fit_forward(const float* p1, const float* p2, const int32_t* idx, int32_t N, int32_t k, float* out, float* R,
+                            float* state, int32_t device, trase_stream_t stream_) {
+  if (int rc = graph_dims_ok("trase_rigid_fit_forward", N, k)) return rc;
+  if (N == 0) return TRASE_OK;
+  if (!p1 || !p2 || !idx || !out || !R || !state) { set_error("trase_rigid_fit_forward: null pointer"); return TRASE_ERR_INVALID; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    ProfScope ps("rigid_fit_fwd", stream);
+    hipLaunchKernelGGL(rigid_fit_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, idx, (uint32_t)N,
+                       (uint32_t)k, out, R, state);
+  }
+  TRASE_POST_LAUNCH("rigid_fit_fwd", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_rigid_fit_backward(const float* p1, const float* p2, const int32_t* idx, const int32_t* rev_ranges,
+                             const int32_t* rev_edges, const float* R, const float* state, const float* g, int32_t N, int32_t k,
+                             float* g1, float* g2, int32_t device, trase_stream_t stream_) {
+  if (int rc = graph_dims_ok("trase_rigid_fit_backward", N, k)) return rc;
+  if (N == 0) return TRASE_OK;
+  if (!p1 || !p2 || !idx || !rev_ranges || !rev_edges || !R || !state || !g || !g1 || !g2) {
+    set_error("trase_rigid_fit_backward: null pointer"); return TRASE_ERR_INVALID;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    // (the row's own edges come from the saved sums: idx is not walked)
+    ProfScope ps("rigid_fit_bwd", stream);
+    hipLaunchKernelGGL(rigid_fit_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, rev_ranges, rev_edges, R,
+                       state, g, (uint32_t)N, (uint32_t)k, g1, g2);
+  }
+  TRASE_POST_LAUNCH("rigid_fit_bwd", stream, 0);
   return TRASE_OK;
 }
 

@@ -344,4 +344,4 @@ _NNFM_WARNED = False
 
 
 # the two k-NN graph losses of utils/loss_utils.py (:132-152, :179-221) live in trase_amd/neighbors.py
-from .neighbors import loss_reg_3d_feature, loss_rigid_body_motion_reg_loss  # noqa: E402,F401
+from .neighbors import loss_reg_3d_feature, loss_rigid_body_motion_reg_loss, polar_rotation, rigid_fit  # noqa: E402,F401

@@ -6,8 +6,10 @@ N x k rows, once more for autograd.  Here the graph is an (N, k) int32 index plu
 forward passes are gather-sums over ``idx`` and the backward passes gather over the transpose for the gradient that flows to
 the *neighbour* end of an edge -- no float atomics, so two calls give the same bits.
 
-``edge_moments`` and ``edge_residual`` are the two edge sums of the rigid loss; the 3 x 3 SVD between them stays
-``torch.svd`` with its own autograd, as in the reference."""
+``edge_moments`` and ``edge_residual`` are the two edge sums of the rigid loss; by default the 3 x 3 SVD between them stays
+``torch.svd`` with its own autograd, as in the reference.  ``polar_rotation`` is that rotation as a kernel with its closed-form
+gradient (trase_amd/csrc/rigid_math.h), ``rigid_fit`` the three steps in one launch each way, and
+``loss_rigid_body_motion_reg_loss(..., rotation="polar")`` the loss over it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -226,11 +228,92 @@ def edge_residual(p1, p2, graph, R):
     return _EdgeResidual.apply(p1, p2, R, graph)
 
 
-def loss_rigid_body_motion_reg_loss(xyz1, xyz2, cluster_ids, num_neighbors=128, max_points=-1):
+class _PolarRotation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, S):
+        lib = _lib.load()
+        dev = S.device
+        N = S.shape[0]
+        s = _f32(S)
+        R = torch.empty(N, 3, 3, device=dev)
+        _lib.check(lib.trase_polar3_forward(_lib.ptr(s), N, _lib.ptr(R), _dev_index(dev), _stream(dev)), "trase_polar3_forward")
+        ctx.save_for_backward(s, R)
+        ctx.dtype = S.dtype
+        return R
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gR):
+        lib = _lib.load()
+        s, R = ctx.saved_tensors
+        N = s.shape[0]
+        dev = s.device
+        g = _f32(gR)
+        gS = torch.empty(N, 3, 3, device=dev)
+        _lib.check(lib.trase_polar3_backward(_lib.ptr(s), _lib.ptr(R), _lib.ptr(g), N, _lib.ptr(gS), _dev_index(dev), _stream(dev)),
+                   "trase_polar3_backward")
+        return gS.to(ctx.dtype)
+
+
+def polar_rotation(S):
+    """R (N, 3, 3) = V U^T of S (N, 3, 3) = U Sigma V^T: the orthogonal polar factor of S^T, det R = sign(det S), +1 where det S
+    evaluates to 0; a non-finite S gives a NaN R.  Differentiable once, in closed form with the denominators sigma_j + sigma_k
+    only; a degenerate row (sigma_2 + sigma_3 <= 12 * 2^-24 |S|_F) gets a zero gradient.  Double backward raises."""
+    _need_gpu(S, "polar_rotation")
+    if S.dim() != 3 or S.shape[1:] != (3, 3):
+        raise ValueError("polar_rotation: S must be (N, 3, 3)")
+    return _PolarRotation.apply(S)
+
+
+class _RigidFit(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p1, p2, graph):
+        lib = _lib.load()
+        dev = p1.device
+        N = p1.shape[0]
+        a, b = _f32(p1), _f32(p2)
+        out, R = torch.empty(N, device=dev), torch.empty(N, 3, 3, device=dev)
+        state = torch.empty(N, _lib.RIGID_STATE_FLOATS, device=dev)
+        _lib.check(lib.trase_rigid_fit_forward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(graph.idx), N, graph.k, _lib.ptr(out), _lib.ptr(R),
+                                               _lib.ptr(state), _dev_index(dev), _stream(dev)), "trase_rigid_fit_forward")
+        ctx.save_for_backward(a, b, R, state, graph.idx, graph.rev_ranges, graph.rev_edges)
+        ctx.meta = (N, graph.k, p1.dtype, p2.dtype)
+        ctx.mark_non_differentiable(R)
+        return out, R
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, _g_R):
+        lib = _lib.load()
+        a, b, R, state, idx, rev_ranges, rev_edges = ctx.saved_tensors
+        N, k, t1, t2 = ctx.meta
+        dev = a.device
+        g = _f32(g_out)
+        g1, g2 = torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev)
+        _lib.check(lib.trase_rigid_fit_backward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(idx), _lib.ptr(rev_ranges), _lib.ptr(rev_edges),
+                                                _lib.ptr(R), _lib.ptr(state), _lib.ptr(g), N, k, _lib.ptr(g1), _lib.ptr(g2),
+                                                _dev_index(dev), _stream(dev)), "trase_rigid_fit_backward")
+        return g1.to(t1), g2.to(t2), None
+
+
+def rigid_fit(p1, p2, graph, *, return_rotation=False):
+    """(N,) sum over the slots of |e1 - R_i e2|^2 with R_i = polar_rotation(edge_moments(p1, p2, graph))_i, in one launch;
+    differentiable (once) in p1 and p2, the dependence of R_i on them included.  return_rotation: also R (N, 3, 3), detached."""
+    _check_points(p1, p2, "rigid_fit")
+    _check_graph(graph, p1.shape[0], "rigid_fit")
+    out, R = _RigidFit.apply(p1, p2, graph)
+    return (out, R) if return_rotation else out
+
+
+def loss_rigid_body_motion_reg_loss(xyz1, xyz2, cluster_ids, num_neighbors=128, max_points=-1, *, rotation="svd"):
     """utils/loss_utils.py:179-221: per cluster, the edges to the num_neighbors nearest points at time 1, the best rotation of
     every point's edge set (SVD of the 3 x 3 moment matrix, R = V U^T) and the mean residual; summed over the clusters and
     divided by their number.  A cluster with fewer points than num_neighbors + 1 gets the k-NN's padding (edges to row 0), as the
-    reference would.  One deviation: a cluster whose loss is NaN adds 0 on the device -- no host read, no print."""
+    reference would.  One deviation: a cluster whose loss is NaN adds 0 on the device -- no host read, no print.
+    rotation: "svd" (the default) is torch.svd and its autograd between the two edge kernels, as the reference has it; "polar"
+    is ``rigid_fit``: the same rotation in the kernel with its closed-form gradient, which needs no gap between singular values."""
+    if rotation not in ("svd", "polar"):
+        raise ValueError(f"loss_rigid_body_motion_reg_loss: rotation must be 'svd' or 'polar' (got {rotation!r})")
     _check_points(xyz1, xyz2, "loss_rigid_body_motion_reg_loss")
     loss = 0
     valid_cluster_ids = torch.unique(cluster_ids)
@@ -241,10 +324,13 @@ def loss_rigid_body_motion_reg_loss(xyz1, xyz2, cluster_ids, num_neighbors=128, 
             indices = torch.randperm(p1.size(0))[:max_points].to(p1.device)
             p1, p2 = p1[indices], p2[indices]
         graph = NeighborGraph.build(p1, num_neighbors)
-        S_i = edge_moments(p1, p2, graph)
-        U_i, _, V_i = torch.svd(S_i)
-        R_i = torch.bmm(V_i, U_i.transpose(1, 2))
-        loss_i = edge_residual(p1, p2, graph, R_i).mean()
+        if rotation == "polar":
+            loss_i = rigid_fit(p1, p2, graph).mean()
+        else:
+            S_i = edge_moments(p1, p2, graph)
+            U_i, _, V_i = torch.svd(S_i)
+            R_i = torch.bmm(V_i, U_i.transpose(1, 2))
+            loss_i = edge_residual(p1, p2, graph, R_i).mean()
         bad = torch.isnan(loss_i.detach())
         loss = loss + torch.where(bad, torch.zeros_like(loss_i), loss_i)
         # the zero cotangent of a dropped cluster meets NaN on its way back (0 * NaN); the reference leaves such a cluster out
