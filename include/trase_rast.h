@@ -1024,6 +1024,36 @@ int trase_present_frame(const float* image, int32_t h, int32_t w, int32_t depth,
                         const float* overlay, const float* tint, float tint_weight, float* out, int32_t* minmax, int32_t device,
                         trase_stream_t stream);
 
+/* ---- VGG16 feature extractor of the style-transfer loop (style_transfer/fx.py; train_style_transfer_nnfm.py:141-215) ----
+ * The 3x3 convolutions conv1_1 conv1_2 | conv2_1 conv2_2 | conv3_1 conv3_2 conv3_3 | conv4_1 (| = MaxPool2d(2, 2)), batch 1.
+ * `layers` = k in 1..8 cuts the network behind its k-th convolution and returns that convolution's output BEFORE its ReLU:
+ * out (C, h * w) fp32 planar, C = 64 64 128 128 256 256 256 512, h = H >> p, w = W >> p behind p pools.  H, W >= 2^p,
+ * H * W < 2^25.  image: (3, H, W) fp32 planes, never modified; mean / inv_std: HOST arrays of 3 floats (both NULL: no
+ * normalisation): conv1_1 reads (x - mean) * inv_std, the backward multiplies the image gradient by inv_std.
+ * Arithmetic: conv1_1 and its gradient in fp32; every other product as bf16x3 (operands split into hi + lo bf16, hi.hi +
+ * hi.lo + lo.hi on the matrix cores into an fp32 accumulator that starts at the bias).  No atomics: bitwise reproducible, and a
+ * cut at k gives the bits of layers 1..k of a deeper cut.
+ * trase_vgg_ws_bytes: the bytes of the pack, of the forward's and the backward's workspace and of the saved decisions, and the
+ *   output shape, each from the one walk that also carves the buffer.
+ * trase_vgg_pack: weights[l] (Cout, Cin, 3, 3) and biases[l] (Cout) fp32 device tensors of layer l = 0 .. layers - 1 (HOST
+ *   arrays of pointers) -> `pack`; once per weight set.  A pack of more layers serves every shorter cut.
+ * trase_vgg_forward: `saved` (optional) receives the decisions the backward needs: 1 bit per convolution output (z > 0), 4 bits
+ *   per pooled unit where a pool follows (window position in ATen's scan order -- rows, then columns, update on strict > -- and
+ *   whether the maximum was positive).  With saved == NULL nothing is kept.  ws: ws_forward_bytes.
+ * trase_vgg_backward: d_out (C, h * w) -> d_image (3, H, W), the weights being constants.  ws: ws_backward_bytes.
+ * Refusals: TRASE_ERR_INVALID (layers, sizes, null pointers, pack / saved / ws not 16-byte aligned) and TRASE_ERR_WORKSPACE
+ * (pack, saved or ws too small), with a message, before a device is touched. */
+int trase_vgg_ws_bytes(int32_t layers, int32_t H, int32_t W, size_t* pack_bytes, size_t* ws_forward_bytes, size_t* ws_backward_bytes,
+                    size_t* saved_bytes, int32_t* C, int32_t* h, int32_t* w);
+int trase_vgg_pack(int32_t layers, const float* const* weights, const float* const* biases, void* pack, size_t pack_bytes,
+                   int32_t device, trase_stream_t stream);
+int trase_vgg_forward(int32_t layers, const void* pack, size_t pack_bytes, const float* image, int32_t H, int32_t W,
+                      const float* mean, const float* inv_std, float* out, void* saved, size_t saved_bytes, void* ws,
+                      size_t ws_bytes, int32_t device, trase_stream_t stream);
+int trase_vgg_backward(int32_t layers, const void* pack, size_t pack_bytes, const float* d_out, int32_t H, int32_t W,
+                       const float* inv_std, const void* saved, size_t saved_bytes, float* d_image, void* ws, size_t ws_bytes,
+                       int32_t device, trase_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

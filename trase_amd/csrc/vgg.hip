@@ -1,0 +1,614 @@
+// vgg.hip -- the style-transfer feature extractor: VGG16's 3x3 convolutions up to conv4_1, forward and gradient to the image
+// (trase_vgg_ws_bytes / _pack / _forward / _backward; trase_amd/vgg.py).
+//
+// Network: conv1_1 conv1_2 | conv2_1 conv2_2 | conv3_1 conv3_2 conv3_3 | conv4_1 (| = MaxPool2d(2, 2), floor), 3x3, stride 1,
+// zero padding 1, bias, ReLU after each but the returned one; channels 3 -> 64 -> 64 -> 128 -> 128 -> 256 -> 256 -> 256 -> 512.
+// `layers` = k in 1..8 cuts the network behind its k-th convolution, whose output BEFORE the ReLU is returned as fp32 (C, h*w).
+//
+// Arithmetic (mlp_split.hip's): every matrix operand v -- activations, weights, cotangents -- is hi = bf16(v), lo = bf16(v - hi);
+// a product is lo.hi + hi.lo + hi.hi, three v_mfma_f32_32x32x16_bf16 into one fp32 accumulator that starts at the bias.  The
+// 3-channel ends (conv1_1 and its gradient to the image) are fp32 VALU kernels with the normalisation fused in.
+//
+// Organisation: implicit GEMM, no im2col.  Between layers an activation is two channel-last planes [pixel][C] (hi, lo), so a
+// lane's operand fragment -- 8 consecutive channels of one pixel at one tap -- is one 16-byte load.  K = 9 Cin is tap-major: a
+// K-step of 16 stays inside one tap (Cin is a multiple of 64), an out-of-image tap is a zero fragment.
+//   * a WORKGROUP (4 waves) owns a VG_TILE x VG_TILE = 16 x 16 pixel tile and 64 output channels (blockIdx.y); wave w owns the
+//     tile's rows 4 w .. 4 w + 3 as two MFMA column groups of 32 pixels (2 rows x 16) and both 32-channel blocks: 64 accumulators;
+//   * weights are a stream of K-step slabs [ks][hi|lo][k/8][n][k%8] written once per weight set by the pack kernel, forward and
+//     backward: the backward stream holds the spatially flipped weights with Cin and Cout exchanged, so the gradient to a
+//     layer's input is this same kernel run on the cotangent;
+//   * per K-step a wave loads 4 activation and 4 weight fragments (global, one K-step ahead of their use) for 12 MFMAs;
+//   * the accumulator layout (lane (m, h), register 4 q + j <-> channel 8 q + 4 h + j of pixel m) puts the four pixels of a 2x2
+//     pool window into lanes m, m^1, m^16, m^17: the pool is fused into the epilogue (ATen's rule: scan in (row, column) order,
+//     update on strict >).
+// Saved for the backward: 1 bit per convolution output (z > 0) as uint16 [pixel][C/16], or, where a pool follows, 4 bits per
+// POOLED unit (window position, maximum > 0) as uint64 [pooled pixel][C/16]; bit / nibble vg_bit(c) of word vg_group(c).
+// No atomics: two calls give the same bits.
+#include "common.h"
+#include "mlp_enc.h"
+
+namespace trase {
+
+constexpr int VG_LAYERS = 8;
+constexpr int VG_TILE = 16;                                       // pixels per side of a workgroup's tile
+constexpr int VG_NB = 64;                                         // output channels per workgroup
+__host__ __device__ constexpr int vg_chan(int l) { return l == 0 ? 3 : l <= 2 ? 64 : l <= 4 ? 128 : l <= 7 ? 256 : 512; }   // channels behind layer l
+__host__ __device__ constexpr int vg_shift(int l) { return l <= 2 ? 0 : l <= 4 ? 1 : l <= 7 ? 2 : 3; }                    // pools in front of layer l
+__host__ __device__ constexpr bool vg_pooled(int l) { return l == 2 || l == 4 || l == 7; }                                // a pool follows layer l
+__host__ __device__ __forceinline__ int vg_group(int c) { return (c >> 5) * 2 + ((c >> 2) & 1); }
+__host__ __device__ __forceinline__ int vg_bit(int c) { return ((c >> 3) & 3) * 4 + (c & 3); }
+
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void vg_split(float v, __bf16& hi, __bf16& lo) {
+  hi = (__bf16)v;
+  lo = (__bf16)(v - (float)hi);
+}
+
+// ---- pack ------------------------------------------------------------------------------------------------------------------
+// one thread per weight element of one stream of one layer: [ks][hi|lo][k/8][n][k%8], ks = tap * (K / 16) + channel step
+__global__ __launch_bounds__(256) void vgg_pack_kernel(const float* __restrict__ w, int Cin, int Cout, int backward,
+                                                       __bf16* __restrict__ stream) {
+  const int K = backward ? Cout : Cin, N = backward ? Cin : Cout;       // the stream's contraction and output widths
+  const int plane = 2 * N * 8;
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t total = (size_t)9 * (K / 16) * plane;
+  if (idx >= total) return;
+  const int ks = (int)(idx / plane), r = (int)(idx % plane), h = r / (N * 8), n = (r >> 3) % N, e = r & 7;
+  const int tap = ks / (K / 16), c = (ks % (K / 16)) * 16 + 8 * h + e, ky = tap / 3, kx = tap % 3;
+  const float v = backward ? w[(((size_t)c * Cin + n) * 3 + (2 - ky)) * 3 + (2 - kx)]
+                           : w[(((size_t)n * Cin + c) * 3 + ky) * 3 + kx];
+  __bf16 hi, lo;
+  vg_split(v, hi, lo);
+  __bf16* o = stream + (size_t)ks * 2 * plane + r;
+  o[0] = hi; o[plane] = lo;
+}
+
+__global__ __launch_bounds__(256) void vgg_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] = src[i];
+}
+
+// ---- conv1_1: fp32, normalisation fused into the load -------------------------------------------------------------------
+struct VgNorm { float mean[3]; float inv_std[3]; };
+
+template <bool FINAL>
+__global__ __launch_bounds__(256) void vgg_conv1_kernel(const float* __restrict__ img, int H, int W, VgNorm nm,
+                                                        const float* __restrict__ w1, const float* __restrict__ b1,
+                                                        __bf16* __restrict__ out_hi, __bf16* __restrict__ out_lo,
+                                                        float* __restrict__ out_f32, uint16_t* __restrict__ relu_bits) {
+  __shared__ float s_w[64 * 27 + 64];
+  for (int i = threadIdx.x; i < 64 * 27; i += 256) s_w[i] = w1[i];
+  if (threadIdx.x < 64) s_w[64 * 27 + threadIdx.x] = b1[threadIdx.x];
+  __syncthreads();
+  const int HW = H * W;
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= HW) return;
+  const int y = pix / W, x = pix - y * W;
+  float v[27];
+#pragma unroll
+  for (int ci = 0; ci < 3; ++ci)
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int yy = y + ky - 1, xx = x + kx - 1;
+        float t = 0.f;
+        if (yy >= 0 && yy < H && xx >= 0 && xx < W) t = (img[(size_t)ci * HW + (size_t)yy * W + xx] - nm.mean[ci]) * nm.inv_std[ci];
+        v[ci * 9 + ky * 3 + kx] = t;
+      }
+  uint32_t bits[4] = {0u, 0u, 0u, 0u};
+  for (int c4 = 0; c4 < 64; c4 += 4) {
+    bf16x4 vh, vl;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = c4 + j;
+      float z = s_w[64 * 27 + c];
+#pragma unroll
+      for (int i = 0; i < 27; ++i) z = fmaf(v[i], s_w[c * 27 + i], z);
+      if (FINAL) {
+        out_f32[(size_t)c * HW + pix] = z;
+      } else {
+        if (z > 0.f) bits[vg_group(c)] |= 1u << vg_bit(c);
+        __bf16 a, b;
+        vg_split(fmaxf(z, 0.f), a, b);
+        vh[j] = a; vl[j] = b;
+      }
+    }
+    if (!FINAL) {
+      *reinterpret_cast<bf16x4*>(out_hi + (size_t)pix * 64 + c4) = vh;
+      *reinterpret_cast<bf16x4*>(out_lo + (size_t)pix * 64 + c4) = vl;
+    }
+  }
+  if (!FINAL && relu_bits) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) relu_bits[(size_t)pix * 4 + g] = (uint16_t)bits[g];
+  }
+}
+
+// gradient to the image: the transposed conv1_1 on the (masked) cotangent of its output, times 1 / std.  A workgroup owns
+// 16 x 16 pixels; EIGHT lanes share a pixel, lane c of them owning channels 8 c .. 8 c + 7, so a load instruction reads eight
+// pixels' whole 128-byte rows (one pixel per lane reads 16 bytes of 64 different lines per instruction and thrashes L1: 4.9 ms
+// at 1080p).  The eight partial sums meet in a fixed butterfly.  Weights: w1t[tap][co] = (w[co][0..2][tap], 0), from LDS.
+__global__ __launch_bounds__(256) void vgg_image_grad_kernel(const __bf16* __restrict__ g_hi, const __bf16* __restrict__ g_lo, int H,
+                                                             int W, VgNorm nm, const float4* __restrict__ w1t, float* __restrict__ d_img) {
+  __shared__ float4 s_w[9 * 64];
+  for (int i = threadIdx.x; i < 9 * 64; i += 256) s_w[i] = w1t[i];
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, cg = lane & 7, sub = lane >> 3;
+  const size_t HW = (size_t)H * W;
+  for (int i = 0; i < 8; ++i) {                     // the wave's 4 rows x 16 columns, eight pixels at a time
+    const int y = blockIdx.y * 16 + wave * 4 + (i >> 1), x = blockIdx.x * 16 + (i & 1) * 8 + sub;
+    float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      const int ky = tap / 3, kx = tap - 3 * ky;
+      const int yy = y - ky + 1, xx = x - kx + 1;
+      const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;           // outside: the nearest pixel is read and not used
+      const size_t o = ((size_t)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)) * 64 + 8 * cg;
+      const bf16x8 vh = *reinterpret_cast<const bf16x8*>(g_hi + o), vl = *reinterpret_cast<const bf16x8*>(g_lo + o);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float gv = ok ? (float)vh[e] + (float)vl[e] : 0.f;
+        const float4 wv = s_w[tap * 64 + 8 * cg + e];
+        d0 = fmaf(gv, wv.x, d0); d1 = fmaf(gv, wv.y, d1); d2 = fmaf(gv, wv.z, d2);
+      }
+    }
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) { d0 += __shfl_xor(d0, off); d1 += __shfl_xor(d1, off); d2 += __shfl_xor(d2, off); }
+    if (x < W && y < H && cg < 3) {
+      const float d = cg == 0 ? d0 * nm.inv_std[0] : cg == 1 ? d1 * nm.inv_std[1] : d2 * nm.inv_std[2];
+      d_img[cg * HW + (size_t)y * W + x] = d;
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void vgg_w1t_kernel(const float* __restrict__ w1, float4* __restrict__ w1t) {
+  const int tap = blockIdx.x, co = threadIdx.x;
+  w1t[tap * 64 + co] = make_float4(w1[co * 27 + tap], w1[co * 27 + 9 + tap], w1[co * 27 + 18 + tap], 0.f);
+}
+
+// the cotangent of the returned layer, fp32 planar (C, HW) -> split channel-last planes
+__global__ __launch_bounds__(256) void vgg_cot_split_kernel(const float* __restrict__ g, int C, int HW, __bf16* __restrict__ o_hi,
+                                                            __bf16* __restrict__ o_lo) {
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const int c8 = blockIdx.y * 8;
+  if (pix >= HW) return;
+  bf16x8 vh, vl;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    __bf16 a, b;
+    vg_split(g[(size_t)(c8 + e) * HW + pix], a, b);
+    vh[e] = a; vl[e] = b;
+  }
+  *reinterpret_cast<bf16x8*>(o_hi + (size_t)pix * C + c8) = vh;
+  *reinterpret_cast<bf16x8*>(o_lo + (size_t)pix * C + c8) = vl;
+}
+
+// ---- the MFMA convolution ---------------------------------------------------------------------------------------------------
+enum { VG_FWD_RELU = 0, VG_FWD_POOL = 1, VG_FWD_OUT = 2, VG_BWD_MASK = 3, VG_BWD_UNPOOL = 4 };
+
+struct VgConv {
+  const __bf16* in_hi; const __bf16* in_lo;      // [H * W][Cin]
+  const __bf16* stream;                          // [9 Cin / 16][hi|lo][2][Cout][8]
+  const float* bias;                             // (Cout) or null (backward)
+  int H, W, Cin, Cout, lg_steps;                 // lg_steps = log2(Cin / 16)
+  __bf16* out_hi; __bf16* out_lo;                // channel-last [pixels][Cout]: (H, W); POOL: (H/2, W/2); UNPOOL: (out_H, out_W)
+  float* out_f32;                                // FWD_OUT: (Cout, H * W)
+  uint16_t* relu_bits;                           // FWD_RELU writes (null: nothing is kept), BWD_MASK reads: [H * W][Cout / 16]
+  uint64_t* pool_codes;                          // FWD_POOL writes (or null), BWD_UNPOOL reads: [pooled pixels][Cout / 16]
+  int out_H, out_W;                              // BWD_UNPOOL: the full-resolution plane the windows scatter into
+};
+
+template <int EPI>
+__global__ __launch_bounds__(256) void vgg_conv_kernel(VgConv a) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int m = lane & 31, h = lane >> 5;
+  const int ntx = (a.W + VG_TILE - 1) / VG_TILE;
+  const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
+  const int cb = blockIdx.y;
+  const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
+  int py[2], px[2];
+#pragma unroll
+  for (int rg = 0; rg < 2; ++rg) {
+    py[rg] = ty * VG_TILE + wave * 4 + rg * 2 + (m >> 4);
+    px[rg] = tx * VG_TILE + (m & 15);
+  }
+  const int steps = 1 << a.lg_steps, KS = 9 * steps;
+  const int plane = 2 * Cout * 8;
+  const __bf16* const gw = a.stream + h * (Cout * 8) + (size_t)(cb * VG_NB + m) * 8;
+
+  // fragments of K-step ks: activations f[rg * 2 + hl], weights f[4 + nb * 2 + hl]; a pixel outside the image reads the
+  // nearest inside one (never stored), a tap outside the image is zeros
+  auto fetch = [&](int ks, bf16x8 (&f)[8]) {
+    ks = min(ks, KS - 1);
+    const int tap = ks >> a.lg_steps, c0 = (ks & (steps - 1)) * 16;
+    const int ky = (tap * 11) >> 5, dy = ky - 1, dx = tap - 3 * ky - 1;
+#pragma unroll
+    for (int rg = 0; rg < 2; ++rg) {
+      const int yy = py[rg] + dy, xx = px[rg] + dx;
+      const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
+      const int cy = min(max(yy, 0), H - 1), cx = min(max(xx, 0), W - 1);
+      const size_t o = ((size_t)cy * W + cx) * Cin + c0 + 8 * h;
+      bf16x8 vh = *reinterpret_cast<const bf16x8*>(a.in_hi + o), vl = *reinterpret_cast<const bf16x8*>(a.in_lo + o);
+      if (!ok) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { vh[e] = (__bf16)0.f; vl[e] = (__bf16)0.f; }
+      }
+      f[rg * 2] = vh; f[rg * 2 + 1] = vl;
+    }
+    const __bf16* p = gw + (size_t)ks * 2 * plane;
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+      for (int hl = 0; hl < 2; ++hl) f[4 + nb * 2 + hl] = *reinterpret_cast<const bf16x8*>(p + hl * plane + nb * 256);
+  };
+
+  f32x16 acc[2][2];                                // [pixel group][channel block]
+  // lane (m, h), register 4 q + j <-> channel 32 nb + 8 q + 4 h + j of pixel m
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float b = a.bias ? a.bias[cb * VG_NB + nb * 32 + 8 * q + 4 * h + j] : 0.f;
+        acc[0][nb][4 * q + j] = b; acc[1][nb][4 * q + j] = b;
+      }
+  auto mma = [&](const bf16x8 (&f)[8]) {
+#pragma unroll
+    for (int term = 0; term < 3; ++term)           // lo.hi, hi.lo, hi.hi: consecutive MFMAs go to different accumulators
+#pragma unroll
+      for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb)
+          acc[rg][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[4 + nb * 2 + (term == 0 ? 1 : 0)], f[rg * 2 + (term == 1 ? 1 : 0)],
+                                                                acc[rg][nb], 0, 0, 0);
+  };
+  bf16x8 f0[8], f1[8];
+  fetch(0, f0);
+  for (int ks = 0; ks < KS; ks += 2) {             // KS is even: Cin / 16 is a multiple of 4
+    fetch(ks + 1, f1);
+    mma(f0);
+    fetch(ks + 2, f0);
+    mma(f1);
+  }
+
+  // ---- epilogue ------------------------------------------------------------------------------------------------------------
+  const int G = Cout / 16;                          // words per pixel of the saved bits
+#pragma unroll
+  for (int rg = 0; rg < 2; ++rg) {
+    const int y = py[rg], x = px[rg];
+    const bool inside = y < H && x < W;
+    const size_t pix = (size_t)y * W + x;
+    if (EPI == VG_FWD_OUT) {
+      if (inside) {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int c = cb * VG_NB + nb * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
+            a.out_f32[(size_t)c * ((size_t)H * W) + pix] = acc[rg][nb][r];
+          }
+      }
+    } else if (EPI == VG_FWD_RELU || EPI == VG_BWD_MASK) {
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb) {
+        const int g = (cb * 2 + nb) * 2 + h;
+        uint32_t bits = 0u;
+        if (EPI == VG_BWD_MASK && inside) bits = a.relu_bits[pix * G + g];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          bf16x4 vh, vl;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float v = acc[rg][nb][4 * q + j];
+            if (EPI == VG_FWD_RELU) {
+              if (v > 0.f) bits |= 1u << (4 * q + j);
+              v = fmaxf(v, 0.f);
+            } else {
+              v = ((bits >> (4 * q + j)) & 1u) ? v : 0.f;
+            }
+            __bf16 hi, lo;
+            vg_split(v, hi, lo);
+            vh[j] = hi; vl[j] = lo;
+          }
+          if (inside) {
+            const size_t o = pix * Cout + cb * VG_NB + nb * 32 + 8 * q + 4 * h;
+            *reinterpret_cast<bf16x4*>(a.out_hi + o) = vh;
+            *reinterpret_cast<bf16x4*>(a.out_lo + o) = vl;
+          }
+        }
+        if (EPI == VG_FWD_RELU && inside && a.relu_bits) a.relu_bits[pix * G + g] = (uint16_t)bits;
+      }
+    } else if (EPI == VG_FWD_POOL) {
+      // the window of lanes m, m ^ 1, m ^ 16, m ^ 17 (the tile's origin is even); its owner is the lane with both bits clear
+      const int PH = H >> 1, PW = W >> 1, Y = y >> 1, X = x >> 1;
+      const bool owner = (m & 17) == 0 && Y < PH && X < PW;
+      const size_t ppix = (size_t)Y * PW + X;
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb) {
+        uint64_t codes = 0ull;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          bf16x4 vh, vl;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float v00 = fmaxf(acc[rg][nb][4 * q + j], 0.f);
+            const float v01 = __shfl_xor(v00, 1), v10 = __shfl_xor(v00, 16), v11 = __shfl_xor(v00, 17);
+            float best = v00; uint32_t idx = 0u;
+            if (v01 > best) { best = v01; idx = 1u; }
+            if (v10 > best) { best = v10; idx = 2u; }
+            if (v11 > best) { best = v11; idx = 3u; }
+            codes |= (uint64_t)(idx | (best > 0.f ? 4u : 0u)) << (4 * (4 * q + j));
+            __bf16 hi, lo;
+            vg_split(best, hi, lo);
+            vh[j] = hi; vl[j] = lo;
+          }
+          if (owner) {
+            const size_t o = ppix * Cout + cb * VG_NB + nb * 32 + 8 * q + 4 * h;
+            *reinterpret_cast<bf16x4*>(a.out_hi + o) = vh;
+            *reinterpret_cast<bf16x4*>(a.out_lo + o) = vl;
+          }
+        }
+        if (owner && a.pool_codes) a.pool_codes[ppix * G + (cb * 2 + nb) * 2 + h] = codes;
+      }
+    } else {                                        // VG_BWD_UNPOOL: pixel (y, x) is a pooled unit of the (out_H, out_W) plane
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb) {
+        uint64_t codes = 0ull;
+        if (inside) codes = a.pool_codes[pix * G + (cb * 2 + nb) * 2 + h];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+#pragma unroll
+          for (int p = 0; p < 4; ++p) {
+            bf16x4 vh, vl;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const uint32_t code = (uint32_t)(codes >> (4 * (4 * q + j))) & 15u;
+              const float v = code == (4u | (uint32_t)p) ? acc[rg][nb][4 * q + j] : 0.f;
+              __bf16 hi, lo;
+              vg_split(v, hi, lo);
+              vh[j] = hi; vl[j] = lo;
+            }
+            if (inside) {
+              const size_t opix = (size_t)(2 * y + (p >> 1)) * a.out_W + (2 * x + (p & 1));
+              const size_t o = opix * Cout + cb * VG_NB + nb * 32 + 8 * q + 4 * h;
+              *reinterpret_cast<bf16x4*>(a.out_hi + o) = vh;
+              *reinterpret_cast<bf16x4*>(a.out_lo + o) = vl;
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------
+struct VgPack { float* w1; float4* w1t; float* bias[VG_LAYERS + 1]; __bf16* fwd[VG_LAYERS + 1]; __bf16* bwd[VG_LAYERS + 1]; };
+static size_t vg_stream_elems(int l) { return (size_t)9 * vg_chan(l - 1) * vg_chan(l) * 2; }      // hi and lo
+static size_t vg_pack_layout(void* p, int k, VgPack& f) {
+  WsCursor c(p);
+  f.w1 = c.take<float>(64 * 27);
+  f.w1t = c.take<float4>(9 * 64);
+  for (int l = 1; l <= k; ++l) {                    // layer by layer: a pack of more layers begins with the pack of fewer
+    f.bias[l] = c.take<float>(vg_chan(l));
+    if (l > 1) { f.fwd[l] = c.take<__bf16>(vg_stream_elems(l)); f.bwd[l] = c.take<__bf16>(vg_stream_elems(l)); }
+  }
+  return c.bytes();
+}
+
+static inline size_t vg_pixels(int l, int H, int W) { return (size_t)(H >> vg_shift(l)) * (size_t)(W >> vg_shift(l)); }
+
+// saved decisions of layers 1 .. k - 1
+struct VgSaved { uint16_t* relu[VG_LAYERS + 1]; uint64_t* pool[VG_LAYERS + 1]; };
+static size_t vg_saved_layout(void* p, int k, int H, int W, VgSaved& s) {
+  WsCursor c(p);
+  for (int l = 1; l < k; ++l) {
+    s.relu[l] = nullptr; s.pool[l] = nullptr;
+    if (vg_pooled(l)) s.pool[l] = c.take<uint64_t>(vg_pixels(l + 1, H, W) * (vg_chan(l) / 16));
+    else s.relu[l] = c.take<uint16_t>(vg_pixels(l, H, W) * (vg_chan(l) / 16));
+  }
+  return c.bytes();
+}
+
+// the workspace: two ping-pong activation buffers (hi and lo planes each); layer l's output -- forward: the activation the next
+// layer reads (pooled where a pool follows); backward: the cotangent of its convolution output -- lives in buffer l & 1
+struct VgWs { __bf16* hi[2]; __bf16* lo[2]; };
+static size_t vg_ws_layout(void* p, int k, int H, int W, bool backward, VgWs& w) {
+  size_t units[2] = {0, 0};
+  for (int l = 1; l <= k; ++l) {
+    size_t n = 0;
+    if (backward) n = vg_pixels(l, H, W) * vg_chan(l);
+    else if (l < k) n = vg_pixels(vg_pooled(l) ? l + 1 : l, H, W) * vg_chan(l);
+    if (n > units[l & 1]) units[l & 1] = n;
+  }
+  WsCursor c(p);
+  for (int i = 0; i < 2; ++i) { w.hi[i] = c.take<__bf16>(units[i]); w.lo[i] = c.take<__bf16>(units[i]); }
+  return c.bytes();
+}
+
+static int vg_check_shape(const char* who, int k, int H, int W) {
+  if (k < 1 || k > VG_LAYERS) { set_error("%s: layers must be 1 .. 8 (conv1_1 .. conv4_1), got %d", who, k); return TRASE_ERR_INVALID; }
+  const int need = 1 << vg_shift(k);
+  if (H < need || W < need || (int64_t)H * W >= ((int64_t)1 << 25)) {
+    set_error("%s: need H, W >= %d and H * W < 2^25 (got %d x %d)", who, need, H, W); return TRASE_ERR_INVALID;
+  }
+  return TRASE_OK;
+}
+
+static int vg_lg(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+
+template <int EPI>
+static void vg_launch_conv(const VgConv& a, hipStream_t stream) {
+  const dim3 grid(((a.W + VG_TILE - 1) / VG_TILE) * ((a.H + VG_TILE - 1) / VG_TILE), a.Cout / VG_NB);
+  hipLaunchKernelGGL(vgg_conv_kernel<EPI>, grid, dim3(256), 0, stream, a);
+}
+
+static const char* const VG_FWD_NAMES[VG_LAYERS + 1] = {"", "vgg_fwd_conv1_1", "vgg_fwd_conv1_2", "vgg_fwd_conv2_1", "vgg_fwd_conv2_2",
+                                                         "vgg_fwd_conv3_1", "vgg_fwd_conv3_2", "vgg_fwd_conv3_3", "vgg_fwd_conv4_1"};
+static const char* const VG_BWD_NAMES[VG_LAYERS + 1] = {"", "vgg_bwd_conv1_1", "vgg_bwd_conv1_2", "vgg_bwd_conv2_1", "vgg_bwd_conv2_2",
+                                                         "vgg_bwd_conv3_1", "vgg_bwd_conv3_2", "vgg_bwd_conv3_3", "vgg_bwd_conv4_1"};
+
+static VgNorm vg_norm(const float* mean, const float* inv_std) {
+  VgNorm nm;
+  for (int i = 0; i < 3; ++i) { nm.mean[i] = mean ? mean[i] : 0.f; nm.inv_std[i] = inv_std ? inv_std[i] : 1.f; }
+  return nm;
+}
+
+}  // namespace trase
+
+using namespace trase;
+
+extern "C" {
+
+int trase_vgg_ws_bytes(int32_t layers, int32_t H, int32_t W, size_t* pack_bytes, size_t* ws_forward_bytes, size_t* ws_backward_bytes,
+                    size_t* saved_bytes, int32_t* C, int32_t* h, int32_t* w) {
+  const char* who = "trase_vgg_ws_bytes";
+  int rc = vg_check_shape(who, layers, H, W);
+  if (rc) return rc;
+  if (!pack_bytes || !ws_forward_bytes || !ws_backward_bytes || !saved_bytes || !C || !h || !w) {
+    set_error("%s: null pointer", who); return TRASE_ERR_INVALID;
+  }
+  VgPack p; VgWs ws; VgSaved s;
+  *pack_bytes = vg_pack_layout(nullptr, layers, p);
+  *ws_forward_bytes = vg_ws_layout(nullptr, layers, H, W, false, ws);
+  *ws_backward_bytes = vg_ws_layout(nullptr, layers, H, W, true, ws);
+  *saved_bytes = vg_saved_layout(nullptr, layers, H, W, s);
+  *C = vg_chan(layers); *h = H >> vg_shift(layers); *w = W >> vg_shift(layers);
+  return TRASE_OK;
+}
+
+int trase_vgg_pack(int32_t layers, const float* const* weights, const float* const* biases, void* pack, size_t pack_bytes,
+                   int32_t device, trase_stream_t stream_) {
+  const char* who = "trase_vgg_pack";
+  if (layers < 1 || layers > VG_LAYERS) { set_error("%s: layers must be 1 .. 8 (conv1_1 .. conv4_1), got %d", who, layers); return TRASE_ERR_INVALID; }
+  if (!weights || !biases || !pack) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  for (int l = 0; l < layers; ++l)
+    if (!weights[l] || !biases[l]) { set_error("%s: null layer %d", who, l); return TRASE_ERR_INVALID; }
+  if (((size_t)pack & 15) != 0) { set_error("%s: the pack buffer must be 16-byte aligned", who); return TRASE_ERR_INVALID; }
+  VgPack p;
+  const size_t need = vg_pack_layout(pack, layers, p);
+  if (pack_bytes < need) { set_error("%s: pack buffer too small (%zu bytes, need %zu)", who, pack_bytes, need); return TRASE_ERR_WORKSPACE; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  ProfScope ps("vgg_pack", stream);
+  hipLaunchKernelGGL(vgg_copy_kernel, dim3((64 * 27 + 255) / 256), dim3(256), 0, stream, weights[0], p.w1, 64 * 27);
+  hipLaunchKernelGGL(vgg_w1t_kernel, dim3(9), dim3(64), 0, stream, weights[0], p.w1t);
+  for (int l = 1; l <= layers; ++l)
+    hipLaunchKernelGGL(vgg_copy_kernel, dim3((vg_chan(l) + 255) / 256), dim3(256), 0, stream, biases[l - 1], p.bias[l], vg_chan(l));
+  for (int l = 2; l <= layers; ++l) {
+    const unsigned nb = (unsigned)((vg_stream_elems(l) / 2 + 255) / 256);
+    hipLaunchKernelGGL(vgg_pack_kernel, dim3(nb), dim3(256), 0, stream, weights[l - 1], vg_chan(l - 1), vg_chan(l), 0, p.fwd[l]);
+    hipLaunchKernelGGL(vgg_pack_kernel, dim3(nb), dim3(256), 0, stream, weights[l - 1], vg_chan(l - 1), vg_chan(l), 1, p.bwd[l]);
+  }
+  TRASE_POST_LAUNCH("vgg_pack", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_vgg_forward(int32_t layers, const void* pack, size_t pack_bytes, const float* image, int32_t H, int32_t W,
+                      const float* mean, const float* inv_std, float* out, void* saved, size_t saved_bytes, void* ws,
+                      size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  const char* who = "trase_vgg_forward";
+  int rc = vg_check_shape(who, layers, H, W);
+  if (rc) return rc;
+  const int k = layers;
+  if (!pack || !image || !out) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  if ((mean == nullptr) != (inv_std == nullptr)) { set_error("%s: mean and inv_std come together (both null: no normalisation)", who); return TRASE_ERR_INVALID; }
+  if (((size_t)pack & 15) != 0 || ((size_t)ws & 15) != 0 || ((size_t)saved & 15) != 0) {
+    set_error("%s: pack, saved and ws must be 16-byte aligned", who); return TRASE_ERR_INVALID;
+  }
+  VgPack p; VgWs b; VgSaved s;
+  if (pack_bytes < vg_pack_layout(const_cast<void*>(pack), k, p)) { set_error("%s: pack buffer too small for %d layers", who, k); return TRASE_ERR_WORKSPACE; }
+  const size_t ws_need = vg_ws_layout(ws, k, H, W, false, b);
+  if (ws_need > 0 && (!ws || ws_bytes < ws_need)) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws_bytes, ws_need); return TRASE_ERR_WORKSPACE; }
+  const size_t saved_need = vg_saved_layout(saved, k, H, W, s);
+  if (saved && saved_bytes < saved_need) { set_error("%s: saved buffer too small (%zu bytes, need %zu)", who, saved_bytes, saved_need); return TRASE_ERR_WORKSPACE; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  const VgNorm nm = vg_norm(mean, inv_std);
+  {
+    ProfScope ps(VG_FWD_NAMES[1], stream);
+    const dim3 grid((unsigned)(((size_t)H * W + 255) / 256));
+    if (k == 1)
+      hipLaunchKernelGGL(vgg_conv1_kernel<true>, grid, dim3(256), 0, stream, image, H, W, nm, p.w1, p.bias[1], (__bf16*)nullptr,
+                         (__bf16*)nullptr, out, (uint16_t*)nullptr);
+    else
+      hipLaunchKernelGGL(vgg_conv1_kernel<false>, grid, dim3(256), 0, stream, image, H, W, nm, p.w1, p.bias[1], b.hi[1], b.lo[1],
+                         (float*)nullptr, saved ? s.relu[1] : nullptr);
+  }
+  TRASE_POST_LAUNCH("vgg_fwd_conv1_1", stream, 0);
+  for (int l = 2; l <= k; ++l) {
+    VgConv a{};
+    a.in_hi = b.hi[(l - 1) & 1]; a.in_lo = b.lo[(l - 1) & 1];
+    a.stream = p.fwd[l]; a.bias = p.bias[l];
+    a.H = H >> vg_shift(l); a.W = W >> vg_shift(l); a.Cin = vg_chan(l - 1); a.Cout = vg_chan(l); a.lg_steps = vg_lg(a.Cin / 16);
+    a.out_hi = b.hi[l & 1]; a.out_lo = b.lo[l & 1];
+    ProfScope ps(VG_FWD_NAMES[l], stream);
+    if (l == k) { a.out_f32 = out; vg_launch_conv<VG_FWD_OUT>(a, stream); }
+    else if (vg_pooled(l)) { a.pool_codes = saved ? s.pool[l] : nullptr; vg_launch_conv<VG_FWD_POOL>(a, stream); }
+    else { a.relu_bits = saved ? s.relu[l] : nullptr; vg_launch_conv<VG_FWD_RELU>(a, stream); }
+    TRASE_POST_LAUNCH("vgg_fwd_conv", stream, 0);
+  }
+  return TRASE_OK;
+}
+
+int trase_vgg_backward(int32_t layers, const void* pack, size_t pack_bytes, const float* d_out, int32_t H, int32_t W,
+                       const float* inv_std, const void* saved, size_t saved_bytes, float* d_image, void* ws, size_t ws_bytes,
+                       int32_t device, trase_stream_t stream_) {
+  const char* who = "trase_vgg_backward";
+  int rc = vg_check_shape(who, layers, H, W);
+  if (rc) return rc;
+  const int k = layers;
+  if (!pack || !d_out || !d_image || !ws || (k > 1 && !saved)) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  if (((size_t)pack & 15) != 0 || ((size_t)ws & 15) != 0 || ((size_t)saved & 15) != 0) {
+    set_error("%s: pack, saved and ws must be 16-byte aligned", who); return TRASE_ERR_INVALID;
+  }
+  VgPack p; VgWs b; VgSaved s;
+  if (pack_bytes < vg_pack_layout(const_cast<void*>(pack), k, p)) { set_error("%s: pack buffer too small for %d layers", who, k); return TRASE_ERR_WORKSPACE; }
+  const size_t ws_need = vg_ws_layout(ws, k, H, W, true, b);
+  if (ws_bytes < ws_need) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws_bytes, ws_need); return TRASE_ERR_WORKSPACE; }
+  const size_t saved_need = vg_saved_layout(const_cast<void*>(saved), k, H, W, s);
+  if (saved_bytes < saved_need) { set_error("%s: saved buffer too small (%zu bytes, need %zu)", who, saved_bytes, saved_need); return TRASE_ERR_WORKSPACE; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  {
+    ProfScope ps("vgg_bwd_split", stream);
+    const int hw = (int)vg_pixels(k, H, W);
+    hipLaunchKernelGGL(vgg_cot_split_kernel, dim3((hw + 255) / 256, vg_chan(k) / 8), dim3(256), 0, stream, d_out, vg_chan(k), hw,
+                       b.hi[k & 1], b.lo[k & 1]);
+  }
+  TRASE_POST_LAUNCH("vgg_bwd_split", stream, 0);
+  for (int l = k; l >= 2; --l) {                   // the cotangent of layer l's output -> that of layer l - 1's
+    VgConv a{};
+    a.in_hi = b.hi[l & 1]; a.in_lo = b.lo[l & 1];
+    a.stream = p.bwd[l]; a.bias = nullptr;
+    a.H = H >> vg_shift(l); a.W = W >> vg_shift(l); a.Cin = vg_chan(l); a.Cout = vg_chan(l - 1); a.lg_steps = vg_lg(a.Cin / 16);
+    a.out_hi = b.hi[(l - 1) & 1]; a.out_lo = b.lo[(l - 1) & 1];
+    ProfScope ps(VG_BWD_NAMES[l], stream);
+    if (vg_pooled(l - 1)) {
+      a.out_H = H >> vg_shift(l - 1); a.out_W = W >> vg_shift(l - 1);
+      if ((a.out_H | a.out_W) & 1) {               // an odd last row / column lies in no window
+        const size_t bytes = vg_pixels(l - 1, H, W) * vg_chan(l - 1) * sizeof(__bf16);
+        rc = launch_zero_bytes(a.out_hi, bytes, stream); if (rc) return rc;
+        rc = launch_zero_bytes(a.out_lo, bytes, stream); if (rc) return rc;
+      }
+      a.pool_codes = const_cast<uint64_t*>(s.pool[l - 1]);
+      vg_launch_conv<VG_BWD_UNPOOL>(a, stream);
+    } else {
+      a.relu_bits = const_cast<uint16_t*>(s.relu[l - 1]);
+      vg_launch_conv<VG_BWD_MASK>(a, stream);
+    }
+    TRASE_POST_LAUNCH("vgg_bwd_conv", stream, 0);
+  }
+  {
+    ProfScope ps(VG_BWD_NAMES[1], stream);
+    const VgNorm nm = vg_norm(nullptr, inv_std);
+    hipLaunchKernelGGL(vgg_image_grad_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, stream, b.hi[1], b.lo[1], H, W, nm,
+                       (const float4*)p.w1t, d_image);
+  }
+  TRASE_POST_LAUNCH("vgg_bwd_conv1_1", stream, 0);
+  return TRASE_OK;
+}
+
+}  // extern "C"
