@@ -152,8 +152,8 @@ def test_equal_sizes_run_the_existing_kernels_bit_for_bit(mode):
     for with_reg in (False, True):
         a = _run(feat, sam, sp, sm, mode, with_norm_reg=with_reg)
         f = feat.clone().requires_grad_(True)
-        res = FH._PairHeadResized.apply(f, FH._masks_u8(sam), sm.view(torch.uint8), sam.shape[0], size, pix, FH._MODES[mode], 0.75, 0.5, 1,
-                                        with_reg, None)
+        res = FH._PairHead.apply(f, FH._masks_u8(sam), sm.view(torch.uint8), sam.shape[0], size, pix, FH._MODES[mode], 0.75, 0.5, 1,
+                                 with_reg, None, True)
         loss = res[0] + 0.5 * res[1] + (0.3 * res[3] if with_reg else 0.0)
         grad, = torch.autograd.grad(loss, f)
         b = (res[0].detach(), res[1].detach(), res[2][0], res[2][1]) + ((res[3].detach(),) if with_reg else ()) + (grad,)

@@ -297,7 +297,7 @@ _COUNT_ARGS = {5: (5, 14, 7, 4048, 0.0), 250: (250, 14, 7, 4250), 257: (257, 14,
 
 
 def _layout(cap):
-    """byte ranges of the per-sample arrays in the workspace (pair_ws_walk of csrc/pairhead.hip: 256-byte aligned, in this order)"""
+    """byte ranges of the per-sample arrays in the workspace (pair_ws_layout of csrc/pairhead.hip: 256-byte aligned, in this order)"""
     up = lambda n: (n + 255) // 256 * 256
     nblk = ((cap + 255) // 256) * ((cap + 63) // 64)
     o, out = 0, {}

@@ -27,6 +27,8 @@
 //   ph_scatter<true> keeps the per-sample gradient v (S, 32) in the workspace
 //   ph_spread        one thread per pixel of the (32, Hr, Wr) gradient gathers its taps' h * w * v in a fixed order and
 //                    writes 32 channels once -- with the regulariser's term when asked: no zero fill, no atomics
+// Host side: every trase_pairhead_* entry point (plain / _n / _bits / _resized / _bits_resized) fills a PairCall and runs
+// pairhead_forward or pairhead_backward, which hold the argument checks, the workspace layout and each launch once.
 // Built with -ffp-contract=off: the weight arithmetic follows torch's op order; dot products use explicit fmaf.
 #include "common.h"
 
@@ -37,6 +39,10 @@ constexpr int PH_ROWS = 64;     // rows per workgroup in the pair passes
 constexpr int PH_CHUNKS = 32;   // u-chunks of the backward
 constexpr int PH_MAXW = 8;      // 32-bit membership words: up to 256 sampled masks
 constexpr int PH_MAXN = 8192;   // masks per view
+
+// the head on a (32, Hr, Wr) feature image with (h, w) masks: scale = float(in) / out per axis, as ATen takes it
+struct ResizeGeom { int Hr, Wr, h, w; float scale_h, scale_w; };
+static ResizeGeom resize_geom(int Hr, int Wr, int h, int w) { return ResizeGeom{Hr, Wr, h, w, (float)Hr / (float)h, (float)Wr / (float)w}; }
 
 struct PairWs {
   float* fn;        // [S][32] normalised sampled features
@@ -49,9 +55,15 @@ struct PairWs {
   float* dpart;     // [PH_CHUNKS][S][32]
   int* rank;        // [PH_MAXN] bit position of a sampled mask (-1: not sampled)
   int nblk;
+  // behind them, the resized head's:
+  float* v;                           // [S][32] gradient of the resized (un-normalised) columns
+  int* slot;                          // [h * w] index of the sample at a mask pixel, -1: not sampled
+  int* row_first; int* row_count;     // [Hr] mask rows whose upper tap is this source row: first, how many
+  int* col_first; int* col_count;     // [Wr] the same for columns
 };
-
-static void pair_ws_walk(WsCursor& c, int S, PairWs& w) {
+// g: the geometry of the resized head, null for the head at mask resolution (whose workspace is the front part of the other's)
+static size_t pair_ws_layout(void* ws, int S, const ResizeGeom* g, PairWs& w) {
+  WsCursor c(ws);
   const size_t s = (size_t)S;
   w.nblk = ((S + 255) / 256) * ((S + PH_ROWS - 1) / PH_ROWS);
   w.fn = c.take<float>(PH_F * s);
@@ -64,33 +76,13 @@ static void pair_ws_walk(WsCursor& c, int S, PairWs& w) {
   w.partial = c.take<double>(8 * (size_t)w.nblk);
   w.dpart = c.take<float>(PH_F * s * PH_CHUNKS);
   w.rank = c.take<int>(PH_MAXN);
-}
-static size_t pair_ws_layout(void* ws, int S, PairWs& w) {
-  WsCursor c(ws);
-  pair_ws_walk(c, S, w);
-  return c.bytes();
-}
-
-// the head on a (32, Hr, Wr) feature image with (h, w) masks: scale = float(in) / out per axis, as ATen takes it
-struct ResizeGeom { int Hr, Wr, h, w; float scale_h, scale_w; };
-static ResizeGeom resize_geom(int Hr, int Wr, int h, int w) { return ResizeGeom{Hr, Wr, h, w, (float)Hr / (float)h, (float)Wr / (float)w}; }
-
-struct ResizedWs {
-  PairWs pair;
-  float* v;                           // [S][32] gradient of the resized (un-normalised) columns
-  int* slot;                          // [h * w] index of the sample at a mask pixel, -1: not sampled
-  int* row_first; int* row_count;     // [Hr] mask rows whose upper tap is this source row: first, how many
-  int* col_first; int* col_count;     // [Wr] the same for columns
-};
-static size_t resized_ws_layout(void* ws, int S, const ResizeGeom& g, ResizedWs& r) {
-  WsCursor c(ws);
-  pair_ws_walk(c, S, r.pair);
-  r.v = c.take<float>(PH_F * (size_t)S);
-  r.slot = c.take<int>((size_t)g.h * g.w);
-  r.row_first = c.take<int>(g.Hr);
-  r.row_count = c.take<int>(g.Hr);
-  r.col_first = c.take<int>(g.Wr);
-  r.col_count = c.take<int>(g.Wr);
+  if (!g) return c.bytes();
+  w.v = c.take<float>(PH_F * s);
+  w.slot = c.take<int>((size_t)g->h * g->w);
+  w.row_first = c.take<int>(g->Hr);
+  w.row_count = c.take<int>(g->Hr);
+  w.col_first = c.take<int>(g->Wr);
+  w.col_count = c.take<int>(g->Wr);
   return c.bytes();
 }
 
@@ -856,13 +848,157 @@ int trase_compact_pixels(const uint8_t* flags, int64_t HW, int32_t* pix, int32_t
   return TRASE_OK;
 }
 
-int trase_pairhead_sizes(int32_t S, size_t* ws_bytes) {
-  if (!ws_bytes || S < 1) { set_error("trase_pairhead_sizes: bad arguments"); return TRASE_ERR_INVALID; }
-  PairWs w;
-  *ws_bytes = pair_ws_layout(nullptr, S, w);
+// ---- the pair head: every entry point below describes its call and runs the one forward or the one backward ---------------------
+struct PairCall {
+  const char* who;                // the entry point, for messages
+  bool packed;                    // the masks are the packed stream of maskbits.hip instead of N * HW bool bytes
+  bool resized;                   // feats is (32, g.Hr, g.Wr) and the masks are (g.h, g.w); otherwise both have HW pixels
+  ResizeGeom g;
+  int32_t F; int64_t HW;          // HW: the pixels of one mask
+  const int32_t* pix; int32_t S; const int32_t* S_dev;
+  int32_t mode; float positive_th, negative_th; int32_t use_weights;
+  const void* ws; size_t ws_bytes; int32_t device; trase_stream_t stream;
+};
+static PairCall plain_call(const char* who, bool packed, int32_t F, int64_t HW, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
+                           float positive_th, float negative_th, int32_t use_weights, const void* ws, size_t ws_bytes, int32_t device,
+                           trase_stream_t stream) {
+  return PairCall{who, packed, false, ResizeGeom{}, F, HW, pix, S, S_dev, mode, positive_th, negative_th, use_weights, ws, ws_bytes, device, stream};
+}
+static PairCall resized_call(const char* who, bool packed, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const int32_t* pix, int32_t S,
+                             const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights, const void* ws,
+                             size_t ws_bytes, int32_t device, trase_stream_t stream) {
+  return PairCall{who, packed, true, resize_geom(Hr, Wr, h, w), F, (int64_t)h * w, pix, S, S_dev, mode, positive_th, negative_th, use_weights, ws,
+                  ws_bytes, device, stream};
+}
+
+// the argument rules the *_resized entry points share; 0 when the sizes are usable
+static int resized_sizes_ok(const char* who, int32_t S, int32_t Hr, int32_t Wr, int32_t h, int32_t w) {
+  if (S < 1 || Hr < 1 || Wr < 1 || h < 1 || w < 1) {
+    set_error("%s: need S, Hr, Wr, h, w >= 1 (got S %d, features %d x %d, masks %d x %d)", who, S, Hr, Wr, h, w);
+    return TRASE_ERR_INVALID;
+  }
+  if ((int64_t)Hr * Wr >= ((int64_t)1 << 31) || (int64_t)h * w >= ((int64_t)1 << 31)) {
+    set_error("%s: need Hr * Wr < 2^31 and h * w < 2^31 (got features %d x %d, masks %d x %d)", who, Hr, Wr, h, w);
+    return TRASE_ERR_INVALID;
+  }
+  return TRASE_OK;
+}
+static int channels_ok(const char* who, int32_t F) {
+  if (F != PH_F) { set_error("%s: %d feature channels (compiled for %d)", who, F, PH_F); return TRASE_ERR_INVALID; }
+  return TRASE_OK;
+}
+static int pair_ws_ok(const PairCall& c, PairWs& w) {
+  if (!c.ws || c.ws_bytes < pair_ws_layout(const_cast<void*>(c.ws), c.S, c.resized ? &c.g : nullptr, w)) {
+    set_error("%s: workspace too small", c.who); return TRASE_ERR_WORKSPACE;
+  }
   return TRASE_OK;
 }
 
+static int pairhead_forward(const PairCall& c, const float* feats, const uint8_t* sam_masks, size_t bits_bytes, int32_t N,
+                            const uint8_t* sampled_mask, int32_t n_sampled_masks, const uint32_t* mask_size, float* out8) {
+  const bool null = !feats || !sam_masks || !sampled_mask || !mask_size || !c.pix || !out8;
+  if (c.resized) {        // this family names a null pointer and its sizes; the other answers both with "bad arguments"
+    if (null) { set_error("%s: null pointer", c.who); return TRASE_ERR_INVALID; }
+    if (int rc = resized_sizes_ok(c.who, c.S, c.g.Hr, c.g.Wr, c.g.h, c.g.w)) return rc;
+  }
+  if (null || c.S < 1 || N < 1 || N > PH_MAXN || c.HW < 1 || c.mode < 0 || c.mode > 2) {
+    set_error("%s: bad arguments", c.who); return TRASE_ERR_INVALID;
+  }
+  if (c.packed) { if (int rc = mask_bits_ok(c.who, sam_masks, bits_bytes, N, c.HW)) return rc; }
+  if (int rc = channels_ok(c.who, c.F)) return rc;
+  if (n_sampled_masks < 0 || n_sampled_masks > 32 * PH_MAXW) {
+    set_error("%s: %d sampled masks (at most %d)", c.who, n_sampled_masks, 32 * PH_MAXW); return TRASE_ERR_INVALID;
+  }
+  PairWs w;
+  if (int rc = pair_ws_ok(c, w)) return rc;
+  const int S = c.S;
+  const int* S_dev = c.S_dev;
+  hipStream_t stream = (hipStream_t)c.stream;
+  TRASE_CHECK(hipSetDevice(c.device));
+  // colP and colN are neighbours in the workspace (pair_ws_layout): one fill for both
+  launch_zero_bytes(w.colP, (size_t)((char*)w.colN - (char*)w.colP) + sizeof(int) * (size_t)S, stream);
+  const dim3 grid((S + 255) / 256, (S + PH_ROWS - 1) / PH_ROWS);
+  {
+    ProfScope ps(c.resized ? "pairhead_fwd_resized" : "pairhead_fwd", stream);
+    hipLaunchKernelGGL(ph_rank_kernel, dim3(1), dim3(256), 0, stream, sampled_mask, N, w.rank, w.consts);
+    if (c.resized) {      // what the backward gathers through: written here, where the workspace is still the caller's to write
+      hipLaunchKernelGGL(ph_tables_kernel, dim3((std::max(c.g.Hr, c.g.Wr) + 255) / 256), dim3(256), 0, stream, c.g, w.row_first, w.row_count,
+                         w.col_first, w.col_count);
+      hipLaunchKernelGGL(ph_slots_kernel, dim3(((int)c.HW + 255) / 256), dim3(256), 0, stream, c.pix, S, S_dev, (int)c.HW, w.slot);
+    }
+    const auto gather = !c.resized ? (c.packed ? ph_gather_kernel<false, true> : ph_gather_kernel<false, false>)
+                                   : (c.packed ? ph_gather_kernel<true, true> : ph_gather_kernel<true, false>);
+    hipLaunchKernelGGL(gather, dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)c.HW, c.g, sam_masks, N, w.rank, mask_size, c.pix,
+                       S, S_dev, w.fn, w.rinv, w.a, w.bits);
+    hipLaunchKernelGGL(ph_consts_kernel, dim3(1), dim3(256), 0, stream, w.a, S, S_dev, w.consts);
+    hipLaunchKernelGGL(ph_flags_kernel, grid, dim3(256), 0, stream, w.fn, w.bits, S, S_dev, c.positive_th, c.negative_th, c.mode, w.colP, w.colN,
+                       w.partial);
+    hipLaunchKernelGGL(ph_sum_kernel, grid, dim3(256), 0, stream, w.fn, w.bits, w.a, w.consts, S, S_dev, c.positive_th, c.negative_th, c.mode,
+                       c.use_weights, w.colP, w.colN, w.partial);
+    hipLaunchKernelGGL(ph_final_kernel, dim3(1), dim3(256), 0, stream, w.partial, w.nblk, w.colP, w.colN, S, S_dev, c.mode, w.consts, out8);
+  }
+  if (c.resized) TRASE_POST_LAUNCH("pairhead_fwd_resized", stream, 0);
+  else TRASE_POST_LAUNCH("pairhead_fwd", stream, 0);
+  return TRASE_OK;
+}
+
+// plain: into the (32, HW) image, zero-filled first unless `accumulate`; feats / out2 / g_reg stay null.
+// resized: into the (32, Hr, Wr) image through the per-sample gradient v, every element written once -- with the regulariser's term
+// when feats, out2 and g_reg are given
+static int pairhead_backward(const PairCall& c, const float* out8, const float* g2, int32_t accumulate, const float* feats, const float* out2,
+                             const float* g_reg, float* dL_dfeats) {
+  const bool null = !c.pix || !out8 || !g2 || !dL_dfeats;
+  const bool reg = feats || out2 || g_reg;
+  if (c.resized) {        // as in the forward; the plain family also answers a wrong F with "bad arguments"
+    if (null) { set_error("%s: null pointer", c.who); return TRASE_ERR_INVALID; }
+    if (reg && !(feats && out2 && g_reg)) { set_error("%s: the regulariser needs feats, out2 and g_reg together", c.who); return TRASE_ERR_INVALID; }
+    if (int rc = resized_sizes_ok(c.who, c.S, c.g.Hr, c.g.Wr, c.g.h, c.g.w)) return rc;
+  }
+  if (null || c.S < 1 || c.HW < 1 || c.mode < 0 || c.mode > 2 || (!c.resized && c.F != PH_F)) {
+    set_error("%s: bad arguments", c.who); return TRASE_ERR_INVALID;
+  }
+  if (int rc = channels_ok(c.who, c.F)) return rc;
+  PairWs w;
+  if (int rc = pair_ws_ok(c, w)) return rc;
+  const int S = c.S;
+  const int* S_dev = c.S_dev;
+  hipStream_t stream = (hipStream_t)c.stream;
+  TRASE_CHECK(hipSetDevice(c.device));
+  if (!c.resized && !accumulate) launch_zero_bytes(dL_dfeats, sizeof(float) * (size_t)c.F * (size_t)c.HW, stream);
+  {
+    ProfScope ps(c.resized ? "pairhead_bwd_resized" : "pairhead_bwd", stream);
+    hipLaunchKernelGGL(ph_bwd_kernel, dim3((S + 255) / 256, PH_CHUNKS), dim3(256), 0, stream, w.fn, w.bits, w.a, w.consts, S, S_dev, c.positive_th,
+                       c.negative_th, c.mode, c.use_weights, w.colP, w.colN, out8, g2, w.dpart);
+    hipLaunchKernelGGL(!c.resized ? ph_scatter_kernel<false> : ph_scatter_kernel<true>, dim3((S * PH_F + 255) / 256), dim3(256), 0, stream, w.dpart,
+                       w.fn, w.rinv, c.pix, S, S_dev, c.resized ? 0ll : (long long)c.HW, c.resized ? 0 : accumulate, c.resized ? w.v : dL_dfeats);
+  }
+  if (!c.resized) { TRASE_POST_LAUNCH("pairhead_bwd", stream, 0); return TRASE_OK; }
+  {
+    ProfScope ps("pairhead_spread", stream);
+    hipLaunchKernelGGL(reg ? ph_spread_kernel<true> : ph_spread_kernel<false>, dim3((unsigned)(((int64_t)c.g.Hr * c.g.Wr + 255) / 256)), dim3(256), 0,
+                       stream, w.v, w.slot, w.row_first, w.row_count, w.col_first, w.col_count, c.g, feats, out2, g_reg, dL_dfeats);
+  }
+  TRASE_POST_LAUNCH("pairhead_bwd_resized", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_pairhead_sizes(int32_t S, size_t* ws_bytes) {
+  if (!ws_bytes || S < 1) { set_error("trase_pairhead_sizes: bad arguments"); return TRASE_ERR_INVALID; }
+  PairWs w;
+  *ws_bytes = pair_ws_layout(nullptr, S, nullptr, w);
+  return TRASE_OK;
+}
+
+int trase_pairhead_sizes_resized(int32_t S, int32_t Hr, int32_t Wr, int32_t h, int32_t w, size_t* ws_bytes) {
+  if (!ws_bytes) { set_error("trase_pairhead_sizes_resized: null pointer"); return TRASE_ERR_INVALID; }
+  if (int rc = resized_sizes_ok("trase_pairhead_sizes_resized", S, Hr, Wr, h, w)) return rc;
+  const ResizeGeom g = resize_geom(Hr, Wr, h, w);
+  PairWs pw;
+  *ws_bytes = pair_ws_layout(nullptr, S, &g, pw);
+  return TRASE_OK;
+}
+
+// (the form without a device-side count and the one with it answer under the same name)
 int trase_pairhead_forward(const float* feats, int32_t F, int64_t HW, const uint8_t* sam_masks, int32_t N,
                            const uint8_t* sampled_mask, int32_t n_sampled_masks, const uint32_t* mask_size, const int32_t* pix,
                            int32_t S, int32_t mode, float positive_th, float negative_th, int32_t use_weights, float* out8,
@@ -871,62 +1007,42 @@ int trase_pairhead_forward(const float* feats, int32_t F, int64_t HW, const uint
                                   negative_th, use_weights, out8, ws, ws_bytes, device, stream_);
 }
 
-// the head at mask resolution on bool bytes (packed == false: who = "trase_pairhead_forward") or on the packed stream
-static int pairhead_forward_impl(const char* who, bool packed, const float* feats, int32_t F, int64_t HW, const uint8_t* sam_masks,
-                                 size_t bits_bytes, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
-                                 const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
-                                 float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
-                                 int32_t device, trase_stream_t stream_) {
-  if (!feats || !sam_masks || !sampled_mask || !mask_size || !pix || !out8 || S < 1 || N < 1 || N > PH_MAXN || HW < 1 || mode < 0 || mode > 2) {
-    set_error("%s: bad arguments", who); return TRASE_ERR_INVALID;
-  }
-  if (packed) { if (int rc = mask_bits_ok(who, sam_masks, bits_bytes, N, HW)) return rc; }
-  if (F != PH_F) { set_error("%s: %d feature channels (compiled for %d)", who, F, PH_F); return TRASE_ERR_INVALID; }
-  if (n_sampled_masks < 0 || n_sampled_masks > 32 * PH_MAXW) {
-    set_error("%s: %d sampled masks (at most %d)", who, n_sampled_masks, 32 * PH_MAXW); return TRASE_ERR_INVALID;
-  }
-  PairWs w;
-  if (!ws || ws_bytes < pair_ws_layout(ws, S, w)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
-  hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(device));
-  // colP and colN are neighbours in the workspace (pair_ws_layout): one fill for both
-  launch_zero_bytes(w.colP, (size_t)((char*)w.colN - (char*)w.colP) + sizeof(int) * (size_t)S, stream);
-  const dim3 grid((S + 255) / 256, (S + PH_ROWS - 1) / PH_ROWS);
-  {
-    ProfScope ps("pairhead_fwd", stream);
-    hipLaunchKernelGGL(ph_rank_kernel, dim3(1), dim3(256), 0, stream, sampled_mask, N, w.rank, w.consts);
-    if (packed)
-      hipLaunchKernelGGL((ph_gather_kernel<false, true>), dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, ResizeGeom{}, sam_masks,
-                         N, w.rank, mask_size, pix, S, (const int*)S_dev, w.fn, w.rinv, w.a, w.bits);
-    else
-      hipLaunchKernelGGL((ph_gather_kernel<false, false>), dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, ResizeGeom{}, sam_masks,
-                         N, w.rank, mask_size, pix, S, (const int*)S_dev, w.fn, w.rinv, w.a, w.bits);
-    hipLaunchKernelGGL(ph_consts_kernel, dim3(1), dim3(256), 0, stream, w.a, S, (const int*)S_dev, w.consts);
-    hipLaunchKernelGGL(ph_flags_kernel, grid, dim3(256), 0, stream, w.fn, w.bits, S, (const int*)S_dev, positive_th, negative_th, mode, w.colP,
-                       w.colN, w.partial);
-    hipLaunchKernelGGL(ph_sum_kernel, grid, dim3(256), 0, stream, w.fn, w.bits, w.a, w.consts, S, (const int*)S_dev, positive_th, negative_th,
-                       mode, use_weights, w.colP, w.colN, w.partial);
-    hipLaunchKernelGGL(ph_final_kernel, dim3(1), dim3(256), 0, stream, w.partial, w.nblk, w.colP, w.colN, S, (const int*)S_dev, mode, w.consts,
-                       out8);
-  }
-  TRASE_POST_LAUNCH("pairhead_fwd", stream, 0);
-  return TRASE_OK;
-}
-
 int trase_pairhead_forward_n(const float* feats, int32_t F, int64_t HW, const uint8_t* sam_masks, int32_t N,
                              const uint8_t* sampled_mask, int32_t n_sampled_masks, const uint32_t* mask_size, const int32_t* pix,
                              int32_t S, const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
                              float* out8, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
-  return pairhead_forward_impl("trase_pairhead_forward", false, feats, F, HW, sam_masks, 0, N, sampled_mask, n_sampled_masks, mask_size, pix, S,
-                               S_dev, mode, positive_th, negative_th, use_weights, out8, ws, ws_bytes, device, stream_);
+  return pairhead_forward(plain_call("trase_pairhead_forward", false, F, HW, pix, S, S_dev, mode, positive_th, negative_th, use_weights, ws, ws_bytes,
+                                     device, stream_),
+                          feats, sam_masks, 0, N, sampled_mask, n_sampled_masks, mask_size, out8);
 }
 
 int trase_pairhead_forward_bits(const float* feats, int32_t F, int64_t HW, const uint8_t* bits, size_t bits_bytes, int32_t N,
                                 const uint8_t* sampled_mask, int32_t n_sampled_masks, const uint32_t* mask_size, const int32_t* pix,
                                 int32_t S, const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
                                 float* out8, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
-  return pairhead_forward_impl("trase_pairhead_forward_bits", true, feats, F, HW, bits, bits_bytes, N, sampled_mask, n_sampled_masks, mask_size,
-                               pix, S, S_dev, mode, positive_th, negative_th, use_weights, out8, ws, ws_bytes, device, stream_);
+  return pairhead_forward(plain_call("trase_pairhead_forward_bits", true, F, HW, pix, S, S_dev, mode, positive_th, negative_th, use_weights, ws,
+                                     ws_bytes, device, stream_),
+                          feats, bits, bits_bytes, N, sampled_mask, n_sampled_masks, mask_size, out8);
+}
+
+int trase_pairhead_forward_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w,
+                                   const uint8_t* sam_masks, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
+                                   const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
+                                   float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
+                                   int32_t device, trase_stream_t stream_) {
+  return pairhead_forward(resized_call("trase_pairhead_forward_resized", false, F, Hr, Wr, h, w, pix, S, S_dev, mode, positive_th, negative_th,
+                                       use_weights, ws, ws_bytes, device, stream_),
+                          feats, sam_masks, 0, N, sampled_mask, n_sampled_masks, mask_size, out8);
+}
+
+int trase_pairhead_forward_bits_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const uint8_t* bits,
+                                        size_t bits_bytes, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
+                                        const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
+                                        float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
+                                        int32_t device, trase_stream_t stream_) {
+  return pairhead_forward(resized_call("trase_pairhead_forward_bits_resized", true, F, Hr, Wr, h, w, pix, S, S_dev, mode, positive_th, negative_th,
+                                       use_weights, ws, ws_bytes, device, stream_),
+                          feats, bits, bits_bytes, N, sampled_mask, n_sampled_masks, mask_size, out8);
 }
 
 int trase_pairhead_backward(int32_t F, int64_t HW, const int32_t* pix, int32_t S, int32_t mode, float positive_th,
@@ -939,159 +1055,25 @@ int trase_pairhead_backward(int32_t F, int64_t HW, const int32_t* pix, int32_t S
 int trase_pairhead_backward_n(int32_t F, int64_t HW, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode, float positive_th,
                               float negative_th, int32_t use_weights, const float* out8, const float* g2, const void* ws,
                               size_t ws_bytes, int32_t accumulate, float* dL_dfeats, int32_t device, trase_stream_t stream_) {
-  if (!pix || !out8 || !g2 || !dL_dfeats || S < 1 || HW < 1 || mode < 0 || mode > 2 || F != PH_F) {
-    set_error("trase_pairhead_backward: bad arguments"); return TRASE_ERR_INVALID;
-  }
-  PairWs w;
-  if (!ws || ws_bytes < pair_ws_layout(const_cast<void*>(ws), S, w)) { set_error("trase_pairhead_backward: workspace too small"); return TRASE_ERR_WORKSPACE; }
-  hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(device));
-  if (!accumulate) launch_zero_bytes(dL_dfeats, sizeof(float) * (size_t)F * (size_t)HW, stream);
-  {
-    ProfScope ps("pairhead_bwd", stream);
-    hipLaunchKernelGGL(ph_bwd_kernel, dim3((S + 255) / 256, PH_CHUNKS), dim3(256), 0, stream, w.fn, w.bits, w.a, w.consts, S, (const int*)S_dev,
-                       positive_th, negative_th, mode, use_weights, w.colP, w.colN, out8, g2, w.dpart);
-    hipLaunchKernelGGL(ph_scatter_kernel<false>, dim3((S * PH_F + 255) / 256), dim3(256), 0, stream, w.dpart, w.fn, w.rinv, pix, S, (const int*)S_dev,
-                       (long long)HW, accumulate, dL_dfeats);
-  }
-  TRASE_POST_LAUNCH("pairhead_bwd", stream, 0);
-  return TRASE_OK;
-}
-
-// the argument rules the three *_resized entry points share; 0 when the sizes are usable
-static int resized_sizes_ok(const char* who, int32_t S, int32_t Hr, int32_t Wr, int32_t h, int32_t w) {
-  if (S < 1 || Hr < 1 || Wr < 1 || h < 1 || w < 1) {
-    set_error("%s: need S, Hr, Wr, h, w >= 1 (got S %d, features %d x %d, masks %d x %d)", who, S, Hr, Wr, h, w);
-    return TRASE_ERR_INVALID;
-  }
-  if ((int64_t)Hr * Wr >= ((int64_t)1 << 31) || (int64_t)h * w >= ((int64_t)1 << 31)) {
-    set_error("%s: need Hr * Wr < 2^31 and h * w < 2^31 (got features %d x %d, masks %d x %d)", who, Hr, Wr, h, w);
-    return TRASE_ERR_INVALID;
-  }
-  return TRASE_OK;
-}
-
-int trase_pairhead_sizes_resized(int32_t S, int32_t Hr, int32_t Wr, int32_t h, int32_t w, size_t* ws_bytes) {
-  if (!ws_bytes) { set_error("trase_pairhead_sizes_resized: null pointer"); return TRASE_ERR_INVALID; }
-  if (int rc = resized_sizes_ok("trase_pairhead_sizes_resized", S, Hr, Wr, h, w)) return rc;
-  ResizedWs r;
-  *ws_bytes = resized_ws_layout(nullptr, S, resize_geom(Hr, Wr, h, w), r);
-  return TRASE_OK;
-}
-
-static int pairhead_forward_resized_impl(const char* who, bool packed, const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h,
-                                         int32_t w, const uint8_t* sam_masks, size_t bits_bytes, int32_t N, const uint8_t* sampled_mask,
-                                         int32_t n_sampled_masks, const uint32_t* mask_size, const int32_t* pix, int32_t S,
-                                         const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
-                                         float* out8, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
-  if (!feats || !sam_masks || !sampled_mask || !mask_size || !pix || !out8) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
-  if (int rc = resized_sizes_ok(who, S, Hr, Wr, h, w)) return rc;
-  if (N < 1 || N > PH_MAXN || mode < 0 || mode > 2) { set_error("%s: bad arguments", who); return TRASE_ERR_INVALID; }
-  if (packed) { if (int rc = mask_bits_ok(who, sam_masks, bits_bytes, N, (int64_t)h * w)) return rc; }
-  if (F != PH_F) { set_error("%s: %d feature channels (compiled for %d)", who, F, PH_F); return TRASE_ERR_INVALID; }
-  if (n_sampled_masks < 0 || n_sampled_masks > 32 * PH_MAXW) {
-    set_error("%s: %d sampled masks (at most %d)", who, n_sampled_masks, 32 * PH_MAXW); return TRASE_ERR_INVALID;
-  }
-  const ResizeGeom g = resize_geom(Hr, Wr, h, w);
-  ResizedWs r;
-  if (!ws || ws_bytes < resized_ws_layout(ws, S, g, r)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
-  const PairWs& p = r.pair;
-  const int HW = h * w;
-  hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(device));
-  launch_zero_bytes(p.colP, (size_t)((char*)p.colN - (char*)p.colP) + sizeof(int) * (size_t)S, stream);
-  const dim3 grid((S + 255) / 256, (S + PH_ROWS - 1) / PH_ROWS);
-  {
-    ProfScope ps("pairhead_fwd_resized", stream);
-    hipLaunchKernelGGL(ph_rank_kernel, dim3(1), dim3(256), 0, stream, sampled_mask, N, p.rank, p.consts);
-    // what the backward gathers through: written here, where the workspace is still the caller's to write
-    hipLaunchKernelGGL(ph_tables_kernel, dim3((std::max(Hr, Wr) + 255) / 256), dim3(256), 0, stream, g, r.row_first, r.row_count, r.col_first,
-                       r.col_count);
-    hipLaunchKernelGGL(ph_slots_kernel, dim3((HW + 255) / 256), dim3(256), 0, stream, pix, S, (const int*)S_dev, HW, r.slot);
-    if (packed)
-      hipLaunchKernelGGL((ph_gather_kernel<true, true>), dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, g, sam_masks, N, p.rank,
-                         mask_size, pix, S, (const int*)S_dev, p.fn, p.rinv, p.a, p.bits);
-    else
-      hipLaunchKernelGGL((ph_gather_kernel<true, false>), dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, (long long)HW, g, sam_masks, N, p.rank,
-                         mask_size, pix, S, (const int*)S_dev, p.fn, p.rinv, p.a, p.bits);
-    hipLaunchKernelGGL(ph_consts_kernel, dim3(1), dim3(256), 0, stream, p.a, S, (const int*)S_dev, p.consts);
-    hipLaunchKernelGGL(ph_flags_kernel, grid, dim3(256), 0, stream, p.fn, p.bits, S, (const int*)S_dev, positive_th, negative_th, mode, p.colP,
-                       p.colN, p.partial);
-    hipLaunchKernelGGL(ph_sum_kernel, grid, dim3(256), 0, stream, p.fn, p.bits, p.a, p.consts, S, (const int*)S_dev, positive_th, negative_th,
-                       mode, use_weights, p.colP, p.colN, p.partial);
-    hipLaunchKernelGGL(ph_final_kernel, dim3(1), dim3(256), 0, stream, p.partial, p.nblk, p.colP, p.colN, S, (const int*)S_dev, mode, p.consts,
-                       out8);
-  }
-  TRASE_POST_LAUNCH("pairhead_fwd_resized", stream, 0);
-  return TRASE_OK;
-}
-
-int trase_pairhead_forward_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w,
-                                   const uint8_t* sam_masks, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
-                                   const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
-                                   float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
-                                   int32_t device, trase_stream_t stream_) {
-  return pairhead_forward_resized_impl("trase_pairhead_forward_resized", false, feats, F, Hr, Wr, h, w, sam_masks, 0, N, sampled_mask,
-                                       n_sampled_masks, mask_size, pix, S, S_dev, mode, positive_th, negative_th, use_weights, out8, ws,
-                                       ws_bytes, device, stream_);
-}
-
-int trase_pairhead_forward_bits_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const uint8_t* bits,
-                                        size_t bits_bytes, int32_t N, const uint8_t* sampled_mask, int32_t n_sampled_masks,
-                                        const uint32_t* mask_size, const int32_t* pix, int32_t S, const int32_t* S_dev, int32_t mode,
-                                        float positive_th, float negative_th, int32_t use_weights, float* out8, void* ws, size_t ws_bytes,
-                                        int32_t device, trase_stream_t stream_) {
-  return pairhead_forward_resized_impl("trase_pairhead_forward_bits_resized", true, feats, F, Hr, Wr, h, w, bits, bits_bytes, N, sampled_mask,
-                                       n_sampled_masks, mask_size, pix, S, S_dev, mode, positive_th, negative_th, use_weights, out8, ws,
-                                       ws_bytes, device, stream_);
+  return pairhead_backward(plain_call("trase_pairhead_backward", false, F, HW, pix, S, S_dev, mode, positive_th, negative_th, use_weights, ws,
+                                      ws_bytes, device, stream_),
+                           out8, g2, accumulate, nullptr, nullptr, nullptr, dL_dfeats);
 }
 
 int trase_pairhead_backward_resized(int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const int32_t* pix, int32_t S,
                                     const int32_t* S_dev, int32_t mode, float positive_th, float negative_th, int32_t use_weights,
                                     const float* out8, const float* g2, const void* ws, size_t ws_bytes, const float* feats,
                                     const float* out2, const float* g_reg, float* dL_dfeats, int32_t device, trase_stream_t stream_) {
-  if (!pix || !out8 || !g2 || !dL_dfeats) { set_error("trase_pairhead_backward_resized: null pointer"); return TRASE_ERR_INVALID; }
-  const bool reg = feats || out2 || g_reg;
-  if (reg && !(feats && out2 && g_reg)) {
-    set_error("trase_pairhead_backward_resized: the regulariser needs feats, out2 and g_reg together"); return TRASE_ERR_INVALID;
-  }
-  if (int rc = resized_sizes_ok("trase_pairhead_backward_resized", S, Hr, Wr, h, w)) return rc;
-  if (mode < 0 || mode > 2) { set_error("trase_pairhead_backward_resized: bad arguments"); return TRASE_ERR_INVALID; }
-  if (F != PH_F) { set_error("trase_pairhead_backward_resized: %d feature channels (compiled for %d)", F, PH_F); return TRASE_ERR_INVALID; }
-  const ResizeGeom g = resize_geom(Hr, Wr, h, w);
-  ResizedWs r;
-  if (!ws || ws_bytes < resized_ws_layout(const_cast<void*>(ws), S, g, r)) {
-    set_error("trase_pairhead_backward_resized: workspace too small"); return TRASE_ERR_WORKSPACE;
-  }
-  const PairWs& p = r.pair;
-  hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("pairhead_bwd_resized", stream);
-    hipLaunchKernelGGL(ph_bwd_kernel, dim3((S + 255) / 256, PH_CHUNKS), dim3(256), 0, stream, p.fn, p.bits, p.a, p.consts, S, (const int*)S_dev,
-                       positive_th, negative_th, mode, use_weights, p.colP, p.colN, out8, g2, p.dpart);
-    hipLaunchKernelGGL(ph_scatter_kernel<true>, dim3((S * PH_F + 255) / 256), dim3(256), 0, stream, p.dpart, p.fn, p.rinv, pix, S,
-                       (const int*)S_dev, 0ll, 0, r.v);
-  }
-  {
-    ProfScope ps("pairhead_spread", stream);
-    const dim3 dense((unsigned)(((int64_t)Hr * Wr + 255) / 256));
-    if (reg)
-      hipLaunchKernelGGL(ph_spread_kernel<true>, dense, dim3(256), 0, stream, r.v, r.slot, r.row_first, r.row_count, r.col_first, r.col_count, g,
-                         feats, out2, g_reg, dL_dfeats);
-    else
-      hipLaunchKernelGGL(ph_spread_kernel<false>, dense, dim3(256), 0, stream, r.v, r.slot, r.row_first, r.row_count, r.col_first, r.col_count, g,
-                         feats, out2, g_reg, dL_dfeats);
-  }
-  TRASE_POST_LAUNCH("pairhead_bwd_resized", stream, 0);
-  return TRASE_OK;
+  return pairhead_backward(resized_call("trase_pairhead_backward_resized", false, F, Hr, Wr, h, w, pix, S, S_dev, mode, positive_th, negative_th,
+                                        use_weights, ws, ws_bytes, device, stream_),
+                           out8, g2, 0, feats, out2, g_reg, dL_dfeats);
 }
 
 int trase_pairhead_columns_resized(const float* feats, int32_t F, int32_t Hr, int32_t Wr, int32_t h, int32_t w, const int32_t* pix,
                                    int32_t S, float* columns, int32_t device, trase_stream_t stream_) {
   if (!feats || !pix || !columns) { set_error("trase_pairhead_columns_resized: null pointer"); return TRASE_ERR_INVALID; }
   if (int rc = resized_sizes_ok("trase_pairhead_columns_resized", S, Hr, Wr, h, w)) return rc;
-  if (F != PH_F) { set_error("trase_pairhead_columns_resized: %d feature channels (compiled for %d)", F, PH_F); return TRASE_ERR_INVALID; }
+  if (int rc = channels_ok("trase_pairhead_columns_resized", F)) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   {

@@ -169,23 +169,16 @@ def _masks_u8(sam_masks: torch.Tensor) -> torch.Tensor:
 def mask_stats(sam_masks):
     """(cover_count [H, W] int32, mask_size [N] int32): ``sam_masks.sum(dim=0)`` and ``sam_masks.sum(-1).sum(-1)``
     (utils/feature_utils.py:23, :30) in one pass over the masks (a tensor or a PackedMasks)."""
-    if isinstance(sam_masks, PackedMasks):
-        N, H, W = sam_masks._gpu().shape
-        dev = sam_masks.device
-        cover = torch.empty((H, W), dtype=torch.int32, device=dev)
-        size = torch.empty((N,), dtype=torch.int32, device=dev)
-        lib = _lib.load()
-        _lib.check(lib.trase_mask_stats_bits(_lib.ptr(sam_masks.bits), sam_masks.bits.numel(), N, H * W, _lib.ptr(cover), _lib.ptr(size),
-                                             _dev_index(dev), _stream(dev)), "trase_mask_stats_bits")
-        return cover, size
-    m = _masks_u8(sam_masks)
+    packed = isinstance(sam_masks, PackedMasks)
+    m = sam_masks._gpu() if packed else _masks_u8(sam_masks)
     N, H, W = m.shape
     dev = m.device
     cover = torch.empty((H, W), dtype=torch.int32, device=dev)
     size = torch.empty((N,), dtype=torch.int32, device=dev)
     lib = _lib.load()
-    _lib.check(lib.trase_mask_stats(_lib.ptr(m), N, H * W, _lib.ptr(cover), _lib.ptr(size), _dev_index(dev), _stream(dev)),
-               "trase_mask_stats")
+    name = "trase_mask_stats_bits" if packed else "trase_mask_stats"
+    masks = (_lib.ptr(m.bits), m.bits.numel()) if packed else (_lib.ptr(m),)
+    _lib.check(getattr(lib, name)(*masks, N, H * W, _lib.ptr(cover), _lib.ptr(size), _dev_index(dev), _stream(dev)), name)
     return cover, size
 
 
@@ -249,128 +242,93 @@ def check_sampled_counts():
     _poll_count_checks(block=True)
 
 
+def _featnorm_forward(lib, f):
+    """out2 = [(1 - mean norm) ** 2, mean norm] of the contiguous float32 (F, ...) image ``f`` (train.py:281-282)"""
+    dev = f.device
+    F = f.shape[0]
+    HW = f.numel() // F
+    nbytes = C.c_size_t()
+    _lib.check(lib.trase_featnorm_sizes(HW, C.byref(nbytes)), "trase_featnorm_sizes")
+    ws = _bytes(nbytes.value, dev)
+    out2 = torch.empty(2, device=dev)
+    _lib.check(lib.trase_featnorm_forward(_lib.ptr(f), F, HW, _lib.ptr(out2), _lib.ptr(ws), ws.numel(), _dev_index(dev), _stream(dev)),
+               "trase_featnorm_forward")
+    return out2
+
+
+# (packed masks, resized) -> the forward's entry point
+_FORWARD = {(False, False): "trase_pairhead_forward_n", (True, False): "trase_pairhead_forward_bits",
+            (False, True): "trase_pairhead_forward_resized", (True, True): "trase_pairhead_forward_bits_resized"}
+
+
 class _PairHead(torch.autograd.Function):
+    """``resized``: the features have another size than the masks (or are to be treated so): the sampled columns are bilinear taps of
+    the (32, Hr, Wr) image, and the backward writes every element of its gradient once (taps and, with_reg, the regulariser's term in
+    one pass).  Otherwise the columns are read in place and the backward scatters them into the image."""
+
     @staticmethod
-    def forward(ctx, feats, masks_u8, sampled_mask_u8, n_sampled, mask_size, pix, mode, pth, nth, use_w, with_reg, s_dev=None):
+    def forward(ctx, feats, masks_u8, sampled_mask_u8, n_sampled, mask_size, pix, mode, pth, nth, use_w, with_reg, s_dev=None, resized=False):
         # s_dev: int32[2] on the device, s_dev[0] = number of valid entries of `pix` (trase_compact_pixels); None: all of them
-        lib = _lib.load()
-        dev = feats.device
-        F, H, W = feats.shape
-        S = pix.numel()
-        f = feats.detach().float().contiguous()
-        nbytes = C.c_size_t()
-        _lib.check(lib.trase_pairhead_sizes(S, C.byref(nbytes)), "trase_pairhead_sizes")
-        ws = _bytes(nbytes.value, dev)
-        out8 = torch.empty(8, device=dev)
-        d = _dev_index(dev)
-        if isinstance(masks_u8, PackedMasks):       # the stream in place of the bool bytes: same workspace, same backward
-            _lib.check(lib.trase_pairhead_forward_bits(_lib.ptr(f), F, H * W, _lib.ptr(masks_u8.bits), masks_u8.bits.numel(), masks_u8.N,
-                                                       _lib.ptr(sampled_mask_u8), int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S,
-                                                       _lib.ptr(s_dev), int(mode), float(pth), float(nth), int(use_w), _lib.ptr(out8),
-                                                       _lib.ptr(ws), ws.numel(), d, _stream(dev)), "trase_pairhead_forward_bits")
-        else:
-            _lib.check(lib.trase_pairhead_forward_n(_lib.ptr(f), F, H * W, _lib.ptr(masks_u8), masks_u8.shape[0], _lib.ptr(sampled_mask_u8),
-                                                    int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S, _lib.ptr(s_dev), int(mode), float(pth),
-                                                    float(nth), int(use_w), _lib.ptr(out8), _lib.ptr(ws), ws.numel(), d, _stream(dev)),
-                       "trase_pairhead_forward")
-        ctx.s_dev = s_dev
-        sims = out8[4:6].clone()
-        ctx.mark_non_differentiable(sims)
-        ctx.cfg = (F, H, W, S, int(mode), float(pth), float(nth), int(use_w), bool(with_reg))
-        if not with_reg:
-            ctx.save_for_backward(ws, out8, pix)
-            return out8[0], out8[2], sims
-        # the regulariser of train.py:281-282 on the same image: its dense gradient is written first in the backward and
-        # the S sampled columns are added into it (no zero-fill, no separate accumulation pass)
-        _lib.check(lib.trase_featnorm_sizes(H * W, C.byref(nbytes)), "trase_featnorm_sizes")
-        ws_r = _bytes(nbytes.value, dev)
-        out2 = torch.empty(2, device=dev)
-        _lib.check(lib.trase_featnorm_forward(_lib.ptr(f), F, H * W, _lib.ptr(out2), _lib.ptr(ws_r), ws_r.numel(), d, _stream(dev)),
-                   "trase_featnorm_forward")
-        ctx.save_for_backward(ws, out8, pix, f, out2)
-        return out8[0], out8[2], sims, out2[0]
-
-    @staticmethod
-    def backward(ctx, g_pos, g_neg, _g_sims, g_reg=None):
-        lib = _lib.load()
-        F, H, W, S, mode, pth, nth, use_w, with_reg = ctx.cfg
-        ws, out8, pix = ctx.saved_tensors[:3]
-        dev = ws.device
-        d, st = _dev_index(dev), _stream(dev)
-        g2 = torch.stack([g_pos.reshape(()), g_neg.reshape(())]).float().contiguous()
-        d_feats = torch.empty((F, H, W), device=dev)
-        if with_reg:
-            f, out2 = ctx.saved_tensors[3:]
-            gg = g_reg.reshape(1).float().contiguous()
-            _lib.check(lib.trase_featnorm_backward(_lib.ptr(f), F, H * W, _lib.ptr(out2), _lib.ptr(gg), _lib.ptr(d_feats), d, st),
-                       "trase_featnorm_backward")
-        _lib.check(lib.trase_pairhead_backward_n(F, H * W, _lib.ptr(pix), S, _lib.ptr(ctx.s_dev), mode, pth, nth, use_w, _lib.ptr(out8),
-                                                 _lib.ptr(g2), _lib.ptr(ws), ws.numel(), 1 if with_reg else 0, _lib.ptr(d_feats), d, st),
-                   "trase_pairhead_backward")
-        return (d_feats,) + (None,) * 11
-
-
-class _PairHeadResized(torch.autograd.Function):
-    """_PairHead for features of another size than the masks: the sampled columns are bilinear taps of the (32, Hr, Wr) image,
-    and the backward writes every element of its gradient once (taps and, with_reg, the regulariser's term in one pass)."""
-
-    @staticmethod
-    def forward(ctx, feats, masks_u8, sampled_mask_u8, n_sampled, mask_size, pix, mode, pth, nth, use_w, with_reg, s_dev=None):
         lib = _lib.load()
         dev = feats.device
         F, Hr, Wr = feats.shape
         N, h, w = masks_u8.shape
         S = pix.numel()
         f = feats.detach().float().contiguous()
+        geom = (Hr, Wr, h, w) if resized else (Hr * Wr,)
         nbytes = C.c_size_t()
-        _lib.check(lib.trase_pairhead_sizes_resized(S, Hr, Wr, h, w, C.byref(nbytes)), "trase_pairhead_sizes_resized")
+        if resized:
+            _lib.check(lib.trase_pairhead_sizes_resized(S, *geom, C.byref(nbytes)), "trase_pairhead_sizes_resized")
+        else:
+            _lib.check(lib.trase_pairhead_sizes(S, C.byref(nbytes)), "trase_pairhead_sizes")
         ws = _bytes(nbytes.value, dev)
         out8 = torch.empty(8, device=dev)
-        d = _dev_index(dev)
-        if isinstance(masks_u8, PackedMasks):
-            _lib.check(lib.trase_pairhead_forward_bits_resized(_lib.ptr(f), F, Hr, Wr, h, w, _lib.ptr(masks_u8.bits), masks_u8.bits.numel(), N,
-                                                               _lib.ptr(sampled_mask_u8), int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S,
-                                                               _lib.ptr(s_dev), int(mode), float(pth), float(nth), int(use_w), _lib.ptr(out8),
-                                                               _lib.ptr(ws), ws.numel(), d, _stream(dev)),
-                       "trase_pairhead_forward_bits_resized")
-        else:
-            _lib.check(lib.trase_pairhead_forward_resized(_lib.ptr(f), F, Hr, Wr, h, w, _lib.ptr(masks_u8), N, _lib.ptr(sampled_mask_u8),
-                                                          int(n_sampled), _lib.ptr(mask_size), _lib.ptr(pix), S, _lib.ptr(s_dev), int(mode),
-                                                          float(pth), float(nth), int(use_w), _lib.ptr(out8), _lib.ptr(ws), ws.numel(), d,
-                                                          _stream(dev)), "trase_pairhead_forward_resized")
+        packed = isinstance(masks_u8, PackedMasks)      # the stream in place of the bool bytes: same workspace, same backward
+        masks = (_lib.ptr(masks_u8.bits), masks_u8.bits.numel()) if packed else (_lib.ptr(masks_u8),)
+        name = _FORWARD[packed, resized]
+        _lib.check(getattr(lib, name)(_lib.ptr(f), F, *geom, *masks, N, _lib.ptr(sampled_mask_u8), int(n_sampled), _lib.ptr(mask_size),
+                                      _lib.ptr(pix), S, _lib.ptr(s_dev), int(mode), float(pth), float(nth), int(use_w), _lib.ptr(out8),
+                                      _lib.ptr(ws), ws.numel(), _dev_index(dev), _stream(dev)),
+                   "trase_pairhead_forward" if name == "trase_pairhead_forward_n" else name)
         ctx.s_dev = s_dev
         sims = out8[4:6].clone()
         ctx.mark_non_differentiable(sims)
-        ctx.cfg = (F, Hr, Wr, h, w, S, int(mode), float(pth), float(nth), int(use_w), bool(with_reg))
+        ctx.cfg = (F, Hr, Wr, geom, S, int(mode), float(pth), float(nth), int(use_w), bool(with_reg), bool(resized))
         if not with_reg:
             ctx.save_for_backward(ws, out8, pix)
             return out8[0], out8[2], sims
-        # the regulariser of train.py:280-282 on the image as rendered (before the resize)
-        _lib.check(lib.trase_featnorm_sizes(Hr * Wr, C.byref(nbytes)), "trase_featnorm_sizes")
-        ws_r = _bytes(nbytes.value, dev)
-        out2 = torch.empty(2, device=dev)
-        _lib.check(lib.trase_featnorm_forward(_lib.ptr(f), F, Hr * Wr, _lib.ptr(out2), _lib.ptr(ws_r), ws_r.numel(), d, _stream(dev)),
-                   "trase_featnorm_forward")
+        # the regulariser of train.py:280-282 on the image as rendered (before any resize)
+        out2 = _featnorm_forward(lib, f)
         ctx.save_for_backward(ws, out8, pix, f, out2)
         return out8[0], out8[2], sims, out2[0]
 
     @staticmethod
     def backward(ctx, g_pos, g_neg, _g_sims, g_reg=None):
         lib = _lib.load()
-        F, Hr, Wr, h, w, S, mode, pth, nth, use_w, with_reg = ctx.cfg
+        F, Hr, Wr, geom, S, mode, pth, nth, use_w, with_reg, resized = ctx.cfg
         ws, out8, pix = ctx.saved_tensors[:3]
         dev = ws.device
+        d, st = _dev_index(dev), _stream(dev)
         g2 = torch.stack([g_pos.reshape(()), g_neg.reshape(())]).float().contiguous()
         d_feats = torch.empty((F, Hr, Wr), device=dev)
         f = out2 = gg = None
         if with_reg:
             f, out2 = ctx.saved_tensors[3:]
             gg = g_reg.reshape(1).float().contiguous()
-        _lib.check(lib.trase_pairhead_backward_resized(F, Hr, Wr, h, w, _lib.ptr(pix), S, _lib.ptr(ctx.s_dev), mode, pth, nth, use_w,
-                                                       _lib.ptr(out8), _lib.ptr(g2), _lib.ptr(ws), ws.numel(), _lib.ptr(f), _lib.ptr(out2),
-                                                       _lib.ptr(gg), _lib.ptr(d_feats), _dev_index(dev), _stream(dev)),
-                   "trase_pairhead_backward_resized")
-        return (d_feats,) + (None,) * 11
+        if resized:         # one dense pass: the taps and, given its three pointers, the regulariser's term
+            _lib.check(lib.trase_pairhead_backward_resized(F, *geom, _lib.ptr(pix), S, _lib.ptr(ctx.s_dev), mode, pth, nth, use_w, _lib.ptr(out8),
+                                                           _lib.ptr(g2), _lib.ptr(ws), ws.numel(), _lib.ptr(f), _lib.ptr(out2), _lib.ptr(gg),
+                                                           _lib.ptr(d_feats), d, st), "trase_pairhead_backward_resized")
+            return (d_feats,) + (None,) * 12
+        # the regulariser's dense gradient is written first and the S sampled columns are added into it (no zero-fill, no separate
+        # accumulation pass)
+        if with_reg:
+            _lib.check(lib.trase_featnorm_backward(_lib.ptr(f), F, *geom, _lib.ptr(out2), _lib.ptr(gg), _lib.ptr(d_feats), d, st),
+                       "trase_featnorm_backward")
+        _lib.check(lib.trase_pairhead_backward_n(F, *geom, _lib.ptr(pix), S, _lib.ptr(ctx.s_dev), mode, pth, nth, use_w, _lib.ptr(out8),
+                                                 _lib.ptr(g2), _lib.ptr(ws), ws.numel(), 1 if with_reg else 0, _lib.ptr(d_feats), d, st),
+                   "trase_pairhead_backward")
+        return (d_feats,) + (None,) * 12
 
 
 @torch.no_grad()
@@ -464,9 +422,8 @@ def contrastive_head(rendered_features, sam_masks, sampled_pixel, sampled_mask, 
             z = rendered_features.sum() * 0.0
             nan = torch.full((), float("nan"), device=dev)
             return (z, z, nan, nan, feature_norm_reg(rendered_features)) if with_norm_reg else (z, z, nan, nan)
-    res = (_PairHeadResized if resized else _PairHead).apply(rendered_features, m, sm, n_sampled, mask_size.contiguous(), pix,
-                                                             _MODES[mode], positive_th, negative_th, 1 if use_weights else 0,
-                                                             bool(with_norm_reg), s_dev)
+    res = _PairHead.apply(rendered_features, m, sm, n_sampled, mask_size.contiguous(), pix, _MODES[mode], positive_th, negative_th,
+                          1 if use_weights else 0, bool(with_norm_reg), s_dev, resized)
     lp, ln, sims = res[:3]
     return (lp, ln, sims[0], sims[1], res[3]) if with_norm_reg else (lp, ln, sims[0], sims[1])
 
@@ -474,17 +431,8 @@ def contrastive_head(rendered_features, sam_masks, sampled_pixel, sampled_mask, 
 class _FeatNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats):
-        lib = _lib.load()
-        dev = feats.device
         f = feats.detach().float().contiguous()
-        F = f.shape[0]
-        HW = f.numel() // F
-        nbytes = C.c_size_t()
-        _lib.check(lib.trase_featnorm_sizes(HW, C.byref(nbytes)), "trase_featnorm_sizes")
-        ws = _bytes(nbytes.value, dev)
-        out2 = torch.empty(2, device=dev)
-        _lib.check(lib.trase_featnorm_forward(_lib.ptr(f), F, HW, _lib.ptr(out2), _lib.ptr(ws), ws.numel(), _dev_index(dev), _stream(dev)),
-                   "trase_featnorm_forward")
+        out2 = _featnorm_forward(_lib.load(), f)
         ctx.save_for_backward(f, out2)
         return out2[0]
 
