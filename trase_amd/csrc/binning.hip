@@ -26,9 +26,25 @@ __device__ __forceinline__ uint32_t dev_n(const uint32_t* n_ptr, uint32_t cap) {
   return n < cap ? n : cap;
 }
 
+// Tile of workgroup b in the three-launch passes, nb_live = ceil(n / RS_TILE) read on the device.  Consecutive workgroups go
+// round-robin over the 8 XCDs (xcd_block, common.h), while consecutive TILES share memory lines: in the digit-major histogram the
+// counters of 8 tiles for one digit are one 32-byte sector (so each 4-byte counter left its L2 as a sector of its own, and each
+// sector was fetched by up to 8 L2s), and in the scatter's output the runs of neighbouring tiles for one digit are adjacent.
+// Giving every XCD a contiguous eighth of the LIVE tiles lets those neighbours meet in one L2.  The map is over the live count,
+// not over the grid (sized by capacity): over the grid the last XCDs would hold little but dead tiles.  Bijective on
+// [0, nb_live); workgroups at or behind nb_live return.  -DTRASE_RS_NO_XCD_MAP: tile = workgroup, for A/B builds.
+__device__ __forceinline__ uint32_t rs_tile(uint32_t b, uint32_t nb_live) {
+#ifdef TRASE_RS_NO_XCD_MAP
+  return b;
+#else
+  return (uint32_t)xcd_block((int)b, (int)nb_live);
+#endif
+}
+
 // ---- pass kernel 1: per-workgroup digit histograms --------------------------------------------
 // DB = digit bits of a pass: 8 (the pair sort, KNN, 32-bit depth keys) or 9 (the default 27-bit depth keys in 3 passes)
-template <int DB>
+// SMALL: the launch of a short sort (tile = workgroup, as its scatter kernels index)
+template <int DB, bool SMALL = false>
 __global__ __launch_bounds__(RS_THREADS) void radix_hist_kernel(const uint32_t* __restrict__ keys,
                                                                 const uint32_t* __restrict__ n_ptr, uint32_t cap,
                                                                 int shift, uint32_t mask, uint32_t* __restrict__ hist,
@@ -40,8 +56,10 @@ __global__ __launch_bounds__(RS_THREADS) void radix_hist_kernel(const uint32_t* 
   // by every workgroup of the launch, also the ones behind n)
   for (uint32_t i = blockIdx.x * RS_THREADS + threadIdx.x; i < zero_words; i += gridDim.x * RS_THREADS) zero_from[i] = 0u;
   const uint32_t n = dev_n(n_ptr, cap);
-  const uint32_t base = blockIdx.x * RS_TILE;
-  if (base >= n) return;
+  const uint32_t nb_live = (n + RS_TILE - 1) / RS_TILE;
+  if (blockIdx.x >= nb_live) return;
+  const uint32_t tile = SMALL ? blockIdx.x : rs_tile(blockIdx.x, nb_live);
+  const uint32_t base = tile * RS_TILE;
   __shared__ uint32_t h[ND];
 #pragma unroll
   for (int d = threadIdx.x; d < ND; d += RS_THREADS) h[d] = 0;
@@ -76,7 +94,7 @@ __global__ __launch_bounds__(RS_THREADS) void radix_hist_kernel(const uint32_t* 
   }
   __syncthreads();
 #pragma unroll
-  for (int d = threadIdx.x; d < ND; d += RS_THREADS) hist[(size_t)d * nb_max + blockIdx.x] = h[d];
+  for (int d = threadIdx.x; d < ND; d += RS_THREADS) hist[(size_t)d * nb_max + tile] = h[d];
 }
 
 // inclusive scan over the 256 threads of a workgroup: a DPP scan inside every wave, then the three lower waves'
@@ -160,8 +178,10 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(
   constexpr int ND = 1 << DB;
   constexpr int DPT = ND / RS_THREADS;          // digits per thread in the per-digit steps: thread t owns [t DPT, (t + 1) DPT)
   const uint32_t n = dev_n(n_ptr, cap);
-  const uint32_t base = blockIdx.x * RS_TILE;
-  if (base >= n) return;
+  const uint32_t nb_live = (n + RS_TILE - 1) / RS_TILE;
+  if (blockIdx.x >= nb_live) return;
+  const uint32_t tile = SMALL ? blockIdx.x : rs_tile(blockIdx.x, nb_live);      // (SMALL: at most RS_SMALL_NB workgroups, unmapped)
+  const uint32_t base = tile * RS_TILE;
   __shared__ uint32_t wcount[RS_WAVES][ND];     // per-wave digit counts, then (in place) the counts of the earlier waves
   const int wave = threadIdx.x >> 6;
   const unsigned lane = threadIdx.x & 63;
@@ -186,7 +206,7 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(
 #pragma unroll
         for (int u = 0; u < 8; ++u) v8[u] = (b0 + u < nb) ? row[b0 + u] : 0u;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) { total += v8[u]; before += (b0 + u < (int)blockIdx.x) ? v8[u] : 0u; }
+        for (int u = 0; u < 8; ++u) { total += v8[u]; before += (b0 + u < (int)tile) ? v8[u] : 0u; }
       }
       my_digit_total[j] = total; my_hist[j] = before;
     }
@@ -194,7 +214,7 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(
 #pragma unroll
   for (int j = 0; j < DPT; ++j) {
     my_digit_total[j] = digit_total[threadIdx.x * DPT + j];
-    my_hist[j] = hist[(size_t)(threadIdx.x * DPT + j) * nb_max + blockIdx.x];
+    my_hist[j] = hist[(size_t)(threadIdx.x * DPT + j) * nb_max + tile];
   }
   }
   // every key and value of the thread is requested up front: inside the ranking loop (volatile LDS counters, wave barriers)
@@ -375,7 +395,7 @@ static int radix_sort_pairs_t(const LaunchCtx& c, const SortBufs& t, const uint3
       uint32_t* hist_n = (p + 1 < passes) ? t.hist + hw * (p + 1) : nullptr;
       if (p == 0) {
         ProfScope ps("radix_hist", c.stream);
-        hipLaunchKernelGGL(radix_hist_kernel<DB>, dim3(nb), dim3(RS_THREADS), 0, c.stream, t.keys[cur], n_ptr, n_cap, shift, mask, hist_p,
+        hipLaunchKernelGGL((radix_hist_kernel<DB, true>), dim3(nb), dim3(RS_THREADS), 0, c.stream, t.keys[cur], n_ptr, n_cap, shift, mask, hist_p,
                            t.digit_total, t.nb_max, flag_key, flag_word, t.hist + hw, (uint32_t)(hw * (passes - 1)));
       }
       TRASE_POST_LAUNCH("radix_hist", c.stream, c.debug);
