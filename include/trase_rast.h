@@ -1054,6 +1054,38 @@ int trase_vgg_backward(int32_t layers, const void* pack, size_t pack_bytes, cons
                        const float* inv_std, const void* saved, size_t saved_bytes, float* d_image, void* ws, size_t ws_bytes,
                        int32_t device, trase_stream_t stream);
 
+/* ---- LPIPS with the VGG16 backbone (lpipsPyTorch, net_type='vgg', version 0.1; metrics_segmentation.py:118-165), forward only ----
+ * Thirteen 3x3 convolutions conv1_1 conv1_2 | conv2_1 conv2_2 | conv3_1 conv3_2 conv3_3 | conv4_1 conv4_2 conv4_3 | conv5_1
+ * conv5_2 conv5_3 (| = MaxPool2d(2, 2)) on two images x, y (3, H, W) fp32, batch 1, with the kernels and the arithmetic of the
+ * extractor above.  The taps are the post-ReLU activations relu1_2 relu2_2 relu3_3 relu4_3 relu5_3 BEFORE the pool that follows:
+ * C_l = 64 128 256 512 512 channels of h_l x w_l = (H >> l) x (W >> l) pixels, l = 0 .. 4; a tap's value is hi + lo of its
+ * split planes.  Per tap and pixel, in float64 and rounded to fp32 once,
+ *   d = sum_c lin_c (a_c / (sqrt(sum_c a_c^2) + 1e-10) - b_c / (sqrt(sum_c b_c^2) + 1e-10))^2,
+ * norms first, then differences; a pixel whose channels are all 0 gives 0.  A layer's value is the float64 mean of its map, summed
+ * in a fixed order (256 chunks, then their partial sums).  No atomics: two calls give the same bits, (x, y) and (y, x) give the same bits, (x, x) gives exactly 0.
+ * trase_lpips_ws_bytes: H, W >= 16 (relu5_3 has a pixel), H * W < 2^25.  map_floats = sum_l h_l w_l.  ws_bytes: THREE buffers of
+ *   H * W * 64 split values (hi and lo bf16 planes: 256 H W bytes each; every activation behind the first pool is at most half
+ *   a buffer, so x's conv1_1 buffer is reused), the five maps and 5 x 256 float64 partial sums of their means.
+ * trase_lpips_pack: weights[l] (Cout, Cin, 3, 3), biases[l] (Cout), l = 0 .. 12, and lin[t] (C_t), t = 0 .. 4: fp32 device
+ *   tensors (HOST arrays of pointers) -> `pack`: conv1_1 and the lin vectors as fp32, layers 2 .. 13 as forward weight streams.
+ * trase_lpips_forward: mean / inv_std as in trase_vgg_forward.  out_layers: 5 float64 on the device, the layers' values; LPIPS is
+ *   their sum.  maps (optional): map_floats fp32, the five per-pixel maps one after the other.  taps_x / taps_y (optional,
+ *   together): sum_l C_l h_l w_l fp32 each, the five taps as planar (C_l, h_l w_l), one after the other.  All launches go to
+ *   `stream`; nothing is allocated or synchronised.
+ * trase_lpips_head: the head alone on two fp32 planar (C, hw) activations a, b and lin (C) (device): they are split as the
+ *   cotangent of trase_vgg_backward is and go through the same head kernel.  C in {64, 128, 256, 512}, hw >= 1, C * hw < 2^31.
+ *   out_layer: 1 float64 (device); map (optional): hw fp32.  ws: 4 r(2 C hw) + r(4 hw) + 2048 bytes, r = rounded up to 256.
+ * Refusals: TRASE_ERR_INVALID (sizes, null pointers, pack / ws not 16-byte aligned, out_layers not 8-byte aligned) and
+ * TRASE_ERR_WORKSPACE (pack or ws too small), with a message, before a device is touched. */
+int trase_lpips_ws_bytes(int32_t H, int32_t W, size_t* pack_bytes, size_t* ws_bytes, size_t* map_floats);
+int trase_lpips_pack(const float* const* weights, const float* const* biases, const float* const* lin, void* pack, size_t pack_bytes,
+                     int32_t device, trase_stream_t stream);
+int trase_lpips_forward(const void* pack, size_t pack_bytes, const float* x, const float* y, int32_t H, int32_t W, const float* mean,
+                        const float* inv_std, double* out_layers, float* maps, float* taps_x, float* taps_y, void* ws, size_t ws_bytes,
+                        int32_t device, trase_stream_t stream);
+int trase_lpips_head(const float* a, const float* b, const float* lin, int32_t C, int32_t hw, double* out_layer, float* map, void* ws,
+                     size_t ws_bytes, int32_t device, trase_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 // vgg.hip -- the style-transfer feature extractor: VGG16's 3x3 convolutions up to conv4_1, forward and gradient to the image
-// (trase_vgg_ws_bytes / _pack / _forward / _backward; trase_amd/vgg.py).
+// (trase_vgg_ws_bytes / _pack / _forward / _backward; trase_amd/vgg.py).  The LPIPS metric's stack to relu5_3 and its distance
+// head (trase_lpips_*; trase_amd/lpips.py) run on the same kernels and are described where they begin, further down.
 //
 // Network: conv1_1 conv1_2 | conv2_1 conv2_2 | conv3_1 conv3_2 conv3_3 | conv4_1 (| = MaxPool2d(2, 2), floor), 3x3, stride 1,
 // zero padding 1, bias, ReLU after each but the returned one; channels 3 -> 64 -> 64 -> 128 -> 128 -> 256 -> 256 -> 256 -> 512.
@@ -456,6 +457,193 @@ static VgNorm vg_norm(const float* mean, const float* inv_std) {
   return nm;
 }
 
+// ---- LPIPS (VGG): the stack to relu5_3 and the distance head, forward only ---------------------------------------------------
+// (trase_lpips_ws_bytes / _pack / _forward / _head; trase_amd/lpips.py).  Thirteen convolutions
+//   conv1_1 conv1_2 | conv2_1 conv2_2 | conv3_1 conv3_2 conv3_3 | conv4_1 conv4_2 conv4_3 | conv5_1 conv5_2 conv5_3
+// run layer by layer for both images with the kernels above: vgg_conv1_kernel<false>, then vgg_conv_kernel<VG_FWD_RELU> for EVERY
+// later layer -- also where a pool follows, because the tap (relu1_2, relu2_2, relu3_3, relu4_3, relu5_3) is the full-resolution
+// activation.  Behind a tapped layer:
+//   * lpips_head_kernel reads both images' channel-last hi / lo planes, a value being t = (float)hi + (float)lo, and forms per
+//     pixel  d = sum_c lin_c (a_c / (sqrt(sum a^2) + 1e-10) - b_c / (sqrt(sum b^2) + 1e-10))^2  in float64, in two passes over the
+//     channels (norms, then differences: the expanded one-pass form cancels when x is close to y), rounded to fp32 ONCE into the
+//     layer's map.  Eight lanes share a pixel, lane g of them owning channels 64 i + 8 g .. + 7 (16-byte loads, a pixel's 128-byte
+//     row per instruction); the eight partial sums meet in a fixed xor butterfly, which gives every lane the same bits and treats
+//     the two images alike: d(x, y) and d(y, x) are the same bits, d(x, x) is exactly 0.
+//   * lpips_pool_kernel writes the 2x2 floor pool of the split planes for the next layer.  It SELECTS the (hi, lo) pair of the
+//     window's maximum, compared lexicographically (hi, then lo) in ATen's scan order with update on strict >.  vg_split is monotone
+//     in both parts, so the pair selected is the pair vg_split gives the maximum of the four fp32 values: the bits the VG_FWD_POOL
+//     epilogue writes.  (Splitting max(hi + lo) again would not do: v = hi + 0.4999 ulp has lo rounded up to half an ulp, and
+//     bf16(hi + lo) then rounds the tie to even, to hi + 1 ulp when hi is odd -- the same sum as another pair of bits.)  It is a
+//     launch of its own and not part of the head: a lane of the head owns one pixel's channels, a window spans two rows.
+//   * lpips_partial_kernel and lpips_mean_kernel sum each map in float64 in a fixed order (256 chunks per map, a workgroup each;
+//     then one workgroup per layer joins the partial sums) and divide by the pixel count.  No atomics anywhere.
+constexpr int LP_LAYERS = 13;
+constexpr int LP_TAPS = 5;
+__host__ __device__ constexpr int lp_chan(int l) { return l == 0 ? 3 : l <= 2 ? 64 : l <= 4 ? 128 : l <= 7 ? 256 : 512; }
+__host__ __device__ constexpr int lp_shift(int l) { return l <= 2 ? 0 : l <= 4 ? 1 : l <= 7 ? 2 : l <= 10 ? 3 : 4; }
+__host__ __device__ constexpr bool lp_pooled(int l) { return l == 2 || l == 4 || l == 7 || l == 10; }
+constexpr int LP_TAP_LAYER[LP_TAPS] = {2, 4, 7, 10, 13};
+
+__global__ __launch_bounds__(256) void lpips_head_kernel(const __bf16* __restrict__ x_hi, const __bf16* __restrict__ x_lo,
+                                                         const __bf16* __restrict__ y_hi, const __bf16* __restrict__ y_lo, int C, int hw,
+                                                         const float* __restrict__ lin, float* __restrict__ map) {
+  // no contraction: a * ra - b * rb as ONE fused multiply-add would round the two images' terms differently, and (x, y) would no
+  // longer be the bits of (y, x), nor (x, x) exactly 0; the fused multiply-adds wanted are written out
+#pragma clang fp contract(off)
+  const int pix = blockIdx.x * 32 + (threadIdx.x >> 3), cg = threadIdx.x & 7;
+  const size_t row = (size_t)min(pix, hw - 1) * C;          // a pixel past the end reads the last one and stores nothing
+  double na = 0.0, nb = 0.0;
+  for (int c0 = 8 * cg; c0 < C; c0 += 64) {
+    const bf16x8 ah = *reinterpret_cast<const bf16x8*>(x_hi + row + c0), al = *reinterpret_cast<const bf16x8*>(x_lo + row + c0);
+    const bf16x8 bh = *reinterpret_cast<const bf16x8*>(y_hi + row + c0), bl = *reinterpret_cast<const bf16x8*>(y_lo + row + c0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const double a = (double)((float)ah[e] + (float)al[e]), b = (double)((float)bh[e] + (float)bl[e]);
+      na = fma(a, a, na); nb = fma(b, b, nb);
+    }
+  }
+#pragma unroll
+  for (int off = 1; off < 8; off <<= 1) { na += __shfl_xor(na, off); nb += __shfl_xor(nb, off); }
+  const double ra = 1.0 / (sqrt(na) + 1e-10), rb = 1.0 / (sqrt(nb) + 1e-10);      // the epsilon outside the root: a zero pixel gives 0
+  double d = 0.0;
+  for (int c0 = 8 * cg; c0 < C; c0 += 64) {
+    const bf16x8 ah = *reinterpret_cast<const bf16x8*>(x_hi + row + c0), al = *reinterpret_cast<const bf16x8*>(x_lo + row + c0);
+    const bf16x8 bh = *reinterpret_cast<const bf16x8*>(y_hi + row + c0), bl = *reinterpret_cast<const bf16x8*>(y_lo + row + c0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const double a = (double)((float)ah[e] + (float)al[e]), b = (double)((float)bh[e] + (float)bl[e]);
+      const double t = a * ra - b * rb;
+      d = fma((double)lin[c0 + e], t * t, d);
+    }
+  }
+#pragma unroll
+  for (int off = 1; off < 8; off <<= 1) d += __shfl_xor(d, off);
+  if (cg == 0 && pix < hw) map[pix] = (float)d;
+}
+
+// one thread per pooled pixel and 8 channels: (H, W) -> (H / 2, W / 2), an odd last row or column lies in no window
+__global__ __launch_bounds__(256) void lpips_pool_kernel(const __bf16* __restrict__ in_hi, const __bf16* __restrict__ in_lo, int H, int W,
+                                                         int C, __bf16* __restrict__ out_hi, __bf16* __restrict__ out_lo) {
+  const int PH = H >> 1, PW = W >> 1, G = C >> 3;
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)PH * PW * G) return;
+  const int g = (int)(idx % G);
+  const size_t pp = idx / G;
+  const int Y = (int)(pp / PW), X = (int)(pp - (size_t)Y * PW);
+  bf16x8 bh, bl;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const size_t o = ((size_t)(2 * Y + (i >> 1)) * W + (2 * X + (i & 1))) * C + 8 * g;
+    const bf16x8 vh = *reinterpret_cast<const bf16x8*>(in_hi + o), vl = *reinterpret_cast<const bf16x8*>(in_lo + o);
+    if (i == 0) { bh = vh; bl = vl; continue; }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float h1 = (float)vh[e], h0 = (float)bh[e];
+      if (h1 > h0 || (h1 == h0 && (float)vl[e] > (float)bl[e])) { bh[e] = vh[e]; bl[e] = vl[e]; }
+    }
+  }
+  *reinterpret_cast<bf16x8*>(out_hi + pp * C + 8 * g) = bh;
+  *reinterpret_cast<bf16x8*>(out_lo + pp * C + 8 * g) = bl;
+}
+
+// channel-last split planes -> fp32 planar (C, hw) of hi + lo, the values the head reads; one thread per pixel and 8 channels
+__global__ __launch_bounds__(256) void lpips_tap_kernel(const __bf16* __restrict__ in_hi, const __bf16* __restrict__ in_lo, int C, int hw,
+                                                        float* __restrict__ out) {
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const int c8 = blockIdx.y * 8;
+  if (pix >= hw) return;
+  const bf16x8 vh = *reinterpret_cast<const bf16x8*>(in_hi + (size_t)pix * C + c8), vl = *reinterpret_cast<const bf16x8*>(in_lo + (size_t)pix * C + c8);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) out[(size_t)(c8 + e) * hw + pix] = (float)vh[e] + (float)vl[e];
+}
+
+// the mean of a map in two fixed-order steps: workgroup (b, t) sums chunk b of layer t's map (LP_PARTS chunks of 256 ceil(n / 65536)
+// elements; thread i: elements i, i + 256, .. of the chunk, then a tree over the 256 threads) into parts[t][b]; one workgroup per
+// layer then joins the LP_PARTS partial sums in a tree and divides by n
+constexpr int LP_PARTS = 256;
+struct LpMeans { const float* map[LP_TAPS]; int n[LP_TAPS]; };
+__device__ __forceinline__ double lp_block_sum(double v, double* s) {
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+    __syncthreads();
+  }
+  return s[0];
+}
+__global__ __launch_bounds__(256) void lpips_partial_kernel(LpMeans m, double* __restrict__ parts) {
+  __shared__ double s[256];
+  const float* __restrict__ map = m.map[blockIdx.y];
+  const int n = m.n[blockIdx.y];
+  const int chunk = 256 * ((n + 256 * LP_PARTS - 1) / (256 * LP_PARTS));
+  const int lo = min((int)blockIdx.x * chunk, n), hi = min(lo + chunk, n);     // chunk * LP_PARTS < 2^25 + 2^16
+  double acc = 0.0;
+  for (int i = lo + threadIdx.x; i < hi; i += 256) acc += (double)map[i];
+  const double sum = lp_block_sum(acc, s);
+  if (threadIdx.x == 0) parts[blockIdx.y * LP_PARTS + blockIdx.x] = sum;
+}
+__global__ __launch_bounds__(256) void lpips_mean_kernel(LpMeans m, const double* __restrict__ parts, double* __restrict__ out) {
+  __shared__ double s[256];
+  const double sum = lp_block_sum(parts[blockIdx.x * LP_PARTS + threadIdx.x], s);
+  if (threadIdx.x == 0) out[blockIdx.x] = sum / (double)m.n[blockIdx.x];
+}
+
+struct LpPack { float* w1; float* bias[LP_LAYERS + 1]; __bf16* fwd[LP_LAYERS + 1]; float* lin[LP_TAPS]; };
+static size_t lp_pack_layout(void* p, LpPack& f) {
+  WsCursor c(p);
+  f.w1 = c.take<float>(64 * 27);
+  for (int l = 1; l <= LP_LAYERS; ++l) {
+    f.bias[l] = c.take<float>(lp_chan(l));
+    if (l > 1) f.fwd[l] = c.take<__bf16>((size_t)9 * lp_chan(l - 1) * lp_chan(l) * 2);
+  }
+  for (int t = 0; t < LP_TAPS; ++t) f.lin[t] = c.take<float>(lp_chan(LP_TAP_LAYER[t]));
+  return c.bytes();
+}
+
+static inline size_t lp_pixels(int l, int H, int W) { return (size_t)(H >> lp_shift(l)) * (size_t)(W >> lp_shift(l)); }
+static size_t lp_map_floats(int H, int W) {
+  size_t n = 0;
+  for (int t = 0; t < LP_TAPS; ++t) n += lp_pixels(LP_TAP_LAYER[t], H, W);
+  return n;
+}
+
+// the workspace of trase_lpips_forward: THREE buffers of H * W * 64 split values (hi and lo planes each), the five maps and the
+// partial sums of their means.  The largest activation is a full-resolution 64-channel one and every activation behind the
+// first pool is at most half of it, so: conv1_1 of image im -> buffer im; conv1_2 of x: 0 -> 2, of y: 1 -> 0 (x's conv1_1 output
+// is spent by then); from the first pool on, image im ping-pongs between the im-th halves of buffers 1 and 2.
+struct LpWs { __bf16* hi[3]; __bf16* lo[3]; float* maps; double* parts; };
+static size_t lp_ws_layout(void* p, int H, int W, LpWs& w) {
+  const size_t units = (size_t)H * W * 64;
+  WsCursor c(p);
+  for (int i = 0; i < 3; ++i) { w.hi[i] = c.take<__bf16>(units); w.lo[i] = c.take<__bf16>(units); }
+  w.maps = c.take<float>(lp_map_floats(H, W));
+  w.parts = c.take<double>(LP_TAPS * LP_PARTS);
+  return c.bytes();
+}
+
+// the workspace of trase_lpips_head: both inputs' split planes, the map and the partial sums of its mean
+struct LpHeadWs { __bf16* hi[2]; __bf16* lo[2]; float* map; double* parts; };
+static size_t lp_head_layout(void* p, int C, int hw, LpHeadWs& w) {
+  WsCursor c(p);
+  for (int im = 0; im < 2; ++im) { w.hi[im] = c.take<__bf16>((size_t)C * hw); w.lo[im] = c.take<__bf16>((size_t)C * hw); }
+  w.map = c.take<float>((size_t)hw);
+  w.parts = c.take<double>(LP_PARTS);
+  return c.bytes();
+}
+
+static int lp_check_shape(const char* who, int H, int W) {
+  if (H < 16 || W < 16 || (int64_t)H * W >= ((int64_t)1 << 25)) {
+    set_error("%s: need H, W >= 16 and H * W < 2^25 (got %d x %d)", who, H, W); return TRASE_ERR_INVALID;
+  }
+  return TRASE_OK;
+}
+
+static const char* const LP_CONV_NAMES[LP_LAYERS + 1] = {"", "lpips_conv1_1", "lpips_conv1_2", "lpips_conv2_1", "lpips_conv2_2", "lpips_conv3_1",
+                                                         "lpips_conv3_2", "lpips_conv3_3", "lpips_conv4_1", "lpips_conv4_2", "lpips_conv4_3",
+                                                         "lpips_conv5_1", "lpips_conv5_2", "lpips_conv5_3"};
+static const char* const LP_HEAD_NAMES[LP_TAPS] = {"lpips_head_relu1_2", "lpips_head_relu2_2", "lpips_head_relu3_3", "lpips_head_relu4_3",
+                                                   "lpips_head_relu5_3"};
+
 }  // namespace trase
 
 using namespace trase;
@@ -608,6 +796,164 @@ int trase_vgg_backward(int32_t layers, const void* pack, size_t pack_bytes, cons
                        (const float4*)p.w1t, d_image);
   }
   TRASE_POST_LAUNCH("vgg_bwd_conv1_1", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_lpips_ws_bytes(int32_t H, int32_t W, size_t* pack_bytes, size_t* ws_bytes, size_t* map_floats) {
+  const char* who = "trase_lpips_ws_bytes";
+  int rc = lp_check_shape(who, H, W);
+  if (rc) return rc;
+  if (!pack_bytes || !ws_bytes || !map_floats) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  LpPack p; LpWs ws;
+  *pack_bytes = lp_pack_layout(nullptr, p);
+  *ws_bytes = lp_ws_layout(nullptr, H, W, ws);
+  *map_floats = lp_map_floats(H, W);
+  return TRASE_OK;
+}
+
+int trase_lpips_pack(const float* const* weights, const float* const* biases, const float* const* lin, void* pack, size_t pack_bytes,
+                     int32_t device, trase_stream_t stream_) {
+  const char* who = "trase_lpips_pack";
+  if (!weights || !biases || !lin || !pack) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  for (int l = 0; l < LP_LAYERS; ++l)
+    if (!weights[l] || !biases[l]) { set_error("%s: null layer %d", who, l); return TRASE_ERR_INVALID; }
+  for (int t = 0; t < LP_TAPS; ++t)
+    if (!lin[t]) { set_error("%s: null lin %d", who, t); return TRASE_ERR_INVALID; }
+  if (((size_t)pack & 15) != 0) { set_error("%s: the pack buffer must be 16-byte aligned", who); return TRASE_ERR_INVALID; }
+  LpPack p;
+  const size_t need = lp_pack_layout(pack, p);
+  if (pack_bytes < need) { set_error("%s: pack buffer too small (%zu bytes, need %zu)", who, pack_bytes, need); return TRASE_ERR_WORKSPACE; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  ProfScope ps("lpips_pack", stream);
+  hipLaunchKernelGGL(vgg_copy_kernel, dim3((64 * 27 + 255) / 256), dim3(256), 0, stream, weights[0], p.w1, 64 * 27);
+  for (int l = 1; l <= LP_LAYERS; ++l)
+    hipLaunchKernelGGL(vgg_copy_kernel, dim3((lp_chan(l) + 255) / 256), dim3(256), 0, stream, biases[l - 1], p.bias[l], lp_chan(l));
+  for (int l = 2; l <= LP_LAYERS; ++l) {
+    const unsigned nb = (unsigned)(((size_t)9 * lp_chan(l - 1) * lp_chan(l) + 255) / 256);
+    hipLaunchKernelGGL(vgg_pack_kernel, dim3(nb), dim3(256), 0, stream, weights[l - 1], lp_chan(l - 1), lp_chan(l), 0, p.fwd[l]);
+  }
+  for (int t = 0; t < LP_TAPS; ++t) {
+    const int c = lp_chan(LP_TAP_LAYER[t]);
+    hipLaunchKernelGGL(vgg_copy_kernel, dim3((c + 255) / 256), dim3(256), 0, stream, lin[t], p.lin[t], c);
+  }
+  TRASE_POST_LAUNCH("lpips_pack", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_lpips_forward(const void* pack, size_t pack_bytes, const float* x, const float* y, int32_t H, int32_t W, const float* mean,
+                        const float* inv_std, double* out_layers, float* maps, float* taps_x, float* taps_y, void* ws, size_t ws_bytes,
+                        int32_t device, trase_stream_t stream_) {
+  const char* who = "trase_lpips_forward";
+  int rc = lp_check_shape(who, H, W);
+  if (rc) return rc;
+  if (!pack || !x || !y || !out_layers || !ws) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  if ((mean == nullptr) != (inv_std == nullptr)) { set_error("%s: mean and inv_std come together (both null: no normalisation)", who); return TRASE_ERR_INVALID; }
+  if ((taps_x == nullptr) != (taps_y == nullptr)) { set_error("%s: taps_x and taps_y come together", who); return TRASE_ERR_INVALID; }
+  if (((size_t)pack & 15) != 0 || ((size_t)ws & 15) != 0) { set_error("%s: pack and ws must be 16-byte aligned", who); return TRASE_ERR_INVALID; }
+  if (((size_t)out_layers & 7) != 0 || (((size_t)x | (size_t)y | (size_t)maps | (size_t)taps_x | (size_t)taps_y) & 3) != 0) {
+    set_error("%s: out_layers must be 8-byte aligned, the fp32 buffers 4-byte aligned", who); return TRASE_ERR_INVALID;
+  }
+  LpPack p; LpWs b;
+  if (pack_bytes < lp_pack_layout(const_cast<void*>(pack), p)) { set_error("%s: pack buffer too small", who); return TRASE_ERR_WORKSPACE; }
+  const size_t ws_need = lp_ws_layout(ws, H, W, b);
+  if (ws_bytes < ws_need) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws_bytes, ws_need); return TRASE_ERR_WORKSPACE; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  const VgNorm nm = vg_norm(mean, inv_std);
+  const float* img[2] = {x, y};
+  float* taps[2] = {taps_x, taps_y};
+  float* const map_base = maps ? maps : b.maps;
+  LpMeans means;
+  struct Planes { __bf16* hi; __bf16* lo; };
+  const size_t half = (size_t)H * W * 32;          // elements of half a buffer
+  auto halves = [&](int buf, int im) { return Planes{b.hi[buf] + im * half, b.lo[buf] + im * half}; };
+  Planes cur[2] = {};                               // where each image's newest activation lives
+  int deep = 0, tap = 0;                            // behind the first pool: the buffer (1 or 2) whose halves hold `cur`
+  size_t map_off = 0, tap_off = 0;
+  for (int l = 1; l <= LP_LAYERS; ++l) {
+    const int h = H >> lp_shift(l), w = W >> lp_shift(l), hw = h * w, c = lp_chan(l);
+    {
+      ProfScope ps(LP_CONV_NAMES[l], stream);
+      for (int im = 0; im < 2; ++im) {
+        if (l == 1) {
+          cur[im] = Planes{b.hi[im], b.lo[im]};
+          hipLaunchKernelGGL(vgg_conv1_kernel<false>, dim3((unsigned)((hw + 255) / 256)), dim3(256), 0, stream, img[im], H, W, nm, p.w1,
+                             p.bias[1], cur[im].hi, cur[im].lo, (float*)nullptr, (uint16_t*)nullptr);
+        } else {
+          const Planes dst = l == 2 ? (im == 0 ? Planes{b.hi[2], b.lo[2]} : Planes{b.hi[0], b.lo[0]}) : halves(3 - deep, im);
+          VgConv a{};
+          a.in_hi = cur[im].hi; a.in_lo = cur[im].lo;
+          a.stream = p.fwd[l]; a.bias = p.bias[l];
+          a.H = h; a.W = w; a.Cin = lp_chan(l - 1); a.Cout = c; a.lg_steps = vg_lg(a.Cin / 16);
+          a.out_hi = dst.hi; a.out_lo = dst.lo;
+          vg_launch_conv<VG_FWD_RELU>(a, stream);
+          cur[im] = dst;
+        }
+      }
+    }
+    TRASE_POST_LAUNCH("lpips_conv", stream, 0);
+    if (l > 2) deep = 3 - deep;
+    if (l != LP_TAP_LAYER[tap]) continue;
+    {
+      ProfScope ps(LP_HEAD_NAMES[tap], stream);
+      hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)((hw + 31) / 32)), dim3(256), 0, stream, cur[0].hi, cur[0].lo, cur[1].hi, cur[1].lo, c,
+                         hw, p.lin[tap], map_base + map_off);
+      for (int im = 0; im < 2; ++im) {
+        if (taps[im])
+          hipLaunchKernelGGL(lpips_tap_kernel, dim3((unsigned)((hw + 255) / 256), c / 8), dim3(256), 0, stream, cur[im].hi, cur[im].lo, c, hw,
+                             taps[im] + tap_off);
+        if (lp_pooled(l)) {                         // the first pool goes to buffer 1, whose conv1_1 output of y is spent
+          const Planes dst = halves(l == 2 ? 1 : 3 - deep, im);
+          const size_t n = (size_t)(h >> 1) * (w >> 1) * (c / 8);
+          hipLaunchKernelGGL(lpips_pool_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, cur[im].hi, cur[im].lo, h, w, c, dst.hi,
+                             dst.lo);
+          cur[im] = dst;
+        }
+      }
+    }
+    TRASE_POST_LAUNCH("lpips_head", stream, 0);
+    means.map[tap] = map_base + map_off; means.n[tap] = hw;
+    map_off += (size_t)hw; tap_off += (size_t)hw * c;
+    if (lp_pooled(l)) deep = l == 2 ? 1 : 3 - deep;
+    ++tap;
+  }
+  {
+    ProfScope ps("lpips_mean", stream);
+    hipLaunchKernelGGL(lpips_partial_kernel, dim3(LP_PARTS, LP_TAPS), dim3(256), 0, stream, means, b.parts);
+    hipLaunchKernelGGL(lpips_mean_kernel, dim3(LP_TAPS), dim3(256), 0, stream, means, (const double*)b.parts, out_layers);
+  }
+  TRASE_POST_LAUNCH("lpips_mean", stream, 0);
+  return TRASE_OK;
+}
+
+int trase_lpips_head(const float* a, const float* b, const float* lin, int32_t C, int32_t hw, double* out_layer, float* map, void* ws,
+                     size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  const char* who = "trase_lpips_head";
+  if ((C != 64 && C != 128 && C != 256 && C != 512) || hw < 1 || (int64_t)C * hw >= ((int64_t)1 << 31)) {
+    set_error("%s: need C in {64, 128, 256, 512}, hw >= 1 and C * hw < 2^31 (got C %d, hw %d)", who, C, hw); return TRASE_ERR_INVALID;
+  }
+  if (!a || !b || !lin || !out_layer || !ws) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
+  if (((size_t)ws & 15) != 0) { set_error("%s: ws must be 16-byte aligned", who); return TRASE_ERR_INVALID; }
+  if (((size_t)out_layer & 7) != 0 || (((size_t)a | (size_t)b | (size_t)lin | (size_t)map) & 3) != 0) {
+    set_error("%s: out_layer must be 8-byte aligned, the fp32 buffers 4-byte aligned", who); return TRASE_ERR_INVALID;
+  }
+  LpHeadWs w;
+  const size_t ws_need = lp_head_layout(ws, C, hw, w);
+  if (ws_bytes < ws_need) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws_bytes, ws_need); return TRASE_ERR_WORKSPACE; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  ProfScope ps("lpips_head", stream);
+  const float* in[2] = {a, b};
+  for (int im = 0; im < 2; ++im)
+    hipLaunchKernelGGL(vgg_cot_split_kernel, dim3((hw + 255) / 256, C / 8), dim3(256), 0, stream, in[im], C, hw, w.hi[im], w.lo[im]);
+  float* const m = map ? map : w.map;
+  hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)((hw + 31) / 32)), dim3(256), 0, stream, w.hi[0], w.lo[0], w.hi[1], w.lo[1], C, hw, lin, m);
+  LpMeans means{};
+  means.map[0] = m; means.n[0] = hw;
+  hipLaunchKernelGGL(lpips_partial_kernel, dim3(LP_PARTS, 1), dim3(256), 0, stream, means, w.parts);
+  hipLaunchKernelGGL(lpips_mean_kernel, dim3(1), dim3(256), 0, stream, means, (const double*)w.parts, out_layer);
+  TRASE_POST_LAUNCH("lpips_head", stream, 0);
   return TRASE_OK;
 }
 

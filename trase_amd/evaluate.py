@@ -10,7 +10,8 @@ for its RGB, blanks the outside and turns both images into 8-bit frames on the h
 ``FrameScores`` collects what metrics_segmentation.py:33-48 and :118-150 compute from the written files -- IoU and pixel
 accuracy of the predicted mask, PSNR and SSIM of the cut-out against the benchmark's object image -- in a small device
 buffer, one record per frame, read back ONCE by ``result()``.  ``segment_scores`` / ``image_scores`` score images a caller
-already has with the same kernel.  LPIPS is not computed.
+already has with the same kernel.  With ``FrameScores(..., lpips=net)`` (an ``LPIPSVGG``, trase_amd/lpips.py) the frame's
+LPIPS (``lpips(render, gt, net_type='vgg')``, metrics_segmentation.py:118-165) goes into the same record.
 
 Deliberate deviations: the mask comes from ``1 - T_final`` and not from a second render; a ground-truth
 mask is "non-zero = object"; a NaN pixel is outside the mask and 0 in the 8-bit frames.
@@ -31,11 +32,11 @@ from .segment import _device_index
 RECORD_WORDS = 8            # TRASE_EVAL_RECORD_WORDS
 PARTIAL_SLOTS = 2048        # TRASE_EVAL_MAX_BLOCKS
 # words of a frame's record
-INTER, UNION, EQUAL, PIXELS, SSE, VALUES, _RESERVED, SSIM = range(RECORD_WORDS)
+INTER, UNION, EQUAL, PIXELS, SSE, VALUES, LPIPS, SSIM = range(RECORD_WORDS)
 GT_NONE, GT_F32_CHW, GT_U8_CHW, GT_U8_HWC = range(4)
 
 
-def scores_from_records(records, sse_float=None, *, quantize: bool = True, ssim: bool = True) -> dict:
+def scores_from_records(records, sse_float=None, *, quantize: bool = True, ssim: bool = True, lpips: bool = False) -> dict:
     """The scores of metrics_segmentation.py from (n, 8) int64 records (host), in float64.
 
     Per frame: ``IOU = inter / union`` (0 when the union is empty, ``compute_iou``), ``ACC = equal / pixels``
@@ -44,7 +45,7 @@ def scores_from_records(records, sse_float=None, *, quantize: bool = True, ssim:
     float64 per frame) for the unquantised one, ``SSIM`` = the float64 stored in the record.  A frame that recorded no mask
     pair (no image pair) has ``None`` in the mask (image) lists; the means run over the frames that have the score and
     are ``None`` when no frame has it.  Returns ``{"IOU", "ACC", "PSNR_frames", "SSIM_frames": per-frame lists; "mIOU",
-    "mACC", "PSNR", "SSIM": means}``."""
+    "mACC", "PSNR", "SSIM": means}``; with ``lpips`` also ``"LPIPS_frames"`` and ``"LPIPS"``, the float64 stored in word 6."""
     rec = np.ascontiguousarray(np.asarray(records, dtype=np.int64).reshape(-1, RECORD_WORDS))
     ssim_f64 = rec.view(np.float64)[:, SSIM]
     iou, acc, psnr, ssims = [], [], [], []
@@ -63,8 +64,13 @@ def scores_from_records(records, sse_float=None, *, quantize: bool = True, ssim:
         xs = [x for x in xs if x is not None]
         return float(np.mean(np.asarray(xs, dtype=np.float64))) if xs else None
 
-    return {"IOU": iou, "ACC": acc, "PSNR_frames": psnr, "SSIM_frames": ssims,
-            "mIOU": mean(iou), "mACC": mean(acc), "PSNR": mean(psnr), "SSIM": mean(ssims)}
+    out = {"IOU": iou, "ACC": acc, "PSNR_frames": psnr, "SSIM_frames": ssims,
+           "mIOU": mean(iou), "mACC": mean(acc), "PSNR": mean(psnr), "SSIM": mean(ssims)}
+    if lpips:
+        lpips_f64 = rec.view(np.float64)[:, LPIPS]
+        frames = [float(lpips_f64[i]) if r[VALUES] > 0 else None for i, r in enumerate(rec)]
+        out["LPIPS_frames"], out["LPIPS"] = frames, mean(frames)
+    return out
 
 
 class FrameScores:
@@ -73,12 +79,15 @@ class FrameScores:
     (``reset()`` zeroes everything).  ``quantize`` (default): the image pair is compared as the 8-bit files the reference
     reads back, ``floor(255 x + 0.5)`` clamped to 0..255, and the squared error is an exact integer; ``quantize=False``
     compares the fp32 values, summed in float64 per workgroup and combined in workgroup order.  ``ssim=False`` skips the SSIM
-    launch.  Everything recorded is bitwise reproducible.
+    launch.  ``lpips`` (an ``LPIPSVGG``): the frame's LPIPS of the pair SSIM sees (quantised unless ``quantize=False``) goes
+    into word 6 of the record as a device float64, without a synchronisation; ``result()`` then also returns
+    ``"LPIPS_frames"`` and ``"LPIPS"``.  With ``lpips=None`` records, keys and launches are what they are without it.
+    Everything recorded is bitwise reproducible.
 
     ``result()`` makes ONE device-to-host copy and returns ``{"IOU", "ACC", "PSNR_frames", "SSIM_frames": per-frame
     lists; "mIOU", "mACC", "PSNR", "SSIM": means in float64}`` (``scores_from_records``)."""
 
-    def __init__(self, capacity: int, *, device, quantize: bool = True, ssim: bool = True):
+    def __init__(self, capacity: int, *, device, quantize: bool = True, ssim: bool = True, lpips=None):
         if int(capacity) < 1:
             raise ValueError("FrameScores: capacity must be at least 1")
         self.capacity, self.quantize, self.ssim = int(capacity), bool(quantize), bool(ssim)
@@ -87,6 +96,8 @@ class FrameScores:
         words = RECORD_WORDS + (0 if self.quantize else PARTIAL_SLOTS)
         self.buffer = torch.zeros(self.capacity, words, dtype=torch.int64, device=self.device)
         self._ssim = self.buffer.view(torch.float64)[:, SSIM]
+        self.lpips = lpips
+        self._lpips = self.buffer.view(torch.float64)[:, LPIPS]
 
     @property
     def records(self) -> torch.Tensor:
@@ -111,7 +122,8 @@ class FrameScores:
             sse_float = np.zeros(self.capacity, dtype=np.float64)
             for b in range(PARTIAL_SLOTS):               # workgroup order
                 sse_float += parts[:, b]
-        return scores_from_records(host[:, :RECORD_WORDS], sse_float, quantize=self.quantize, ssim=self.ssim)
+        return scores_from_records(host[:, :RECORD_WORDS], sse_float, quantize=self.quantize, ssim=self.ssim,
+                                   lpips=self.lpips is not None)
 
 
 def _cuda(t, what, dev=None):
@@ -181,7 +193,7 @@ def _evaluate(dev, H, W, *, image=None, img_ws=None, final_T=None, pred_in=None,
                 raise ValueError("gt_object needs an image to compare with")
             gt_object, f.gt_object_kind = _gt_object(gt_object, H, W, dev)
             f.gt_object = _lib.ptr(gt_object)
-            if scores.ssim:
+            if scores.ssim or scores.lpips is not None:
                 pair = torch.empty(2, 3, H, W, device=dev)
                 f.pair_object, f.pair_gt = _lib.ptr(pair[0]), _lib.ptr(pair[1])
         keep += [gt_mask, gt_object]
@@ -191,10 +203,14 @@ def _evaluate(dev, H, W, *, image=None, img_ws=None, final_T=None, pred_in=None,
         ws.img, ws.img_bytes = _lib.ptr(img_ws), img_ws.numel()
     _lib.check(lib.trase_evaluate_frame(C.byref(f), C.byref(ws) if ws is not None else None, _device_index(dev), _stream(dev)),
                "trase_evaluate_frame")
-    if pair is not None:
+    if pair is not None and scores.ssim:
         from .losses import ssim as _ssim
         with torch.no_grad():
             scores._ssim[frame].copy_(_ssim(pair[0], pair[1]))      # a device scalar into the record: nothing synchronises
+    if pair is not None and scores.lpips is not None:
+        from .lpips import total_of
+        with torch.no_grad():
+            scores._lpips[frame].copy_(total_of(scores.lpips.to(dev).layers_device(pair[0], pair[1])))
     return out
 
 
