@@ -1,5 +1,5 @@
-"""Generates workspace_sizes.json: what every ``trase_*_sizes`` function and ``trase_rast_geom_layout`` of the built library
-return over a table of shapes.  The table pins the workspace layouts: tests/test_workspace_layout.py asserts that the library
+"""Generates workspace_sizes.json: what every ``trase_*_sizes`` function, ``trase_rast_geom_layout`` and the two VGG16 families'
+``trase_vgg_ws_bytes`` / ``trase_lpips_ws_bytes`` of the built library return over a table of shapes.  The table pins the workspace layouts: tests/test_workspace_layout.py asserts that the library
 under test returns exactly these integers, so regenerate it only from a commit whose layouts are known to be right.
 
     python tests/golden/make_workspace_sizes.py          (TRASE_RAST_LIB=<path> selects another build of the library)
@@ -9,7 +9,8 @@ list among them is an int32 input array), ``out`` the integers the function wrot
 marks a call made with null output pointers.  The shapes cross every rule of the layouts: item counts of 0 (where
 accepted), 1 and either side of the radix sort's workgroup tile (2048), of its short-sort boundary (16 x 2048 = 32768) and of
 the scan partials' 1024; about 2.5 M; feature widths 0, 16 and 32; odd image sizes; point counts across the steps of the KNN
-hash's bucket bits; the limits of every segmentation, display and HDBSCAN entry, one step inside and one step outside.
+hash's bucket bits; the limits of every segmentation, display and HDBSCAN entry, one step inside and one step outside; every cut of the VGG16
+extractor (and 0 and 9) at the smallest image its pools accept, one pixel either side, odd sizes, 1080p and H * W = 2^25 - 4096, 2^25.
 """
 import ctypes as C
 import json
@@ -20,6 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from trase_amd import _lib  # noqa: E402
 
+ALSO = ("trase_rast_geom_layout", "trase_vgg_ws_bytes", "trase_lpips_ws_bytes")     # sizes functions not named *_sizes
 OUT_SLOTS = 16          # length of the array handed to an int64* output (trase_compose_sizes writes n_parts + 1 <= 9 of them)
 
 
@@ -91,7 +93,17 @@ def cases():
     t["trase_feature_gram_sizes"] = ([[n, d] for n in (2, 255, 256, 257, 65536, 65537, 2500000) for d in dims] + [[1, 32], [1000, 0], [1000, 65]])
     t["trase_compose_sizes"] = [[[5], 1, 32], [[3, 0, 7, 100000], 4, 0], [[1] * 8, 8, 64], [[1] * 8, 9, 32], [[4, -1], 2, 32], [[4], 1, 65],
                                 [[4], 0, 32], [[1 << 24, 1 << 24], 2, 32], [[(1 << 24) - 1, 1 << 24], 2, 32]]
+    cuts = list(range(8, -1, -1)) + [9]              # a good call first: the null-output row repeats the first row
+    pools = lambda k: sum(1 for p in (2, 4, 7) if p < k)
+    t["trase_vgg_ws_bytes"] = ([[k, h, w] for (h, w) in ((67, 35), (8, 8), (9, 15), (1080, 1920), (4096, 8191), (4096, 8192)) for k in cuts] +
+                               [[k, s, s] for k in cuts for s in ((1 << pools(k)) - 1, 1 << pools(k), (1 << pools(k)) + 1)])
+    t["trase_lpips_ws_bytes"] = [[h, w] for (h, w) in ((16, 16), (15, 16), (16, 15), (17, 31), (67, 35), (1080, 1920), (4096, 8191), (4096, 8192))]
     return t
+
+
+def declared():
+    """the functions the table covers, out of the library's symbol list"""
+    return sorted(n for n, _, _ in _lib.SYMBOLS if n.endswith("_sizes") or n in ALSO)
 
 
 def build_table(lib):
@@ -109,9 +121,8 @@ def build_table(lib):
 
 def main():
     lib = _lib.load()
-    declared = sorted(n for n, _, _ in _lib.SYMBOLS if n.endswith("_sizes") or n == "trase_rast_geom_layout")
     table = build_table(lib)
-    assert sorted(table) == declared, sorted(set(declared) ^ set(table))
+    assert sorted(table) == declared(), sorted(set(declared()) ^ set(table))
     out = os.path.join(HERE, "workspace_sizes.json")
     with open(out, "w") as f:
         f.write("{\n" + ",\n".join(json.dumps(k) + ": [\n" + ",\n".join("  " + json.dumps(c) for c in v) + "\n]"

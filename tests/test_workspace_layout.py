@@ -1,7 +1,8 @@
 """Every workspace size the library reports, and the offsets of trase_rast_geom_layout, equal the recorded table
 (tests/golden/workspace_sizes.json, written by tests/golden/make_workspace_sizes.py from the commit before the layouts moved
-into one function per workspace) integer for integer, and bad arguments keep their error returns.  No GPU needed: the sizes
-functions are host arithmetic."""
+into one function per workspace; the rows of trase_vgg_ws_bytes and trase_lpips_ws_bytes from the commit before the two VGG16
+families were put on one network table) integer for integer, and bad arguments keep their error returns.  No GPU needed: the
+sizes functions are host arithmetic."""
 import json
 import os
 import sys
@@ -23,7 +24,9 @@ def lib():
 
 def test_table_covers_every_sizes_function():
     from trase_amd import _lib
-    declared = sorted(n for n, _, _ in _lib.SYMBOLS if n.endswith("_sizes") or n == "trase_rast_geom_layout")
+    declared = sorted(n for n, _, _ in _lib.SYMBOLS
+                      if n.endswith("_sizes") or n in ("trase_rast_geom_layout", "trase_vgg_ws_bytes", "trase_lpips_ws_bytes"))
+    assert mws.declared() == declared
     assert sorted(TABLE) == declared
     assert sorted(mws.cases()) == declared
     for name, rows in mws.cases().items():          # the recorded cases are the generator's, none dropped

@@ -1,10 +1,17 @@
-// vgg.hip -- the style-transfer feature extractor: VGG16's 3x3 convolutions up to conv4_1, forward and gradient to the image
-// (trase_vgg_ws_bytes / _pack / _forward / _backward; trase_amd/vgg.py).  The LPIPS metric's stack to relu5_3 and its distance
-// head (trase_lpips_*; trase_amd/lpips.py) run on the same kernels and are described where they begin, further down.
+// vgg.hip -- VGG16's 3x3 convolutions on the matrix cores, described ONCE and used by two families of entry points:
+//   * the style-transfer feature extractor, forward and gradient to the image (trase_vgg_ws_bytes / _pack / _forward / _backward;
+//     trase_amd/vgg.py), which cuts the network behind one of its first VG_CUT_MAX = 8 convolutions;
+//   * the LPIPS metric, forward only (trase_lpips_ws_bytes / _pack / _forward / _head; trase_amd/lpips.py), which runs all thirteen
+//     for two images and adds a distance head behind five of them (described where its kernels begin, further down).
 //
-// Network: conv1_1 conv1_2 | conv2_1 conv2_2 | conv3_1 conv3_2 conv3_3 | conv4_1 (| = MaxPool2d(2, 2), floor), 3x3, stride 1,
-// zero padding 1, bias, ReLU after each but the returned one; channels 3 -> 64 -> 64 -> 128 -> 128 -> 256 -> 256 -> 256 -> 512.
-// `layers` = k in 1..8 cuts the network behind its k-th convolution, whose output BEFORE the ReLU is returned as fp32 (C, h*w).
+// Network (the one table: vg_chan, vg_shift, vg_pooled, vg_pixels over layers 0 .. VG_LAYERS = 13):
+//   conv1_1 conv1_2 | conv2_1 conv2_2 | conv3_1 conv3_2 conv3_3 | conv4_1 conv4_2 conv4_3 | conv5_1 conv5_2 conv5_3
+// (| = MaxPool2d(2, 2), floor), 3x3, stride 1, zero padding 1, bias, ReLU; channels 3 -> 64 -> 64 -> 128 -> 128 -> 256 -> 256 -> 256
+// -> 512 -> .. -> 512.  What the families add to the table: the extractor its cut (`layers` = k in 1..8 returns the k-th
+// convolution's output BEFORE the ReLU as fp32 (C, h*w)), the backward weight streams and w1t in its pack, and the saved decisions;
+// LPIPS its five taps (LP_TAP_LAYER) and their `lin` vectors.  One pack description (VgPackSpec: how many layers, backward streams
+// or not, lin vectors or not), one pack launch list, one builder of a forward convolution's VgConv and one set of argument checks
+// serve both; the two layer loops stay apart, because they move different buffers.
 //
 // Arithmetic (mlp_split.hip's): every matrix operand v -- activations, weights, cotangents -- is hi = bf16(v), lo = bf16(v - hi);
 // a product is lo.hi + hi.lo + hi.hi, three v_mfma_f32_32x32x16_bf16 into one fp32 accumulator that starts at the bias.  The
@@ -30,12 +37,13 @@
 
 namespace trase {
 
-constexpr int VG_LAYERS = 8;
+constexpr int VG_LAYERS = 13;                                     // convolutions of the table
+constexpr int VG_CUT_MAX = 8;                                     // the extractor cuts behind conv1_1 .. conv4_1
 constexpr int VG_TILE = 16;                                       // pixels per side of a workgroup's tile
 constexpr int VG_NB = 64;                                         // output channels per workgroup
 __host__ __device__ constexpr int vg_chan(int l) { return l == 0 ? 3 : l <= 2 ? 64 : l <= 4 ? 128 : l <= 7 ? 256 : 512; }   // channels behind layer l
-__host__ __device__ constexpr int vg_shift(int l) { return l <= 2 ? 0 : l <= 4 ? 1 : l <= 7 ? 2 : 3; }                    // pools in front of layer l
-__host__ __device__ constexpr bool vg_pooled(int l) { return l == 2 || l == 4 || l == 7; }                                // a pool follows layer l
+__host__ __device__ constexpr int vg_shift(int l) { return l <= 2 ? 0 : l <= 4 ? 1 : l <= 7 ? 2 : l <= 10 ? 3 : 4; }      // pools in front of layer l
+__host__ __device__ constexpr bool vg_pooled(int l) { return l == 2 || l == 4 || l == 7 || l == 10; }                     // a pool follows layer l
 __host__ __device__ __forceinline__ int vg_group(int c) { return (c >> 5) * 2 + ((c >> 2) & 1); }
 __host__ __device__ __forceinline__ int vg_bit(int c) { return ((c >> 3) & 3) * 4 + (c & 3); }
 
@@ -385,78 +393,6 @@ __global__ __launch_bounds__(256) void vgg_conv_kernel(VgConv a) {
   }
 }
 
-// ---- host side -------------------------------------------------------------------------------------------------------------
-struct VgPack { float* w1; float4* w1t; float* bias[VG_LAYERS + 1]; __bf16* fwd[VG_LAYERS + 1]; __bf16* bwd[VG_LAYERS + 1]; };
-static size_t vg_stream_elems(int l) { return (size_t)9 * vg_chan(l - 1) * vg_chan(l) * 2; }      // hi and lo
-static size_t vg_pack_layout(void* p, int k, VgPack& f) {
-  WsCursor c(p);
-  f.w1 = c.take<float>(64 * 27);
-  f.w1t = c.take<float4>(9 * 64);
-  for (int l = 1; l <= k; ++l) {                    // layer by layer: a pack of more layers begins with the pack of fewer
-    f.bias[l] = c.take<float>(vg_chan(l));
-    if (l > 1) { f.fwd[l] = c.take<__bf16>(vg_stream_elems(l)); f.bwd[l] = c.take<__bf16>(vg_stream_elems(l)); }
-  }
-  return c.bytes();
-}
-
-static inline size_t vg_pixels(int l, int H, int W) { return (size_t)(H >> vg_shift(l)) * (size_t)(W >> vg_shift(l)); }
-
-// saved decisions of layers 1 .. k - 1
-struct VgSaved { uint16_t* relu[VG_LAYERS + 1]; uint64_t* pool[VG_LAYERS + 1]; };
-static size_t vg_saved_layout(void* p, int k, int H, int W, VgSaved& s) {
-  WsCursor c(p);
-  for (int l = 1; l < k; ++l) {
-    s.relu[l] = nullptr; s.pool[l] = nullptr;
-    if (vg_pooled(l)) s.pool[l] = c.take<uint64_t>(vg_pixels(l + 1, H, W) * (vg_chan(l) / 16));
-    else s.relu[l] = c.take<uint16_t>(vg_pixels(l, H, W) * (vg_chan(l) / 16));
-  }
-  return c.bytes();
-}
-
-// the workspace: two ping-pong activation buffers (hi and lo planes each); layer l's output -- forward: the activation the next
-// layer reads (pooled where a pool follows); backward: the cotangent of its convolution output -- lives in buffer l & 1
-struct VgWs { __bf16* hi[2]; __bf16* lo[2]; };
-static size_t vg_ws_layout(void* p, int k, int H, int W, bool backward, VgWs& w) {
-  size_t units[2] = {0, 0};
-  for (int l = 1; l <= k; ++l) {
-    size_t n = 0;
-    if (backward) n = vg_pixels(l, H, W) * vg_chan(l);
-    else if (l < k) n = vg_pixels(vg_pooled(l) ? l + 1 : l, H, W) * vg_chan(l);
-    if (n > units[l & 1]) units[l & 1] = n;
-  }
-  WsCursor c(p);
-  for (int i = 0; i < 2; ++i) { w.hi[i] = c.take<__bf16>(units[i]); w.lo[i] = c.take<__bf16>(units[i]); }
-  return c.bytes();
-}
-
-static int vg_check_shape(const char* who, int k, int H, int W) {
-  if (k < 1 || k > VG_LAYERS) { set_error("%s: layers must be 1 .. 8 (conv1_1 .. conv4_1), got %d", who, k); return TRASE_ERR_INVALID; }
-  const int need = 1 << vg_shift(k);
-  if (H < need || W < need || (int64_t)H * W >= ((int64_t)1 << 25)) {
-    set_error("%s: need H, W >= %d and H * W < 2^25 (got %d x %d)", who, need, H, W); return TRASE_ERR_INVALID;
-  }
-  return TRASE_OK;
-}
-
-static int vg_lg(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
-template <int EPI>
-static void vg_launch_conv(const VgConv& a, hipStream_t stream) {
-  const dim3 grid(((a.W + VG_TILE - 1) / VG_TILE) * ((a.H + VG_TILE - 1) / VG_TILE), a.Cout / VG_NB);
-  hipLaunchKernelGGL(vgg_conv_kernel<EPI>, grid, dim3(256), 0, stream, a);
-}
-
-static const char* const VG_FWD_NAMES[VG_LAYERS + 1] = {"", "vgg_fwd_conv1_1", "vgg_fwd_conv1_2", "vgg_fwd_conv2_1", "vgg_fwd_conv2_2",
-                                                         "vgg_fwd_conv3_1", "vgg_fwd_conv3_2", "vgg_fwd_conv3_3", "vgg_fwd_conv4_1"};
-static const char* const VG_BWD_NAMES[VG_LAYERS + 1] = {"", "vgg_bwd_conv1_1", "vgg_bwd_conv1_2", "vgg_bwd_conv2_1", "vgg_bwd_conv2_2",
-                                                         "vgg_bwd_conv3_1", "vgg_bwd_conv3_2", "vgg_bwd_conv3_3", "vgg_bwd_conv4_1"};
-
-static VgNorm vg_norm(const float* mean, const float* inv_std) {
-  VgNorm nm;
-  for (int i = 0; i < 3; ++i) { nm.mean[i] = mean ? mean[i] : 0.f; nm.inv_std[i] = inv_std ? inv_std[i] : 1.f; }
-  return nm;
-}
-
 // ---- LPIPS (VGG): the stack to relu5_3 and the distance head, forward only ---------------------------------------------------
 // (trase_lpips_ws_bytes / _pack / _forward / _head; trase_amd/lpips.py).  Thirteen convolutions
 //   conv1_1 conv1_2 | conv2_1 conv2_2 | conv3_1 conv3_2 conv3_3 | conv4_1 conv4_2 conv4_3 | conv5_1 conv5_2 conv5_3
@@ -477,11 +413,7 @@ static VgNorm vg_norm(const float* mean, const float* inv_std) {
 //     launch of its own and not part of the head: a lane of the head owns one pixel's channels, a window spans two rows.
 //   * lpips_partial_kernel and lpips_mean_kernel sum each map in float64 in a fixed order (256 chunks per map, a workgroup each;
 //     then one workgroup per layer joins the partial sums) and divide by the pixel count.  No atomics anywhere.
-constexpr int LP_LAYERS = 13;
 constexpr int LP_TAPS = 5;
-__host__ __device__ constexpr int lp_chan(int l) { return l == 0 ? 3 : l <= 2 ? 64 : l <= 4 ? 128 : l <= 7 ? 256 : 512; }
-__host__ __device__ constexpr int lp_shift(int l) { return l <= 2 ? 0 : l <= 4 ? 1 : l <= 7 ? 2 : l <= 10 ? 3 : 4; }
-__host__ __device__ constexpr bool lp_pooled(int l) { return l == 2 || l == 4 || l == 7 || l == 10; }
 constexpr int LP_TAP_LAYER[LP_TAPS] = {2, 4, 7, 10, 13};
 
 __global__ __launch_bounds__(256) void lpips_head_kernel(const __bf16* __restrict__ x_hi, const __bf16* __restrict__ x_lo,
@@ -588,22 +520,82 @@ __global__ __launch_bounds__(256) void lpips_mean_kernel(LpMeans m, const double
   if (threadIdx.x == 0) out[blockIdx.x] = sum / (double)m.n[blockIdx.x];
 }
 
-struct LpPack { float* w1; float* bias[LP_LAYERS + 1]; __bf16* fwd[LP_LAYERS + 1]; float* lin[LP_TAPS]; };
-static size_t lp_pack_layout(void* p, LpPack& f) {
+// ---- host side: the packs ----------------------------------------------------------------------------------------------------
+// what a pack holds: the first `layers` layers' w1, biases and forward streams; with `backward` also w1t and the backward streams;
+// with `lin` also the five lin vectors of the taps
+struct VgPackSpec { int layers; bool backward; bool lin; };
+static VgPackSpec vg_pack_spec(int k) { return VgPackSpec{k, true, false}; }           // the extractor cut behind layer k
+constexpr VgPackSpec LP_PACK_SPEC{VG_LAYERS, false, true};
+struct VgPack {
+  float* w1; float4* w1t; float* bias[VG_LAYERS + 1]; __bf16* fwd[VG_LAYERS + 1]; __bf16* bwd[VG_LAYERS + 1]; float* lin[LP_TAPS];
+};
+static size_t vg_stream_elems(int l) { return (size_t)9 * vg_chan(l - 1) * vg_chan(l) * 2; }      // hi and lo
+static size_t vg_pack_layout(void* p, VgPackSpec d, VgPack& f) {
   WsCursor c(p);
   f.w1 = c.take<float>(64 * 27);
-  for (int l = 1; l <= LP_LAYERS; ++l) {
-    f.bias[l] = c.take<float>(lp_chan(l));
-    if (l > 1) f.fwd[l] = c.take<__bf16>((size_t)9 * lp_chan(l - 1) * lp_chan(l) * 2);
+  if (d.backward) f.w1t = c.take<float4>(9 * 64);
+  for (int l = 1; l <= d.layers; ++l) {             // layer by layer: a pack of more layers begins with the pack of fewer
+    f.bias[l] = c.take<float>(vg_chan(l));
+    if (l > 1) f.fwd[l] = c.take<__bf16>(vg_stream_elems(l));
+    if (l > 1 && d.backward) f.bwd[l] = c.take<__bf16>(vg_stream_elems(l));
   }
-  for (int t = 0; t < LP_TAPS; ++t) f.lin[t] = c.take<float>(lp_chan(LP_TAP_LAYER[t]));
+  if (d.lin)
+    for (int t = 0; t < LP_TAPS; ++t) f.lin[t] = c.take<float>(vg_chan(LP_TAP_LAYER[t]));
   return c.bytes();
 }
 
-static inline size_t lp_pixels(int l, int H, int W) { return (size_t)(H >> lp_shift(l)) * (size_t)(W >> lp_shift(l)); }
+static void vg_launch_copy(const float* src, float* dst, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(vgg_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, src, dst, n);
+}
+// fills a pack from fp32 weights (Cout, Cin, 3, 3), biases and (where the pack has them) lin vectors, all on the device
+static void vg_launch_pack(VgPackSpec d, const float* const* weights, const float* const* biases, const float* const* lin, const VgPack& p,
+                           hipStream_t stream) {
+  vg_launch_copy(weights[0], p.w1, 64 * 27, stream);
+  if (d.backward) hipLaunchKernelGGL(vgg_w1t_kernel, dim3(9), dim3(64), 0, stream, weights[0], p.w1t);
+  for (int l = 1; l <= d.layers; ++l) vg_launch_copy(biases[l - 1], p.bias[l], vg_chan(l), stream);
+  for (int l = 2; l <= d.layers; ++l) {
+    const unsigned nb = (unsigned)((vg_stream_elems(l) / 2 + 255) / 256);
+    hipLaunchKernelGGL(vgg_pack_kernel, dim3(nb), dim3(256), 0, stream, weights[l - 1], vg_chan(l - 1), vg_chan(l), 0, p.fwd[l]);
+    if (d.backward) hipLaunchKernelGGL(vgg_pack_kernel, dim3(nb), dim3(256), 0, stream, weights[l - 1], vg_chan(l - 1), vg_chan(l), 1, p.bwd[l]);
+  }
+  if (d.lin)
+    for (int t = 0; t < LP_TAPS; ++t) vg_launch_copy(lin[t], p.lin[t], vg_chan(LP_TAP_LAYER[t]), stream);
+}
+
+// ---- host side: the workspaces -----------------------------------------------------------------------------------------------
+static inline size_t vg_pixels(int l, int H, int W) { return (size_t)(H >> vg_shift(l)) * (size_t)(W >> vg_shift(l)); }
+
+// the extractor's saved decisions of layers 1 .. k - 1
+struct VgSaved { uint16_t* relu[VG_CUT_MAX + 1]; uint64_t* pool[VG_CUT_MAX + 1]; };
+static size_t vg_saved_layout(void* p, int k, int H, int W, VgSaved& s) {
+  WsCursor c(p);
+  for (int l = 1; l < k; ++l) {
+    s.relu[l] = nullptr; s.pool[l] = nullptr;
+    if (vg_pooled(l)) s.pool[l] = c.take<uint64_t>(vg_pixels(l + 1, H, W) * (vg_chan(l) / 16));
+    else s.relu[l] = c.take<uint16_t>(vg_pixels(l, H, W) * (vg_chan(l) / 16));
+  }
+  return c.bytes();
+}
+
+// the extractor's workspace: two ping-pong activation buffers (hi and lo planes each); layer l's output -- forward: the activation
+// the next layer reads (pooled where a pool follows); backward: the cotangent of its convolution output -- lives in buffer l & 1
+struct VgWs { __bf16* hi[2]; __bf16* lo[2]; };
+static size_t vg_ws_layout(void* p, int k, int H, int W, bool backward, VgWs& w) {
+  size_t units[2] = {0, 0};
+  for (int l = 1; l <= k; ++l) {
+    size_t n = 0;
+    if (backward) n = vg_pixels(l, H, W) * vg_chan(l);
+    else if (l < k) n = vg_pixels(vg_pooled(l) ? l + 1 : l, H, W) * vg_chan(l);
+    if (n > units[l & 1]) units[l & 1] = n;
+  }
+  WsCursor c(p);
+  for (int i = 0; i < 2; ++i) { w.hi[i] = c.take<__bf16>(units[i]); w.lo[i] = c.take<__bf16>(units[i]); }
+  return c.bytes();
+}
+
 static size_t lp_map_floats(int H, int W) {
   size_t n = 0;
-  for (int t = 0; t < LP_TAPS; ++t) n += lp_pixels(LP_TAP_LAYER[t], H, W);
+  for (int t = 0; t < LP_TAPS; ++t) n += vg_pixels(LP_TAP_LAYER[t], H, W);
   return n;
 }
 
@@ -631,18 +623,91 @@ static size_t lp_head_layout(void* p, int C, int hw, LpHeadWs& w) {
   return c.bytes();
 }
 
-static int lp_check_shape(const char* who, int H, int W) {
-  if (H < 16 || W < 16 || (int64_t)H * W >= ((int64_t)1 << 25)) {
-    set_error("%s: need H, W >= 16 and H * W < 2^25 (got %d x %d)", who, H, W); return TRASE_ERR_INVALID;
-  }
+// ---- host side: the argument checks, each refusal once; they set the message and return the status ------------------------------
+static int vg_check_cut(const char* who, int k) {
+  if (k >= 1 && k <= VG_CUT_MAX) return TRASE_OK;
+  set_error("%s: layers must be 1 .. 8 (conv1_1 .. conv4_1), got %d", who, k); return TRASE_ERR_INVALID;
+}
+// an image that every pool in front of the last layer run leaves at least one pixel of: sides of at least `need`
+static int vg_check_image(const char* who, int need, int H, int W) {
+  if (H >= need && W >= need && (int64_t)H * W < ((int64_t)1 << 25)) return TRASE_OK;
+  set_error("%s: need H, W >= %d and H * W < 2^25 (got %d x %d)", who, need, H, W); return TRASE_ERR_INVALID;
+}
+static int vg_check_cut_image(const char* who, int k, int H, int W) {
+  const int rc = vg_check_cut(who, k);
+  return rc ? rc : vg_check_image(who, 1 << vg_shift(k), H, W);
+}
+static int lp_check_image(const char* who, int H, int W) { return vg_check_image(who, 1 << vg_shift(VG_LAYERS), H, W); }
+static int vg_check_arrays(const char* who, int n, const float* const* weights, const float* const* biases) {
+  for (int l = 0; l < n; ++l)
+    if (!weights[l] || !biases[l]) { set_error("%s: null layer %d", who, l); return TRASE_ERR_INVALID; }
   return TRASE_OK;
 }
+static int vg_check_norm(const char* who, const float* mean, const float* inv_std) {
+  if ((mean == nullptr) == (inv_std == nullptr)) return TRASE_OK;
+  set_error("%s: mean and inv_std come together (both null: no normalisation)", who); return TRASE_ERR_INVALID;
+}
+// `what` names the buffers whose addresses were or-ed into `addresses`
+static int vg_check_align16(const char* who, const char* what, size_t addresses) {
+  if ((addresses & 15) == 0) return TRASE_OK;
+  set_error("%s: %s must be 16-byte aligned", who, what); return TRASE_ERR_INVALID;
+}
+static int lp_check_align(const char* who, const char* out_name, const double* out, size_t fp32_addresses) {
+  if (((size_t)out & 7) == 0 && (fp32_addresses & 3) == 0) return TRASE_OK;
+  set_error("%s: %s must be 8-byte aligned, the fp32 buffers 4-byte aligned", who, out_name); return TRASE_ERR_INVALID;
+}
+// a buffer (`what`) of `have` bytes where `need` are wanted; `missing`: it is wanted and null
+static int vg_check_room(const char* who, const char* what, size_t have, size_t need, bool missing = false) {
+  if (!missing && have >= need) return TRASE_OK;
+  set_error("%s: %s too small (%zu bytes, need %zu)", who, what, have, need); return TRASE_ERR_WORKSPACE;
+}
+// carves a filled pack for the forward and backward entries; the message says which cut when the pack is of a cut network
+static int vg_check_pack(const char* who, VgPackSpec d, const void* pack, size_t pack_bytes, VgPack& p) {
+  if (pack_bytes >= vg_pack_layout(const_cast<void*>(pack), d, p)) return TRASE_OK;
+  if (d.layers < VG_LAYERS) set_error("%s: pack buffer too small for %d layers", who, d.layers);
+  else set_error("%s: pack buffer too small", who);
+  return TRASE_ERR_WORKSPACE;
+}
 
-static const char* const LP_CONV_NAMES[LP_LAYERS + 1] = {"", "lpips_conv1_1", "lpips_conv1_2", "lpips_conv2_1", "lpips_conv2_2", "lpips_conv3_1",
-                                                         "lpips_conv3_2", "lpips_conv3_3", "lpips_conv4_1", "lpips_conv4_2", "lpips_conv4_3",
-                                                         "lpips_conv5_1", "lpips_conv5_2", "lpips_conv5_3"};
+// ---- host side: launches --------------------------------------------------------------------------------------------------------
+static int vg_lg(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
+
+// forward layer l (>= 2) of an H x W image: geometry from the table, stream and bias from the pack; the caller sets the planes
+// read and written and the epilogue's outputs
+static VgConv vg_forward_conv(int l, int H, int W, const VgPack& p) {
+  VgConv a{};
+  a.stream = p.fwd[l]; a.bias = p.bias[l];
+  a.H = H >> vg_shift(l); a.W = W >> vg_shift(l); a.Cin = vg_chan(l - 1); a.Cout = vg_chan(l); a.lg_steps = vg_lg(a.Cin / 16);
+  return a;
+}
+
+template <int EPI>
+static void vg_launch_conv(const VgConv& a, hipStream_t stream) {
+  const dim3 grid(((a.W + VG_TILE - 1) / VG_TILE) * ((a.H + VG_TILE - 1) / VG_TILE), a.Cout / VG_NB);
+  hipLaunchKernelGGL(vgg_conv_kernel<EPI>, grid, dim3(256), 0, stream, a);
+}
+
+// the means of the first n maps of `m`, in two steps
+static void lp_launch_means(const LpMeans& m, int n, double* parts, double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(lpips_partial_kernel, dim3(LP_PARTS, n), dim3(256), 0, stream, m, parts);
+  hipLaunchKernelGGL(lpips_mean_kernel, dim3(n), dim3(256), 0, stream, m, (const double*)parts, out);
+}
+
+// the profiling scopes' names: string literals, ProfScope keeps the pointer
+#define VG_LAYER_NAMES(prefix)                                                                                                             \
+  {"", prefix "conv1_1", prefix "conv1_2", prefix "conv2_1", prefix "conv2_2", prefix "conv3_1", prefix "conv3_2", prefix "conv3_3",       \
+   prefix "conv4_1", prefix "conv4_2", prefix "conv4_3", prefix "conv5_1", prefix "conv5_2", prefix "conv5_3"}
+static const char* const VG_FWD_NAMES[VG_LAYERS + 1] = VG_LAYER_NAMES("vgg_fwd_");
+static const char* const VG_BWD_NAMES[VG_LAYERS + 1] = VG_LAYER_NAMES("vgg_bwd_");
+static const char* const LP_CONV_NAMES[VG_LAYERS + 1] = VG_LAYER_NAMES("lpips_");
 static const char* const LP_HEAD_NAMES[LP_TAPS] = {"lpips_head_relu1_2", "lpips_head_relu2_2", "lpips_head_relu3_3", "lpips_head_relu4_3",
                                                    "lpips_head_relu5_3"};
+
+static VgNorm vg_norm(const float* mean, const float* inv_std) {
+  VgNorm nm;
+  for (int i = 0; i < 3; ++i) { nm.mean[i] = mean ? mean[i] : 0.f; nm.inv_std[i] = inv_std ? inv_std[i] : 1.f; }
+  return nm;
+}
 
 }  // namespace trase
 
@@ -653,13 +718,13 @@ extern "C" {
 int trase_vgg_ws_bytes(int32_t layers, int32_t H, int32_t W, size_t* pack_bytes, size_t* ws_forward_bytes, size_t* ws_backward_bytes,
                     size_t* saved_bytes, int32_t* C, int32_t* h, int32_t* w) {
   const char* who = "trase_vgg_ws_bytes";
-  int rc = vg_check_shape(who, layers, H, W);
+  int rc = vg_check_cut_image(who, layers, H, W);
   if (rc) return rc;
   if (!pack_bytes || !ws_forward_bytes || !ws_backward_bytes || !saved_bytes || !C || !h || !w) {
     set_error("%s: null pointer", who); return TRASE_ERR_INVALID;
   }
   VgPack p; VgWs ws; VgSaved s;
-  *pack_bytes = vg_pack_layout(nullptr, layers, p);
+  *pack_bytes = vg_pack_layout(nullptr, vg_pack_spec(layers), p);
   *ws_forward_bytes = vg_ws_layout(nullptr, layers, H, W, false, ws);
   *ws_backward_bytes = vg_ws_layout(nullptr, layers, H, W, true, ws);
   *saved_bytes = vg_saved_layout(nullptr, layers, H, W, s);
@@ -670,26 +735,17 @@ int trase_vgg_ws_bytes(int32_t layers, int32_t H, int32_t W, size_t* pack_bytes,
 int trase_vgg_pack(int32_t layers, const float* const* weights, const float* const* biases, void* pack, size_t pack_bytes,
                    int32_t device, trase_stream_t stream_) {
   const char* who = "trase_vgg_pack";
-  if (layers < 1 || layers > VG_LAYERS) { set_error("%s: layers must be 1 .. 8 (conv1_1 .. conv4_1), got %d", who, layers); return TRASE_ERR_INVALID; }
+  int rc = vg_check_cut(who, layers);
+  if (rc) return rc;
   if (!weights || !biases || !pack) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
-  for (int l = 0; l < layers; ++l)
-    if (!weights[l] || !biases[l]) { set_error("%s: null layer %d", who, l); return TRASE_ERR_INVALID; }
-  if (((size_t)pack & 15) != 0) { set_error("%s: the pack buffer must be 16-byte aligned", who); return TRASE_ERR_INVALID; }
+  if ((rc = vg_check_arrays(who, layers, weights, biases))) return rc;
+  if ((rc = vg_check_align16(who, "the pack buffer", (size_t)pack))) return rc;
   VgPack p;
-  const size_t need = vg_pack_layout(pack, layers, p);
-  if (pack_bytes < need) { set_error("%s: pack buffer too small (%zu bytes, need %zu)", who, pack_bytes, need); return TRASE_ERR_WORKSPACE; }
+  if ((rc = vg_check_room(who, "pack buffer", pack_bytes, vg_pack_layout(pack, vg_pack_spec(layers), p)))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   ProfScope ps("vgg_pack", stream);
-  hipLaunchKernelGGL(vgg_copy_kernel, dim3((64 * 27 + 255) / 256), dim3(256), 0, stream, weights[0], p.w1, 64 * 27);
-  hipLaunchKernelGGL(vgg_w1t_kernel, dim3(9), dim3(64), 0, stream, weights[0], p.w1t);
-  for (int l = 1; l <= layers; ++l)
-    hipLaunchKernelGGL(vgg_copy_kernel, dim3((vg_chan(l) + 255) / 256), dim3(256), 0, stream, biases[l - 1], p.bias[l], vg_chan(l));
-  for (int l = 2; l <= layers; ++l) {
-    const unsigned nb = (unsigned)((vg_stream_elems(l) / 2 + 255) / 256);
-    hipLaunchKernelGGL(vgg_pack_kernel, dim3(nb), dim3(256), 0, stream, weights[l - 1], vg_chan(l - 1), vg_chan(l), 0, p.fwd[l]);
-    hipLaunchKernelGGL(vgg_pack_kernel, dim3(nb), dim3(256), 0, stream, weights[l - 1], vg_chan(l - 1), vg_chan(l), 1, p.bwd[l]);
-  }
+  vg_launch_pack(vg_pack_spec(layers), weights, biases, nullptr, p, stream);
   TRASE_POST_LAUNCH("vgg_pack", stream, 0);
   return TRASE_OK;
 }
@@ -698,20 +754,17 @@ int trase_vgg_forward(int32_t layers, const void* pack, size_t pack_bytes, const
                       const float* mean, const float* inv_std, float* out, void* saved, size_t saved_bytes, void* ws,
                       size_t ws_bytes, int32_t device, trase_stream_t stream_) {
   const char* who = "trase_vgg_forward";
-  int rc = vg_check_shape(who, layers, H, W);
+  int rc = vg_check_cut_image(who, layers, H, W);
   if (rc) return rc;
   const int k = layers;
   if (!pack || !image || !out) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
-  if ((mean == nullptr) != (inv_std == nullptr)) { set_error("%s: mean and inv_std come together (both null: no normalisation)", who); return TRASE_ERR_INVALID; }
-  if (((size_t)pack & 15) != 0 || ((size_t)ws & 15) != 0 || ((size_t)saved & 15) != 0) {
-    set_error("%s: pack, saved and ws must be 16-byte aligned", who); return TRASE_ERR_INVALID;
-  }
+  if ((rc = vg_check_norm(who, mean, inv_std))) return rc;
+  if ((rc = vg_check_align16(who, "pack, saved and ws", (size_t)pack | (size_t)ws | (size_t)saved))) return rc;
   VgPack p; VgWs b; VgSaved s;
-  if (pack_bytes < vg_pack_layout(const_cast<void*>(pack), k, p)) { set_error("%s: pack buffer too small for %d layers", who, k); return TRASE_ERR_WORKSPACE; }
+  if ((rc = vg_check_pack(who, vg_pack_spec(k), pack, pack_bytes, p))) return rc;
   const size_t ws_need = vg_ws_layout(ws, k, H, W, false, b);
-  if (ws_need > 0 && (!ws || ws_bytes < ws_need)) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws_bytes, ws_need); return TRASE_ERR_WORKSPACE; }
-  const size_t saved_need = vg_saved_layout(saved, k, H, W, s);
-  if (saved && saved_bytes < saved_need) { set_error("%s: saved buffer too small (%zu bytes, need %zu)", who, saved_bytes, saved_need); return TRASE_ERR_WORKSPACE; }
+  if ((rc = vg_check_room(who, "workspace", ws_bytes, ws_need, ws_need > 0 && !ws))) return rc;
+  if (saved && (rc = vg_check_room(who, "saved buffer", saved_bytes, vg_saved_layout(saved, k, H, W, s)))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const VgNorm nm = vg_norm(mean, inv_std);
@@ -727,10 +780,8 @@ int trase_vgg_forward(int32_t layers, const void* pack, size_t pack_bytes, const
   }
   TRASE_POST_LAUNCH("vgg_fwd_conv1_1", stream, 0);
   for (int l = 2; l <= k; ++l) {
-    VgConv a{};
+    VgConv a = vg_forward_conv(l, H, W, p);
     a.in_hi = b.hi[(l - 1) & 1]; a.in_lo = b.lo[(l - 1) & 1];
-    a.stream = p.fwd[l]; a.bias = p.bias[l];
-    a.H = H >> vg_shift(l); a.W = W >> vg_shift(l); a.Cin = vg_chan(l - 1); a.Cout = vg_chan(l); a.lg_steps = vg_lg(a.Cin / 16);
     a.out_hi = b.hi[l & 1]; a.out_lo = b.lo[l & 1];
     ProfScope ps(VG_FWD_NAMES[l], stream);
     if (l == k) { a.out_f32 = out; vg_launch_conv<VG_FWD_OUT>(a, stream); }
@@ -745,19 +796,15 @@ int trase_vgg_backward(int32_t layers, const void* pack, size_t pack_bytes, cons
                        const float* inv_std, const void* saved, size_t saved_bytes, float* d_image, void* ws, size_t ws_bytes,
                        int32_t device, trase_stream_t stream_) {
   const char* who = "trase_vgg_backward";
-  int rc = vg_check_shape(who, layers, H, W);
+  int rc = vg_check_cut_image(who, layers, H, W);
   if (rc) return rc;
   const int k = layers;
   if (!pack || !d_out || !d_image || !ws || (k > 1 && !saved)) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
-  if (((size_t)pack & 15) != 0 || ((size_t)ws & 15) != 0 || ((size_t)saved & 15) != 0) {
-    set_error("%s: pack, saved and ws must be 16-byte aligned", who); return TRASE_ERR_INVALID;
-  }
+  if ((rc = vg_check_align16(who, "pack, saved and ws", (size_t)pack | (size_t)ws | (size_t)saved))) return rc;
   VgPack p; VgWs b; VgSaved s;
-  if (pack_bytes < vg_pack_layout(const_cast<void*>(pack), k, p)) { set_error("%s: pack buffer too small for %d layers", who, k); return TRASE_ERR_WORKSPACE; }
-  const size_t ws_need = vg_ws_layout(ws, k, H, W, true, b);
-  if (ws_bytes < ws_need) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws_bytes, ws_need); return TRASE_ERR_WORKSPACE; }
-  const size_t saved_need = vg_saved_layout(const_cast<void*>(saved), k, H, W, s);
-  if (saved_bytes < saved_need) { set_error("%s: saved buffer too small (%zu bytes, need %zu)", who, saved_bytes, saved_need); return TRASE_ERR_WORKSPACE; }
+  if ((rc = vg_check_pack(who, vg_pack_spec(k), pack, pack_bytes, p))) return rc;
+  if ((rc = vg_check_room(who, "workspace", ws_bytes, vg_ws_layout(ws, k, H, W, true, b)))) return rc;
+  if ((rc = vg_check_room(who, "saved buffer", saved_bytes, vg_saved_layout(const_cast<void*>(saved), k, H, W, s)))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   {
@@ -768,7 +815,7 @@ int trase_vgg_backward(int32_t layers, const void* pack, size_t pack_bytes, cons
   }
   TRASE_POST_LAUNCH("vgg_bwd_split", stream, 0);
   for (int l = k; l >= 2; --l) {                   // the cotangent of layer l's output -> that of layer l - 1's
-    VgConv a{};
+    VgConv a{};                                    // not vg_forward_conv: Cin and Cout are exchanged and there is no bias
     a.in_hi = b.hi[l & 1]; a.in_lo = b.lo[l & 1];
     a.stream = p.bwd[l]; a.bias = nullptr;
     a.H = H >> vg_shift(l); a.W = W >> vg_shift(l); a.Cin = vg_chan(l); a.Cout = vg_chan(l - 1); a.lg_steps = vg_lg(a.Cin / 16);
@@ -801,11 +848,11 @@ int trase_vgg_backward(int32_t layers, const void* pack, size_t pack_bytes, cons
 
 int trase_lpips_ws_bytes(int32_t H, int32_t W, size_t* pack_bytes, size_t* ws_bytes, size_t* map_floats) {
   const char* who = "trase_lpips_ws_bytes";
-  int rc = lp_check_shape(who, H, W);
+  int rc = lp_check_image(who, H, W);
   if (rc) return rc;
   if (!pack_bytes || !ws_bytes || !map_floats) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
-  LpPack p; LpWs ws;
-  *pack_bytes = lp_pack_layout(nullptr, p);
+  VgPack p; LpWs ws;
+  *pack_bytes = vg_pack_layout(nullptr, LP_PACK_SPEC, p);
   *ws_bytes = lp_ws_layout(nullptr, H, W, ws);
   *map_floats = lp_map_floats(H, W);
   return TRASE_OK;
@@ -815,28 +862,17 @@ int trase_lpips_pack(const float* const* weights, const float* const* biases, co
                      int32_t device, trase_stream_t stream_) {
   const char* who = "trase_lpips_pack";
   if (!weights || !biases || !lin || !pack) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
-  for (int l = 0; l < LP_LAYERS; ++l)
-    if (!weights[l] || !biases[l]) { set_error("%s: null layer %d", who, l); return TRASE_ERR_INVALID; }
+  int rc = vg_check_arrays(who, VG_LAYERS, weights, biases);
+  if (rc) return rc;
   for (int t = 0; t < LP_TAPS; ++t)
     if (!lin[t]) { set_error("%s: null lin %d", who, t); return TRASE_ERR_INVALID; }
-  if (((size_t)pack & 15) != 0) { set_error("%s: the pack buffer must be 16-byte aligned", who); return TRASE_ERR_INVALID; }
-  LpPack p;
-  const size_t need = lp_pack_layout(pack, p);
-  if (pack_bytes < need) { set_error("%s: pack buffer too small (%zu bytes, need %zu)", who, pack_bytes, need); return TRASE_ERR_WORKSPACE; }
+  if ((rc = vg_check_align16(who, "the pack buffer", (size_t)pack))) return rc;
+  VgPack p;
+  if ((rc = vg_check_room(who, "pack buffer", pack_bytes, vg_pack_layout(pack, LP_PACK_SPEC, p)))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   ProfScope ps("lpips_pack", stream);
-  hipLaunchKernelGGL(vgg_copy_kernel, dim3((64 * 27 + 255) / 256), dim3(256), 0, stream, weights[0], p.w1, 64 * 27);
-  for (int l = 1; l <= LP_LAYERS; ++l)
-    hipLaunchKernelGGL(vgg_copy_kernel, dim3((lp_chan(l) + 255) / 256), dim3(256), 0, stream, biases[l - 1], p.bias[l], lp_chan(l));
-  for (int l = 2; l <= LP_LAYERS; ++l) {
-    const unsigned nb = (unsigned)(((size_t)9 * lp_chan(l - 1) * lp_chan(l) + 255) / 256);
-    hipLaunchKernelGGL(vgg_pack_kernel, dim3(nb), dim3(256), 0, stream, weights[l - 1], lp_chan(l - 1), lp_chan(l), 0, p.fwd[l]);
-  }
-  for (int t = 0; t < LP_TAPS; ++t) {
-    const int c = lp_chan(LP_TAP_LAYER[t]);
-    hipLaunchKernelGGL(vgg_copy_kernel, dim3((c + 255) / 256), dim3(256), 0, stream, lin[t], p.lin[t], c);
-  }
+  vg_launch_pack(LP_PACK_SPEC, weights, biases, lin, p, stream);
   TRASE_POST_LAUNCH("lpips_pack", stream, 0);
   return TRASE_OK;
 }
@@ -845,34 +881,31 @@ int trase_lpips_forward(const void* pack, size_t pack_bytes, const float* x, con
                         const float* inv_std, double* out_layers, float* maps, float* taps_x, float* taps_y, void* ws, size_t ws_bytes,
                         int32_t device, trase_stream_t stream_) {
   const char* who = "trase_lpips_forward";
-  int rc = lp_check_shape(who, H, W);
+  int rc = lp_check_image(who, H, W);
   if (rc) return rc;
   if (!pack || !x || !y || !out_layers || !ws) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
-  if ((mean == nullptr) != (inv_std == nullptr)) { set_error("%s: mean and inv_std come together (both null: no normalisation)", who); return TRASE_ERR_INVALID; }
+  if ((rc = vg_check_norm(who, mean, inv_std))) return rc;
   if ((taps_x == nullptr) != (taps_y == nullptr)) { set_error("%s: taps_x and taps_y come together", who); return TRASE_ERR_INVALID; }
-  if (((size_t)pack & 15) != 0 || ((size_t)ws & 15) != 0) { set_error("%s: pack and ws must be 16-byte aligned", who); return TRASE_ERR_INVALID; }
-  if (((size_t)out_layers & 7) != 0 || (((size_t)x | (size_t)y | (size_t)maps | (size_t)taps_x | (size_t)taps_y) & 3) != 0) {
-    set_error("%s: out_layers must be 8-byte aligned, the fp32 buffers 4-byte aligned", who); return TRASE_ERR_INVALID;
-  }
-  LpPack p; LpWs b;
-  if (pack_bytes < lp_pack_layout(const_cast<void*>(pack), p)) { set_error("%s: pack buffer too small", who); return TRASE_ERR_WORKSPACE; }
-  const size_t ws_need = lp_ws_layout(ws, H, W, b);
-  if (ws_bytes < ws_need) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws_bytes, ws_need); return TRASE_ERR_WORKSPACE; }
+  if ((rc = vg_check_align16(who, "pack and ws", (size_t)pack | (size_t)ws))) return rc;
+  if ((rc = lp_check_align(who, "out_layers", out_layers, (size_t)x | (size_t)y | (size_t)maps | (size_t)taps_x | (size_t)taps_y))) return rc;
+  VgPack p; LpWs b;
+  if ((rc = vg_check_pack(who, LP_PACK_SPEC, pack, pack_bytes, p))) return rc;
+  if ((rc = vg_check_room(who, "workspace", ws_bytes, lp_ws_layout(ws, H, W, b)))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const VgNorm nm = vg_norm(mean, inv_std);
   const float* img[2] = {x, y};
   float* taps[2] = {taps_x, taps_y};
   float* const map_base = maps ? maps : b.maps;
-  LpMeans means;
+  LpMeans means{};
   struct Planes { __bf16* hi; __bf16* lo; };
   const size_t half = (size_t)H * W * 32;          // elements of half a buffer
   auto halves = [&](int buf, int im) { return Planes{b.hi[buf] + im * half, b.lo[buf] + im * half}; };
   Planes cur[2] = {};                               // where each image's newest activation lives
   int deep = 0, tap = 0;                            // behind the first pool: the buffer (1 or 2) whose halves hold `cur`
   size_t map_off = 0, tap_off = 0;
-  for (int l = 1; l <= LP_LAYERS; ++l) {
-    const int h = H >> lp_shift(l), w = W >> lp_shift(l), hw = h * w, c = lp_chan(l);
+  for (int l = 1; l <= VG_LAYERS; ++l) {
+    const int h = H >> vg_shift(l), w = W >> vg_shift(l), hw = h * w, c = vg_chan(l);
     {
       ProfScope ps(LP_CONV_NAMES[l], stream);
       for (int im = 0; im < 2; ++im) {
@@ -882,10 +915,8 @@ int trase_lpips_forward(const void* pack, size_t pack_bytes, const float* x, con
                              p.bias[1], cur[im].hi, cur[im].lo, (float*)nullptr, (uint16_t*)nullptr);
         } else {
           const Planes dst = l == 2 ? (im == 0 ? Planes{b.hi[2], b.lo[2]} : Planes{b.hi[0], b.lo[0]}) : halves(3 - deep, im);
-          VgConv a{};
+          VgConv a = vg_forward_conv(l, H, W, p);
           a.in_hi = cur[im].hi; a.in_lo = cur[im].lo;
-          a.stream = p.fwd[l]; a.bias = p.bias[l];
-          a.H = h; a.W = w; a.Cin = lp_chan(l - 1); a.Cout = c; a.lg_steps = vg_lg(a.Cin / 16);
           a.out_hi = dst.hi; a.out_lo = dst.lo;
           vg_launch_conv<VG_FWD_RELU>(a, stream);
           cur[im] = dst;
@@ -903,7 +934,7 @@ int trase_lpips_forward(const void* pack, size_t pack_bytes, const float* x, con
         if (taps[im])
           hipLaunchKernelGGL(lpips_tap_kernel, dim3((unsigned)((hw + 255) / 256), c / 8), dim3(256), 0, stream, cur[im].hi, cur[im].lo, c, hw,
                              taps[im] + tap_off);
-        if (lp_pooled(l)) {                         // the first pool goes to buffer 1, whose conv1_1 output of y is spent
+        if (vg_pooled(l)) {                         // the first pool goes to buffer 1, whose conv1_1 output of y is spent
           const Planes dst = halves(l == 2 ? 1 : 3 - deep, im);
           const size_t n = (size_t)(h >> 1) * (w >> 1) * (c / 8);
           hipLaunchKernelGGL(lpips_pool_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, cur[im].hi, cur[im].lo, h, w, c, dst.hi,
@@ -915,13 +946,12 @@ int trase_lpips_forward(const void* pack, size_t pack_bytes, const float* x, con
     TRASE_POST_LAUNCH("lpips_head", stream, 0);
     means.map[tap] = map_base + map_off; means.n[tap] = hw;
     map_off += (size_t)hw; tap_off += (size_t)hw * c;
-    if (lp_pooled(l)) deep = l == 2 ? 1 : 3 - deep;
+    if (vg_pooled(l)) deep = l == 2 ? 1 : 3 - deep;
     ++tap;
   }
   {
     ProfScope ps("lpips_mean", stream);
-    hipLaunchKernelGGL(lpips_partial_kernel, dim3(LP_PARTS, LP_TAPS), dim3(256), 0, stream, means, b.parts);
-    hipLaunchKernelGGL(lpips_mean_kernel, dim3(LP_TAPS), dim3(256), 0, stream, means, (const double*)b.parts, out_layers);
+    lp_launch_means(means, LP_TAPS, b.parts, out_layers, stream);
   }
   TRASE_POST_LAUNCH("lpips_mean", stream, 0);
   return TRASE_OK;
@@ -934,13 +964,11 @@ int trase_lpips_head(const float* a, const float* b, const float* lin, int32_t C
     set_error("%s: need C in {64, 128, 256, 512}, hw >= 1 and C * hw < 2^31 (got C %d, hw %d)", who, C, hw); return TRASE_ERR_INVALID;
   }
   if (!a || !b || !lin || !out_layer || !ws) { set_error("%s: null pointer", who); return TRASE_ERR_INVALID; }
-  if (((size_t)ws & 15) != 0) { set_error("%s: ws must be 16-byte aligned", who); return TRASE_ERR_INVALID; }
-  if (((size_t)out_layer & 7) != 0 || (((size_t)a | (size_t)b | (size_t)lin | (size_t)map) & 3) != 0) {
-    set_error("%s: out_layer must be 8-byte aligned, the fp32 buffers 4-byte aligned", who); return TRASE_ERR_INVALID;
-  }
+  int rc = vg_check_align16(who, "ws", (size_t)ws);
+  if (rc) return rc;
+  if ((rc = lp_check_align(who, "out_layer", out_layer, (size_t)a | (size_t)b | (size_t)lin | (size_t)map))) return rc;
   LpHeadWs w;
-  const size_t ws_need = lp_head_layout(ws, C, hw, w);
-  if (ws_bytes < ws_need) { set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws_bytes, ws_need); return TRASE_ERR_WORKSPACE; }
+  if ((rc = vg_check_room(who, "workspace", ws_bytes, lp_head_layout(ws, C, hw, w)))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   ProfScope ps("lpips_head", stream);
@@ -951,8 +979,7 @@ int trase_lpips_head(const float* a, const float* b, const float* lin, int32_t C
   hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)((hw + 31) / 32)), dim3(256), 0, stream, w.hi[0], w.lo[0], w.hi[1], w.lo[1], C, hw, lin, m);
   LpMeans means{};
   means.map[0] = m; means.n[0] = hw;
-  hipLaunchKernelGGL(lpips_partial_kernel, dim3(LP_PARTS, 1), dim3(256), 0, stream, means, w.parts);
-  hipLaunchKernelGGL(lpips_mean_kernel, dim3(1), dim3(256), 0, stream, means, (const double*)w.parts, out_layer);
+  lp_launch_means(means, 1, w.parts, out_layer, stream);
   TRASE_POST_LAUNCH("lpips_head", stream, 0);
   return TRASE_OK;
 }

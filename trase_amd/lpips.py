@@ -12,61 +12,34 @@ There is no backward: the reference uses LPIPS as a metric under ``no_grad`` onl
 from __future__ import annotations
 
 import ctypes as C
-import math
+import functools
 
 import torch
 
-from . import _lib
+from . import _lib, vgg
 from .rasterizer import _bytes, _stream
 from .vgg import _device_index
 
-KEYS = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3", "conv5_1",
-        "conv5_2", "conv5_3")
-FEATURE_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)   # torchvision's vgg16().features positions of the convolutions
-CHANNELS = (3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)   # in front of layer 1, behind layers 1 .. 13
-POOL_AFTER = (2, 4, 7, 10)
+KEYS, FEATURE_INDEX, CHANNELS, POOL_AFTER = vgg.NET_KEYS, vgg.NET_FEATURE_INDEX, vgg.NET_CHANNELS, vgg.NET_POOL_AFTER    # all thirteen layers
 TAP_LAYERS = (2, 4, 7, 10, 13)                                     # relu1_2 relu2_2 relu3_3 relu4_3 relu5_3 (modules 4 9 16 23 30)
 TAP_NAMES = ("relu1_2", "relu2_2", "relu3_3", "relu4_3", "relu5_3")
-TAP_CHANNELS = (64, 128, 256, 512, 512)
+TAP_CHANNELS = tuple(CHANNELS[l] for l in TAP_LAYERS)
 MEAN = (-.030, -.088, -.188)                                       # networks.py:41-44
 STD = (.458, .448, .450)
-LAYERS = 13
+LAYERS = len(KEYS)
 
 
 def lpips_random_weights(seed: int, device="cpu"):
     """(pairs, lins): the 13 layers He-scaled as in ``vgg16_random_weights`` (std = sqrt(2 / (9 Cin)), biases 0.05 * randn) and
     five non-negative ``lin`` vectors of 64, 128, 256, 512, 512 elements; drawn on the CPU generator, so it needs no GPU"""
     g = torch.Generator().manual_seed(int(seed))
-    pairs = []
-    for l in range(1, LAYERS + 1):
-        cin, cout = CHANNELS[l - 1], CHANNELS[l]
-        w = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (9 * cin))
-        b = 0.05 * torch.randn(cout, generator=g)
-        pairs.append((w.to(device), b.to(device)))
+    pairs = vgg.random_pairs(g, LAYERS, device)
     lins = [(torch.rand(c, generator=g) * (2.0 / c)).to(device) for c in TAP_CHANNELS]
     return pairs, lins
 
 
-def weight_pairs(weights):
-    """[(w, b)] * 13 out of a torchvision state dict (``features.N.weight`` or bare ``N.weight``) or a list of 13 pairs"""
-    if isinstance(weights, dict):
-        pairs = []
-        for idx in FEATURE_INDEX:
-            for prefix in (f"features.{idx}.", f"{idx}."):
-                if prefix + "weight" in weights:
-                    pairs.append((weights[prefix + "weight"], weights[prefix + "bias"]))
-                    break
-            else:
-                raise KeyError(f"LPIPSVGG: the state dict has neither features.{idx}.weight nor {idx}.weight")
-    else:
-        pairs = [tuple(p) for p in weights]
-        if len(pairs) != LAYERS:
-            raise ValueError(f"LPIPSVGG: {LAYERS} (weight, bias) pairs are needed, got {len(pairs)}")
-    for l, (w, b) in enumerate(pairs, start=1):
-        if tuple(w.shape) != (CHANNELS[l], CHANNELS[l - 1], 3, 3) or tuple(b.shape) != (CHANNELS[l],):
-            raise ValueError(f"LPIPSVGG: layer {KEYS[l - 1]} expects weight {(CHANNELS[l], CHANNELS[l - 1], 3, 3)} and bias "
-                             f"{(CHANNELS[l],)}, got {tuple(w.shape)} and {tuple(b.shape)}")
-    return pairs
+# [(w, b)] * 13 out of a torchvision state dict (``features.N.weight`` or bare ``N.weight``) or a list of exactly 13 pairs
+weight_pairs = functools.partial(vgg.weight_pairs, layers=LAYERS, who="LPIPSVGG", exact=True)
 
 
 def lin_vectors(lin_weights):
@@ -111,20 +84,12 @@ def head_ws_bytes(C_: int, hw: int) -> int:
     return 4 * r(2 * C_ * hw) + r(4 * hw) + 2048
 
 
-def _indexed(device):
-    """``torch.device(device)`` with the current index filled in for a bare "cuda": tensors always carry one"""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
-
-
 def total_of(layers):
     """the float64 sum of the five layer values in layer order (a device scalar; a library reduction fixes no order)"""
     return (((layers[0] + layers[1]) + layers[2]) + layers[3]) + layers[4]
 
 
-class LPIPSVGG:
+class LPIPSVGG(vgg._Packed):
     """LPIPS (VGG16, version 0.1), forward only.  ``vgg_weights``: torchvision's state dict (``features.N.weight`` or bare
     ``N.weight``, N in 0 2 5 7 10 12 14 17 19 21 24 26 28) or 13 ``(w, b)`` pairs; ``lin_weights``: see ``lin_vectors``.  Packed at
     construction when a device is known -- call ``repack()`` after changing the weights.
@@ -133,50 +98,24 @@ class LPIPSVGG:
     the ``(5,)`` float64 layer values, the five ``(h_l, w_l)`` fp32 maps, ``(taps_x, taps_y)`` as five ``(C_l, h_l, w_l)`` fp32
     tensors each, in that order, those asked for.  Nothing synchronises."""
 
+    MODULE = "trase_amd.lpips"
+
     def __init__(self, vgg_weights, lin_weights, *, device=None):
         self._pairs = weight_pairs(vgg_weights)
         self._lins = lin_vectors(lin_weights)
-        m = torch.tensor(MEAN, dtype=torch.float32)
-        inv = 1.0 / torch.tensor(STD, dtype=torch.float32)              # fp32 reciprocal: what conv1_1 multiplies by
-        self._mean = (C.c_float * 3)(*m.tolist())
-        self._inv_std = (C.c_float * 3)(*inv.tolist())
-        self.pack = None
+        self._mean, self._inv_std = vgg.norm_arrays(MEAN, STD)
         self.packs = 0                                                  # how often the weights were packed
-        self.device = _indexed(device) if device is not None else None
-        if self.device is None and self._pairs[0][0].device.type == "cuda":
-            self.device = self._pairs[0][0].device
-        if self.device is not None:
-            self.repack()
+        self._place(device)
 
-    def to(self, device):
-        device = _indexed(device)
-        if device.type != "cuda":
-            raise RuntimeError("trase_amd.lpips runs on the GPU only (there is no CPU path)")
-        if self.device != device or self.pack is None:
-            self.device = device
-            self.repack()
-        return self
+    def _pack_bytes(self):
+        return sizes(16, 16)[0]
 
-    def repack(self):
-        """pack the weights as they are now"""
-        lib = _lib.load()
-        dev = self.device
-        if dev is None or dev.type != "cuda":
-            raise RuntimeError("trase_amd.lpips runs on the GPU only (there is no CPU path)")
-        ws = [w.detach().to(dev, torch.float32).contiguous() for w, _ in self._pairs]
-        bs = [b.detach().to(dev, torch.float32).contiguous() for _, b in self._pairs]
-        ls = [v.detach().to(dev, torch.float32).contiguous() for v in self._lins]
-        pack_bytes = sizes(16, 16)[0]
-        if self.pack is None or self.pack.numel() != pack_bytes or self.pack.device != dev:
-            self.pack = _bytes(pack_bytes, dev)
-        wp = (C.c_void_p * LAYERS)(*[t.data_ptr() for t in ws])
-        bp = (C.c_void_p * LAYERS)(*[t.data_ptr() for t in bs])
-        lp = (C.c_void_p * 5)(*[t.data_ptr() for t in ls])
-        _lib.check(lib.trase_lpips_pack(wp, bp, lp, _lib.ptr(self.pack), self.pack.numel(), _device_index(dev), _stream(dev)),
-                   "trase_lpips_pack")
-        torch.cuda.current_stream(dev).synchronize()        # ws / bs / ls may be temporaries
+    def _tensors(self):
+        return [w for w, _ in self._pairs], [b for _, b in self._pairs], self._lins
+
+    def _pack(self, lib, arrays, device_index, stream):
+        _lib.check(lib.trase_lpips_pack(*arrays, _lib.ptr(self.pack), self.pack.numel(), device_index, stream), "trase_lpips_pack")
         self.packs += 1
-        return self
 
     def layers_device(self, x, y, *, maps=None, taps=None):
         """the launch sequence: -> (5,) float64 device tensor of the layer values; ``maps`` / ``taps`` = (taps_x, taps_y): flat fp32
@@ -196,11 +135,10 @@ class LPIPSVGG:
     def __call__(self, x, y, *, return_layers=False, return_maps=False, return_taps=False):
         for t in (x, y):
             if not torch.is_tensor(t) or t.device.type != "cuda":
-                raise RuntimeError("trase_amd.lpips runs on the GPU only (there is no CPU path)")
+                raise self._gpu_only()
             if t.dim() == 4 and t.shape[0] > 1:
                 raise ValueError(f"LPIPSVGG: batches above 1 are not supported, got {tuple(t.shape)}")
-            if not ((t.dim() == 3 and t.shape[0] == 3) or (t.dim() == 4 and tuple(t.shape[:2]) == (1, 3))):
-                raise ValueError(f"LPIPSVGG: expected a (3, H, W) or (1, 3, H, W) image, got {tuple(t.shape)}")
+            vgg.check_image(t, "LPIPSVGG")
             if t.dtype != torch.float32:
                 raise ValueError(f"LPIPSVGG: the images must be fp32, got {t.dtype}")
             if t.requires_grad:

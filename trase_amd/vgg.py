@@ -1,4 +1,8 @@
-"""The style-transfer loop's feature extractor (style_transfer/fx.py; train_style_transfer_nnfm.py:141-215) on the GPU:
+"""VGG16 on the GPU, written down once: the thirteen-layer table (``NET_*``), the seeded draw, ``weight_pairs``, the
+normalisation constants' arrays and the device / pack bookkeeping (``_Packed``) below serve this module's extractor and the
+LPIPS metric of ``trase_amd.lpips``.
+
+The style-transfer loop's feature extractor (style_transfer/fx.py; train_style_transfer_nnfm.py:141-215) on the GPU:
 VGG16's 3x3 convolutions up to conv4_1 as HIP kernels (csrc/vgg.hip), forward and gradient to the image.
 
 ``VGG16Features(weights, key)`` packs the weights once; ``net(image)`` returns the PRE-ReLU output of convolution ``key`` as
@@ -16,10 +20,17 @@ import torch
 from . import _lib
 from .rasterizer import _bytes, _stream
 
-KEYS = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1")
-FEATURE_INDEX = (0, 2, 5, 7, 10, 12, 14, 17)            # torchvision's vgg16().features positions of the eight convolutions
-CHANNELS = (3, 64, 64, 128, 128, 256, 256, 256, 512)    # channels in front of layer 1, behind layers 1 .. 8
-POOL_AFTER = (2, 4, 7)                                  # MaxPool2d(2, 2) follows these layers (1-based)
+# the network's thirteen convolutions (csrc/vgg.hip: vg_chan, vg_shift, vg_pooled)
+NET_KEYS = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3", "conv5_1",
+            "conv5_2", "conv5_3")
+NET_FEATURE_INDEX = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)   # torchvision's vgg16().features positions of the convolutions
+NET_CHANNELS = (3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)   # in front of layer 1, behind layers 1 .. 13
+NET_POOL_AFTER = (2, 4, 7, 10)                          # MaxPool2d(2, 2) follows these layers (1-based)
+CUT_MAX = 8                                             # the extractor cuts behind conv1_1 .. conv4_1
+KEYS = NET_KEYS[:CUT_MAX]
+FEATURE_INDEX = NET_FEATURE_INDEX[:CUT_MAX]
+CHANNELS = NET_CHANNELS[:CUT_MAX + 1]                   # channels in front of layer 1, behind layers 1 .. 8
+POOL_AFTER = tuple(p for p in NET_POOL_AFTER if p < CUT_MAX)
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
 
@@ -37,39 +48,53 @@ def pools_before(layer: int) -> int:
     return sum(1 for p in POOL_AFTER if p < layer)
 
 
-def vgg16_random_weights(seed: int, key: str = "conv4_1", device="cpu"):
-    """He-scaled seeded weights of the layers up to ``key``: std = sqrt(2 / (9 Cin)), biases 0.05 * randn; [(w, b), ...]"""
-    g = torch.Generator().manual_seed(int(seed))
+def random_pairs(g, layers: int, device):
+    """the first ``layers`` layers drawn from generator ``g``, layer by layer (weight, then bias): std = sqrt(2 / (9 Cin)), biases
+    0.05 * randn"""
     out = []
-    for l in range(1, key_layers(key) + 1):
-        cin, cout = CHANNELS[l - 1], CHANNELS[l]
+    for l in range(1, layers + 1):
+        cin, cout = NET_CHANNELS[l - 1], NET_CHANNELS[l]
         w = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (9 * cin))
         b = 0.05 * torch.randn(cout, generator=g)
         out.append((w.to(device), b.to(device)))
     return out
 
 
-def weight_pairs(weights, layers: int):
-    """[(w, b)] * layers out of a torchvision state dict (``features.N.weight`` or bare ``N.weight``) or a list of pairs"""
+def vgg16_random_weights(seed: int, key: str = "conv4_1", device="cpu"):
+    """He-scaled seeded weights of the layers up to ``key`` (``random_pairs``); [(w, b), ...]"""
+    return random_pairs(torch.Generator().manual_seed(int(seed)), key_layers(key), device)
+
+
+def weight_pairs(weights, layers: int, who: str = "VGG16Features", exact: bool = False):
+    """[(w, b)] * layers out of a torchvision state dict (``features.N.weight`` or bare ``N.weight``) or a list of pairs; a longer
+    list is cut to ``layers``, or with ``exact`` refused; ``who`` speaks in the messages"""
     if isinstance(weights, dict):
         pairs = []
-        for idx in FEATURE_INDEX[:layers]:
+        for idx in NET_FEATURE_INDEX[:layers]:
             for prefix in (f"features.{idx}.", f"{idx}."):
                 if prefix + "weight" in weights:
                     pairs.append((weights[prefix + "weight"], weights[prefix + "bias"]))
                     break
             else:
-                raise KeyError(f"VGG16Features: the state dict has neither features.{idx}.weight nor {idx}.weight")
+                raise KeyError(f"{who}: the state dict has neither features.{idx}.weight nor {idx}.weight")
     else:
         pairs = [tuple(p) for p in weights]
-        if len(pairs) < layers:
-            raise ValueError(f"VGG16Features: {layers} (weight, bias) pairs are needed, got {len(pairs)}")
+        if len(pairs) < layers or (exact and len(pairs) != layers):
+            raise ValueError(f"{who}: {layers} (weight, bias) pairs are needed, got {len(pairs)}")
         pairs = pairs[:layers]
     for l, (w, b) in enumerate(pairs, start=1):
-        if tuple(w.shape) != (CHANNELS[l], CHANNELS[l - 1], 3, 3) or tuple(b.shape) != (CHANNELS[l],):
-            raise ValueError(f"VGG16Features: layer {KEYS[l - 1]} expects weight {(CHANNELS[l], CHANNELS[l - 1], 3, 3)} and bias "
-                             f"{(CHANNELS[l],)}, got {tuple(w.shape)} and {tuple(b.shape)}")
+        want = (NET_CHANNELS[l], NET_CHANNELS[l - 1], 3, 3), (NET_CHANNELS[l],)
+        if (tuple(w.shape), tuple(b.shape)) != want:
+            raise ValueError(f"{who}: layer {NET_KEYS[l - 1]} expects weight {want[0]} and bias {want[1]}, got {tuple(w.shape)} and "
+                             f"{tuple(b.shape)}")
     return pairs
+
+
+def norm_arrays(mean, std):
+    """(mean, 1 / std) as the ``float[3]`` arguments of the forward entries; the reciprocal in fp32: what the kernels multiply by"""
+    m = torch.tensor(mean, dtype=torch.float32)
+    inv = 1.0 / torch.tensor(std, dtype=torch.float32)
+    return (C.c_float * 3)(*m.tolist()), (C.c_float * 3)(*inv.tolist())
 
 
 def sizes(layers: int, H: int, W: int):
@@ -83,6 +108,61 @@ def sizes(layers: int, H: int, W: int):
 
 def _device_index(dev):
     return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def _indexed(device):
+    """``torch.device(device)`` with the current index filled in for a bare "cuda": tensors always carry one"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def check_image(t, who: str):
+    if not ((t.dim() == 3 and t.shape[0] == 3) or (t.dim() == 4 and tuple(t.shape[:2]) == (1, 3))):
+        raise ValueError(f"{who}: expected a (3, H, W) or (1, 3, H, W) image, got {tuple(t.shape)}")
+
+
+class _Packed:
+    """Device and pack bookkeeping of a network whose weights are packed once.  A subclass sets ``MODULE`` (for the messages) and
+    ``self._pairs``, and gives ``_pack_bytes()``, ``_tensors()`` (the groups of tensors the C pack takes: weights, biases, ...)
+    and ``_pack(lib, arrays, device_index, stream)`` (the C call on arrays of their device pointers)."""
+
+    def _gpu_only(self):
+        return RuntimeError(f"{self.MODULE} runs on the GPU only (there is no CPU path)")
+
+    def _place(self, device):
+        """the end of ``__init__``: the device asked for, else the weights' if they are on one; packs when there is one"""
+        self.pack = None
+        self.device = _indexed(device) if device is not None else None
+        if self.device is None and self._pairs[0][0].device.type == "cuda":
+            self.device = self._pairs[0][0].device
+        if self.device is not None:
+            self.repack()
+
+    def to(self, device):
+        device = _indexed(device)
+        if device.type != "cuda":
+            raise self._gpu_only()
+        if self.device != device or self.pack is None:
+            self.device = device
+            self.repack()
+        return self
+
+    def repack(self):
+        """pack the weights as they are now (after the caller changed them in place)"""
+        lib = _lib.load()
+        dev = self.device
+        if dev is None or dev.type != "cuda":
+            raise self._gpu_only()
+        staged = [[t.detach().to(dev, torch.float32).contiguous() for t in group] for group in self._tensors()]
+        pack_bytes = self._pack_bytes()
+        if self.pack is None or self.pack.numel() != pack_bytes or self.pack.device != dev:
+            self.pack = _bytes(pack_bytes, dev)
+        arrays = [(C.c_void_p * len(group))(*[t.data_ptr() for t in group]) for group in staged]
+        self._pack(lib, arrays, _device_index(dev), _stream(dev))
+        torch.cuda.current_stream(dev).synchronize()        # the staged copies may be temporaries
+        return self
 
 
 class _VGG(torch.autograd.Function):
@@ -123,13 +203,15 @@ class _VGG(torch.autograd.Function):
 _WEIGHTS_WARNED = False
 
 
-class VGG16Features:
+class VGG16Features(_Packed):
     """VGG16 ``features`` cut at ``key``: ``net(image)`` -> ``(1, C, h, w)`` fp32, the pre-ReLU output of that convolution.
 
     ``weights``: a state dict with torchvision's names (``features.{0,2,5,7,10,12,14,17}.{weight,bias}`` or the bare ``features``
     spelling) or a list of ``(w, b)`` pairs; only the layers up to ``key`` are needed.  They are packed at construction --
     call ``repack()`` after changing them.  The weights are constants here (weights that require grad are detached, with one
     warning): the only gradient is the one to the image."""
+
+    MODULE = "trase_amd.vgg"
 
     def __init__(self, weights, key: str = "conv4_1", *, normalize: bool = True, mean=MEAN, std=STD, device=None):
         global _WEIGHTS_WARNED
@@ -142,46 +224,17 @@ class VGG16Features:
             _WEIGHTS_WARNED = True
         self._pairs = pairs
         self.normalize = bool(normalize)
-        if self.normalize:
-            m = torch.tensor(mean, dtype=torch.float32)
-            inv = 1.0 / torch.tensor(std, dtype=torch.float32)            # fp32 reciprocal: what the kernels multiply by
-            self._mean = (C.c_float * 3)(*m.tolist())
-            self._inv_std = (C.c_float * 3)(*inv.tolist())
-        else:
-            self._mean = self._inv_std = None
-        self.pack = None
-        self.device = torch.device(device) if device is not None else None
-        if self.device is None and pairs[0][0].device.type == "cuda":
-            self.device = pairs[0][0].device
-        if self.device is not None:
-            self.repack()
+        self._mean, self._inv_std = norm_arrays(mean, std) if self.normalize else (None, None)
+        self._place(device)
 
-    def to(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("trase_amd.vgg runs on the GPU only (there is no CPU path)")
-        if self.device != device or self.pack is None:
-            self.device = device
-            self.repack()
-        return self
+    def _pack_bytes(self):
+        return sizes(self.layers, 8, 8)[0]
 
-    def repack(self):
-        """pack the weights as they are now (after the caller changed them in place)"""
-        lib = _lib.load()
-        dev = self.device
-        if dev is None or dev.type != "cuda":
-            raise RuntimeError("trase_amd.vgg runs on the GPU only (there is no CPU path)")
-        ws = [w.detach().to(dev, torch.float32).contiguous() for w, _ in self._pairs]
-        bs = [b.detach().to(dev, torch.float32).contiguous() for _, b in self._pairs]
-        pack_bytes = sizes(self.layers, 8, 8)[0]
-        if self.pack is None or self.pack.numel() != pack_bytes or self.pack.device != dev:
-            self.pack = _bytes(pack_bytes, dev)
-        wp = (C.c_void_p * self.layers)(*[t.data_ptr() for t in ws])
-        bp = (C.c_void_p * self.layers)(*[t.data_ptr() for t in bs])
-        _lib.check(lib.trase_vgg_pack(self.layers, wp, bp, _lib.ptr(self.pack), self.pack.numel(), _device_index(dev), _stream(dev)),
-                   "trase_vgg_pack")
-        torch.cuda.current_stream(dev).synchronize()        # ws / bs may be temporaries
-        return self
+    def _tensors(self):
+        return [w for w, _ in self._pairs], [b for _, b in self._pairs]
+
+    def _pack(self, lib, arrays, device_index, stream):
+        _lib.check(lib.trase_vgg_pack(self.layers, *arrays, _lib.ptr(self.pack), self.pack.numel(), device_index, stream), "trase_vgg_pack")
 
     def out_shape(self, H: int, W: int):
         p = pools_before(self.layers)
@@ -189,9 +242,8 @@ class VGG16Features:
 
     def __call__(self, image: torch.Tensor) -> torch.Tensor:
         if image.device.type != "cuda":
-            raise RuntimeError("trase_amd.vgg runs on the GPU only (there is no CPU path)")
-        if not ((image.dim() == 3 and image.shape[0] == 3) or (image.dim() == 4 and tuple(image.shape[:2]) == (1, 3))):
-            raise ValueError(f"VGG16Features: expected a (3, H, W) or (1, 3, H, W) image, got {tuple(image.shape)}")
+            raise self._gpu_only()
+        check_image(image, "VGG16Features")
         if self.pack is None or self.device != image.device:
             self.to(image.device)
         # under no_grad, or for an image that needs no gradient, nothing is kept
