@@ -769,6 +769,22 @@ int trase_frame_pack(const uint8_t* hwc, int32_t H, int32_t W, int32_t channels,
 int trase_frame_unpack(const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, float* chw, int32_t device, trase_stream_t stream);
 int trase_frame_black_mask(const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, int32_t h, int32_t w, uint8_t* mask, int32_t device,
                            trase_stream_t stream);
+/* trase_frame_resize: the frame at another size, bit for bit what PILtoTorch's pil_image.resize(resolution) gives on the RGB bytes
+ *   (Pillow, mode "RGB", the default filter BICUBIC, no box, no reducing_gap): per axis ImagingResample's coefficient rows -- double
+ *   arithmetic in Pillow's order, normalised by the sum taken in tap order, rounded to 22 fractional bits -- then the horizontal
+ *   pass into bytes and the vertical pass on those, each clamp(((1 << 21) + sum coeff * byte) >> 22, 0, 255); an axis whose size
+ *   does not change is skipped.  One launch, no workspace.  src (device): src_layout 3 = (src_H, src_W, 3) bytes; 4 =
+ *   (src_H, src_W, 4), the alpha dropped or, with a background (three HOST floats), composited first as trase_frame_pack does,
+ *   then resized as RGB; TRASE_FRAME_PLANAR = the planes of a frame, rows src_pitch >= src_W bytes apart (src_pitch is ignored
+ *   otherwise).  No byte at or past the end of the source is read.  planes, H, W, pitch: the destination frame, padding written as
+ *   0.  Refusals: trase_frame_pack's, a layout other than these, and an axis that shrinks by more than 16 (src > 16 * dst).
+ *   Equal sizes: layouts 3 and 4 give the bits of trase_frame_pack, a planar source is copied.
+ * trase_selftest_resize_tables: the coefficient rows the kernel computes, by the same __device__ function: coeffs (out, ksize)
+ *   int32, zero beyond n, ksize = (int)ceil(2 * max(in / out, 1)) * 2 + 1; bounds (out, 2) int32 = (xmin, n).  in <= 16 * out. */
+#define TRASE_FRAME_PLANAR 1
+int trase_frame_resize(const uint8_t* src, int32_t src_H, int32_t src_W, int32_t src_layout, int32_t src_pitch, const float* background,
+                       uint8_t* planes, int32_t H, int32_t W, int32_t pitch, int32_t device, trase_stream_t stream);
+int trase_selftest_resize_tables(int32_t in, int32_t out, int32_t* coeffs, int32_t* bounds, int32_t device, trase_stream_t stream);
 int trase_loss_l1_ssim_forward_u8(const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags, float* out2,
                                   void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
 int trase_loss_l1_ssim_backward_u8(const float* img, const uint8_t* planes, int32_t H, int32_t W, int32_t pitch, uint32_t flags,

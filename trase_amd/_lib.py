@@ -15,7 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TRASE_RAST_LIB") or os.path.join(_HERE, "lib", "libtrase_rast.so")   # override: A/B builds
 
 c_float_p = C.POINTER(C.c_float)
-RIGID_STATE_FLOATS = 16     # TRASE_RIGID_STATE_FLOATS of include/trase_rast.h: floats per row between the rigid fit's two passes
+FRAME_PLANAR = 1            # TRASE_FRAME_PLANAR: the src_layout of trase_frame_resize for the planes of a frame
+RIGID_STATE_FLOATS = 16    # TRASE_RIGID_STATE_FLOATS of include/trase_rast.h: floats per row between the rigid fit's two passes
 
 
 class RastSettings(C.Structure):
@@ -283,6 +284,9 @@ SYMBOLS = [
     ("trase_frame_unpack", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     ("trase_frame_black_mask", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                          C.c_void_p]),
+    ("trase_frame_resize", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float * 3), C.c_void_p, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    ("trase_selftest_resize_tables", C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("trase_loss_l1_ssim_forward_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_int32, C.c_void_p]),
     ("trase_loss_l1_ssim_backward_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,

@@ -5,10 +5,13 @@ Every ground-truth frame of the reference is the image of a byte array: ``PILtoT
 that as fp32 on the device (scene/cameras.py:60, 24.9 MB per 1080p frame) or, with ``load_image_on_the_fly``, rebuilds it on
 the host in every iteration (train.py:220-230).  ``ByteFrame`` keeps the bytes (6.2 MB), planar so that the loss kernels read
 one plane per channel; ``trase_amd.losses`` accepts it wherever it accepts the fp32 tensor and returns bitwise the same
-results, and ``black_mask`` gives ``--mask_black_bg`` its mask (train.py:231-234, :253-269) without the fp32 frame."""
+results, and ``black_mask`` gives ``--mask_black_bg`` its mask (train.py:231-234, :253-269) without the fp32 frame.  With
+``resolution=(W, H)`` the frame is ``pil_image.resize(resolution)`` of the bytes -- Pillow's default bicubic filter, bit for bit,
+in the launch that writes the planes -- which is what ``PILtoTorch`` does before it takes them."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -17,8 +20,47 @@ from . import _lib
 from .rasterizer import _stream
 
 
+MAX_SHRINK = 16          # trase_frame_resize: each axis shrinks by at most this (in <= 16 * out)
+
+
 def _dev_index(dev) -> int:
     return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def camera_resolution(orig_w, orig_h, resolution=-1, resolution_scale=1.0):
+    """The ``(W, H)`` that ``loadCam`` (utils/camera_utils.py:30-48) hands to ``PILtoTorch``: ``round`` of the quotient for
+    ``--resolution`` 1 / 2 / 4 / 8; for -1 the source's own size, or 1600 pixels wide for a wider source; otherwise
+    ``resolution`` pixels wide; both of the latter through ``int()``."""
+    if resolution in [1, 2, 4, 8]:
+        return round(orig_w / (resolution_scale * resolution)), round(orig_h / (resolution_scale * resolution))
+    if resolution == -1:
+        global_down = orig_w / 1600 if orig_w > 1600 else 1
+    else:
+        global_down = orig_w / resolution
+    scale = float(global_down) * float(resolution_scale)
+    return int(orig_w / scale), int(orig_h / scale)
+
+
+@torch.no_grad()
+def resize_tables(in_size, out_size, device):
+    """The coefficient rows the resize kernel computes for one axis, by its own device function: ``(coeffs, bounds)``, int32
+    tensors of (out, ksize) -- zero beyond n -- and (out, 2) = (xmin, n)."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"resize_tables: sizes must be at least 1 (got {in_size} -> {out_size})")
+    if in_size > MAX_SHRINK * out_size:
+        raise ValueError(f"resize_tables: an axis may shrink by at most {MAX_SHRINK} (got {in_size} -> {out_size})")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("trase_amd.frames runs on the GPU only (there is no CPU path)")
+    ksize = int(math.ceil(2.0 * max(in_size / out_size, 1.0))) * 2 + 1
+    coeffs = torch.empty((out_size, ksize), dtype=torch.int32, device=dev)
+    bounds = torch.empty((out_size, 2), dtype=torch.int32, device=dev)
+    dev = coeffs.device
+    lib = _lib.load()
+    _lib.check(lib.trase_selftest_resize_tables(in_size, out_size, _lib.ptr(coeffs), _lib.ptr(bounds), _dev_index(dev), _stream(dev)),
+               "trase_selftest_resize_tables")
+    return coeffs, bounds
 
 
 class ByteFrame:
@@ -88,9 +130,29 @@ class ByteFrame:
         return src, int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
 
     @staticmethod
+    def _resolution(resolution, who):
+        """``(W, H)`` as two ints at least 1, or None"""
+        if resolution is None:
+            return None
+        try:
+            W, H = resolution
+            W, H = int(W), int(H)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: resolution must be (W, H) (got {resolution!r})") from None
+        if W < 1 or H < 1:
+            raise ValueError(f"{who}: resolution must be at least 1 x 1 (got {W} x {H})")
+        return W, H
+
+    @staticmethod
+    def _check_shrink(who, sH, sW, H, W):
+        if sH > MAX_SHRINK * H or sW > MAX_SHRINK * W:
+            raise ValueError(f"{who}: an axis may shrink by at most {MAX_SHRINK} (got {sW} x {sH} -> {W} x {H})")
+
+    @staticmethod
     @torch.no_grad()
-    def _pack(hwc, background, device) -> "ByteFrame":
-        src, H, W, ch = ByteFrame.host_array(hwc)
+    def _pack(hwc, background, device, resolution=None) -> "ByteFrame":
+        who = "ByteFrame.from_array" if background is None else "ByteFrame.from_rgba"
+        src, sH, sW, ch = ByteFrame.host_array(hwc)
         bg = None
         if background is not None:
             if ch != 4:
@@ -100,6 +162,8 @@ class ByteFrame:
             if b.numel() != 3:
                 raise ValueError(f"ByteFrame.from_rgba: the background must hold three values (got {b.numel()})")
             bg = (C.c_float * 3)(*b.tolist())
+        W, H = ByteFrame._resolution(resolution, who) or (sW, sH)
+        ByteFrame._check_shrink(who, sH, sW, H, W)
         dev = torch.device(device) if device is not None else src.device
         if dev.type != "cuda":
             raise RuntimeError("trase_amd.frames runs on the GPU only (there is no CPU path)")
@@ -108,25 +172,46 @@ class ByteFrame:
         pitch = ByteFrame.pitch_for(W)
         data = torch.empty(3 * H * pitch, dtype=torch.uint8, device=dev)
         lib = _lib.load()
-        _lib.check(lib.trase_frame_pack(_lib.ptr(src), H, W, ch, bg, _lib.ptr(data), pitch, _dev_index(dev), _stream(dev)),
-                   "trase_frame_pack")
+        if (H, W) == (sH, sW):
+            _lib.check(lib.trase_frame_pack(_lib.ptr(src), H, W, ch, bg, _lib.ptr(data), pitch, _dev_index(dev), _stream(dev)),
+                       "trase_frame_pack")
+        else:
+            _lib.check(lib.trase_frame_resize(_lib.ptr(src), sH, sW, ch, 0, bg, _lib.ptr(data), H, W, pitch, _dev_index(dev),
+                                              _stream(dev)), "trase_frame_resize")
         return ByteFrame(data, H, W)
 
     @staticmethod
-    def from_array(hwc, device=None) -> "ByteFrame":
+    def from_array(hwc, device=None, *, resolution=None) -> "ByteFrame":
         """``np.array(pil_image)``, (H, W, 3) or (H, W, 4) uint8 on the host or the device: one upload of the bytes as they are
         and one launch that writes the planes.  A fourth channel is dropped (utils/camera_utils.py:51).  ``device``: where the
-        frame lives (default: the source's device)."""
-        return ByteFrame._pack(hwc, None, device)
+        frame lives (default: the source's device).  ``resolution``: ``(W, H)``, the argument of ``PILtoTorch`` -- the frame is
+        ``pil_image.resize(resolution)`` of the RGB bytes (Pillow's default bicubic filter, bit for bit), formed by that one
+        launch; ``None`` or the source's own size packs the bytes as they are."""
+        return ByteFrame._pack(hwc, None, device, resolution)
 
     @staticmethod
-    def from_rgba(rgba, background, device=None) -> "ByteFrame":
+    def from_rgba(rgba, background, device=None, *, resolution=None) -> "ByteFrame":
         """The on-the-fly frame of train.py:221-228 from ``np.array(image.convert("RGBA"))``: per channel the byte
         ``trunc(((v / 255.0) * (a / 255.0) + bg * (1 - a / 255.0)) * 255.0)``, evaluated on the device in float64 exactly as numpy
-        evaluates it (``background``: three values, taken as float32 like the reference's tensor)."""
+        evaluates it (``background``: three values, taken as float32 like the reference's tensor).  ``resolution``: ``(W, H)`` of
+        train.py:229 -- the composite is resized as an RGB image (what the reference does where every alpha is 255)."""
         if background is None:
             raise ValueError("ByteFrame.from_rgba: a background is required (use from_array to drop the alpha)")
-        return ByteFrame._pack(rgba, background, device)
+        return ByteFrame._pack(rgba, background, device, resolution)
+
+    @torch.no_grad()
+    def resized(self, resolution) -> "ByteFrame":
+        """A new frame at ``resolution = (W, H)`` from this resident one (the coarser levels of ``resolution_scales``): Pillow's
+        bicubic resize of its bytes, one launch."""
+        dev = self._gpu().data.device
+        W, H = ByteFrame._resolution(resolution, "ByteFrame.resized") or (self.W, self.H)
+        ByteFrame._check_shrink("ByteFrame.resized", self.H, self.W, H, W)
+        pitch = ByteFrame.pitch_for(W)
+        data = torch.empty(3 * H * pitch, dtype=torch.uint8, device=dev)
+        lib = _lib.load()
+        _lib.check(lib.trase_frame_resize(_lib.ptr(self.data), self.H, self.W, _lib.FRAME_PLANAR, self.pitch, None, _lib.ptr(data), H, W,
+                                          pitch, _dev_index(dev), _stream(dev)), "trase_frame_resize")
+        return ByteFrame(data, H, W)
 
     @staticmethod
     @torch.no_grad()
