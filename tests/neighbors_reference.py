@@ -254,3 +254,62 @@ def max_grid_distance_units(lo, hi, step):
     below 2^24 for fp32 to hold every partial sum exactly."""
     cells = int(round((hi - lo) / step))
     return 3 * (cells - 1) ** 2
+
+
+# ---- distCUDA2 and the narrow k-NN's edge scenes --------------------------------------------------------------------------------
+def dist2_lex(points):
+    """simple_knn's distCUDA2: for every row the three smallest squared distances to the OTHER rows (other by index: a copy of
+    the point counts, with distance 0), fewer where the cloud has fewer than 4 rows.  -> (their sums in float64, the fp32
+    value float32(sum) / float32(3), an IEEE division; the mean of three only from 4 rows on, the sum is always divided by 3)."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    n = len(p)
+    sums = np.zeros(n, dtype=np.float64)
+    have = min(3, n - 1)
+    for lo in range(0, n, 512):
+        d = p[lo:lo + 512, None, :] - p[None, :, :]
+        d2 = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
+        rows = np.arange(len(d2))
+        d2[rows, lo + rows] = np.inf                                   # not itself
+        if have > 0:
+            sums[lo:lo + 512] = np.sort(d2, axis=1)[:, :have].sum(axis=1)
+    return sums, sums.astype(np.float32) / np.float32(3)
+
+
+def axis_line_cloud(n, axis, lo, hi, step, seed, include=()):
+    """n distinct points of the lattice `step` on the line along `axis` from lo to hi, both end points among them (rows 0 and
+    1), so that the cloud's extent is exactly hi - lo along the axis and exactly 0 along the other two (which sit on lattice
+    values inside [lo, hi)).  include: offsets from lo (multiples of step) that must be among the points, e.g. cell faces."""
+    g = np.random.default_rng(seed)
+    cells = int(round((hi - lo) / step))
+    fixed = [0, cells] + [int(round(o / step)) for o in include]
+    fixed = list(dict.fromkeys(fixed))
+    assert len(fixed) <= n <= cells + 1 and all(0 <= f <= cells for f in fixed)
+    rest = np.setdiff1d(np.arange(cells + 1), fixed)
+    pos = np.concatenate([fixed, g.choice(rest, n - len(fixed), replace=False)]).astype(np.int64)
+    pos[2:] = g.permutation(pos[2:])
+    q = np.empty((n, 3), dtype=np.int64)
+    q[:, (axis + 1) % 3] = cells // 3
+    q[:, (axis + 2) % 3] = cells // 2
+    q[:, axis] = pos
+    return (lo + q * step).astype(np.float32)
+
+
+def line_cell_width(n, extent, occ=4.0):
+    """The cell width knn_params_kernel gives a collinear cloud of n points: h1 = occ * extent / n in fp32 (one multiply, one
+    divide), not below extent / 2^20."""
+    h = np.float32(np.float32(occ) * np.float32(extent)) / np.float32(n)
+    return np.maximum(h, np.float32(extent) * np.float32(1.0 / 1048576.0))
+
+
+def line_face_disagreements(n, extent, step, occ=4.0):
+    """The lattice offsets x in [0, extent] (x = coordinate - origin, exact in fp32) whose cell as the kernels compute it,
+    int(fl(x * fl(1 / h))), is not floor(x / h) in float64, with h = line_cell_width(n, extent): the positions on (or within a
+    rounding of) a cell face.  -> (offsets in float64, h)."""
+    h = line_cell_width(n, extent, occ)
+    inv_h = np.float32(1.0) / h
+    x = np.arange(int(round(extent / step)) + 1, dtype=np.float64) * step
+    x32 = x.astype(np.float32)
+    assert np.array_equal(x32.astype(np.float64), x)
+    cell32 = (x32 * inv_h).astype(np.int64)
+    cell64 = np.floor(x / float(h)).astype(np.int64)
+    return x[cell32 != cell64], h

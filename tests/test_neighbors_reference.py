@@ -158,6 +158,71 @@ def test_k_above_the_limit_is_refused_in_python():
     assert losses.loss_rigid_body_motion_reg_loss is nb.loss_rigid_body_motion_reg_loss
 
 
+def test_dist2_lex_equals_the_kdtree():
+    from scipy.spatial import cKDTree
+    g = np.random.default_rng(4)
+    p = g.normal(size=(1500, 3)) * [1.0, 0.3, 2.0]
+    sums, f32 = nr.dist2_lex(p)
+    d, _ = cKDTree(p).query(p, k=4)
+    want = (d[:, 1:] ** 2).sum(axis=1)
+    assert np.abs(sums - want).max() <= 1e-12 * want.max()
+    assert f32.dtype == np.float32 and np.array_equal(f32, sums.astype(np.float32) / np.float32(3))
+    # copies are other points (distance 0); fewer than 4 rows: what exists
+    q = np.array([[0, 0, 0], [2, 0, 0], [0, 0, 0], [0, 1, 0]], dtype=np.float64)
+    assert nr.dist2_lex(q)[0].tolist() == [1.0 + 4.0, 4.0 + 4.0 + 5.0, 1.0 + 4.0, 1.0 + 1.0 + 5.0]
+    assert nr.dist2_lex(q[:3])[0].tolist() == [4.0, 8.0, 4.0] and nr.dist2_lex(q[:2])[0].tolist() == [4.0, 4.0]
+    assert nr.dist2_lex(q[:1])[0].tolist() == [0.0] and nr.dist2_lex(q[:1])[1].tolist() == [0.0]
+
+
+def test_axis_lines_and_their_cell_width():
+    for axis in (0, 1, 2):
+        c = nr.axis_line_cloud(24, axis, -4.0, 4.0, 1.0 / 256, 9, include=(4.0, 4.0 - 1.0 / 256))
+        ext = c.max(axis=0) - c.min(axis=0)
+        assert c.dtype == np.float32 and c.shape == (24, 3)
+        assert ext[axis] == 8.0 and ext[(axis + 1) % 3] == 0.0 and ext[(axis + 2) % 3] == 0.0
+        assert c[0, axis] == -4.0 and c[1, axis] == 4.0 and len(np.unique(c[:, axis])) == 24
+        assert 0.0 in c[:, axis] and np.float32(-1.0 / 256) in c[:, axis]
+        assert np.array_equal(c * 256, np.round(c * 256))
+    assert nr.line_cell_width(32, 8.0) == 1.0 and nr.line_cell_width(32, 8.0).dtype == np.float32
+    assert nr.line_cell_width(24, 8.0) == np.float32(32.0) / np.float32(24.0)
+    assert nr.line_cell_width(1, 8.0, occ=1e-9) == np.float32(8.0) * np.float32(2.0 ** -20)        # the 2^20-cells floor
+
+
+def test_face_lines_have_positions_on_the_wrong_side_of_a_face():
+    """The premise of the cell-face cases: with 24 or 48 points on a line of extent 8 some positions of the 1/256 lattice get an
+    fp32 cell that is not floor(x / h) (h = 4/3, 2/3 rounded up, 1/h rounded to 0.75, 1.5); with 32 points h = 1 and none does."""
+    from tests.test_gpu_knn_narrow import FACE_LINE, FACE_NS, face_case, face_offsets
+    step, lo, hi = FACE_LINE
+    assert FACE_NS == (24, 32, 48)
+    assert nr.line_face_disagreements(24, hi - lo, step)[0].tolist() == [4.0, 8.0]
+    assert nr.line_face_disagreements(48, hi - lo, step)[0].tolist() == [2.0, 4.0, 6.0, 8.0]
+    wrong, h = nr.line_face_disagreements(32, hi - lo, step)
+    assert len(wrong) == 0 and h == 1.0
+    for n in FACE_NS:
+        near, wrong = face_offsets(n)
+        for axis in (0, 1, 2):
+            cloud, q = face_case(n, axis)
+            assert len(cloud) == n and cloud[:, axis].max() - cloud[:, axis].min() == hi - lo
+            assert set((wrong + lo).tolist()) <= set(cloud[:, axis].astype(np.float64).tolist())      # points ON those faces
+            assert set((near + lo).tolist()) <= set(q[:, axis].astype(np.float64).tolist())
+            both = np.concatenate([cloud, q]).astype(np.float64) / step
+            assert np.array_equal(both, np.round(both))
+            assert ((both.max(axis=0) - both.min(axis=0)) ** 2).sum() < 2 ** 24            # the largest squared distance
+
+
+def test_narrow_lattices_keep_fp32_sums_exact():
+    """distCUDA2 adds three squared distances in fp32: in units of step^2 the sum is an integer that must stay below 2^24, in
+    every exact case of tests/test_gpu_knn_narrow.py (the squared distances themselves: the test below and the one above)."""
+    from tests.test_gpu_knn_narrow import FACE_LINE, FACE_NS, dist2_cloud, dist2_plan, face_case
+    clouds = [dist2_cloud(kind, n, grid) for kind, n, grid in dist2_plan()]
+    clouds += [(face_case(n, axis)[0], FACE_LINE[0]) for n in FACE_NS for axis in (0, 1, 2)]
+    for cloud, step in clouds:
+        sums, f32 = nr.dist2_lex(cloud)
+        units = sums / (step * step)
+        assert np.array_equal(units, np.round(units)) and units.max() < 2 ** 24
+        assert np.array_equal(sums.astype(np.float32).astype(np.float64), sums)
+
+
 def test_grid_scenes_keep_fp32_distances_exact():
     """The premise of the exact k-NN tests: in units of the grid step every squared distance is an integer below 2^24, so
     fp32 holds every difference, product and partial sum exactly, in any order and with or without fused multiply-adds."""

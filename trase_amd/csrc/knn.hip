@@ -87,7 +87,9 @@ __global__ void knn_params_kernel(KnnParams* p, float occ) {
   const float h1 = occ * a / n;
   const float h2 = sqrtf(occ * a * b / n);
   const float h3 = cbrtf(occ * a * b * c / n);
-  float h = (c < h2) ? ((b < h1) ? h1 : h2) : h3;  // effective dimensionality of the cloud
+  // effective dimensionality of the cloud; <=, so that an extent of exactly 0 (h2 = 0 under a collinear cloud) leaves its
+  // branch too: with < such a cloud got h3 = 0, the floor below, and queries that walk tens of thousands of empty shells
+  float h = (c <= h2) ? ((b <= h1) ? h1 : h2) : h3;
   h = fmaxf(h, a * (1.0f / 1048576.0f));           // at most 2^20 cells per axis
   if (!(h > 0.f)) h = 1.0f;                         // all points coincide
   p->h = h;
@@ -202,8 +204,14 @@ __device__ __forceinline__ void knn_walk(const KnnParams& p, float x, float y, f
             int ox, oy, oz;
             cell_of(p, qx, qy, qz, ox, oy, oz);
             if (ox != xx || oy != yy || oz != zz) continue;   // hash collision: belongs to another cell
-            const float dx = qx - x, dy = qy - y, dz = qz - z;
-            float d = dx * dx + dy * dy + dz * dz;
+            // the wide kernel's expression: differences and squares exact in float64, the sum rounded ONCE to fp32 (within
+            // 2^-24 relative; all in fp32 the three differences round as well, up to 5 * 2^-24)
+            // (the query is converted here, per candidate: hoisted out of the walk its three doubles cost KT = 8 a wave of
+            // occupancy, 64 -> 70 VGPRs and +9 % at K = 6; the empty statement keeps the compiler from hoisting them)
+            float xs = x, ys = y, zs = z;
+            asm volatile("" : "+v"(xs), "+v"(ys), "+v"(zs));
+            const double dx = (double)qx - (double)xs, dy = (double)qy - (double)ys, dz = (double)qz - (double)zs;
+            float d = (float)(dx * dx + dy * dy + dz * dz);
             uint32_t id = j;
             if (d < bd[KT - 1] || (d == bd[KT - 1] && id < bi[KT - 1])) {
               // sorted insertion (ties by index so the result does not depend on the bucket order)
@@ -338,8 +346,7 @@ __global__ __launch_bounds__(WAVE * KW_WAVES) void knn_points_wide_kernel(const 
                 int ox, oy, oz;
                 cell_of(p, qx, qy, qz, ox, oy, oz);
                 // differences and squares in float64 are exact, so d is the squared distance rounded ONCE (three roundings
-                // of the sum, each far below an fp32 ulp, aside): within 2^-24 relative where knn_walk's all-fp32 expression
-                // can be 5 * 2^-24 off.  Where that expression is exact -- coordinates on a grid -- the two agree bit for bit.
+                // of the sum, each far below an fp32 ulp, aside): within 2^-24 relative, the expression of knn_walk.
                 const double dx = (double)qx - (double)x, dy = (double)qy - (double)y, dz = (double)qz - (double)z;
                 const float d = (float)(dx * dx + dy * dy + dz * dz);
                 // (a hash collision belongs to another cell; a NaN or overflowed distance is never a neighbour, as in knn_walk)

@@ -749,9 +749,8 @@ def knn_points(p1: torch.Tensor, p2: torch.Tensor, lengths1=None, lengths2=None,
     """Same call contract as pytorch3d.ops.knn_points for the shapes TRASE uses: p1 (B,N1,3),
     p2 (B,N2,3) -> (dists (B,N1,K) squared L2, idx (B,N1,K) int64, knn).  1 <= K <= 256 (K <= 16: one thread per
     query; larger: one wave per query), rows ascending by (distance, index), idx 0 / distance 0 where p2 has fewer than K
-    points.  L2 only, full lengths.  K > 16 evaluates a squared distance in float64 rounded once to fp32, K <= 16 as the fp32
-    expression dx*dx + dy*dy + dz*dz: where that expression is inexact the two can differ in the last bits and in the order of
-    near-ties, so the first 16 columns of a K = 17 call need not equal the K = 16 call bit for bit."""
+    points.  L2 only, full lengths.  A squared distance is evaluated in float64 and rounded once to fp32 (within 2^-24
+    relative) at every K."""
     if not 1 <= int(K) <= KNN_MAX_K:
         raise ValueError(f"knn_points: need 1 <= K <= {KNN_MAX_K} (got {K})")
     if norm != 2 or lengths1 is not None or lengths2 is not None:
