@@ -231,9 +231,15 @@ def test_precomputed_colour_and_covariance_inputs():
 def test_lower_sh_degrees(deg):
     act, cam = small_case(n=300, w=80, h=64, feat=0, seed=10 + deg)
     st = settings_for(cam, sh_degree=deg)
-    g, _ = _gpu_call(act, st, need_grad=False)
-    o, _ = _oracle_call(act, st, gpu=g)
+    g, gl = _gpu_call(act, st)
+    o, ol = _oracle_call(act, st, gpu=g)
     _check_maps(g, o)
+    gi = _masked(torch.randn(3, 64, 80, generator=torch.Generator().manual_seed(deg)), o)
+    (o.image * gi.double()).sum().backward()
+    g[0].backward(gi.cuda())
+    _check_grads(gl, ol, o, ["means3D", "means2D", "opacities", "scales", "rotations", "shs"])
+    n = (deg + 1) ** 2                    # coefficients beyond the active degree take no part: exact zeros
+    assert float(gl["shs"].grad[:, n:].abs().max()) == 0.0
 
 
 def test_feature_only_loss_feature_state():
