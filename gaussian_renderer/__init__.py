@@ -4,6 +4,7 @@ reference checkout on PYTHONPATH and the training / rendering scripts run unmodi
 MI355X path.  ``render_composite`` and its rigid-edit helpers (gaussian_renderer/__init__.py:158-331 of the reference)
 are trase_amd/edit.py's."""
 from trase_amd.renderer import render  # noqa: F401
+from trase_amd.layers import render_layers  # noqa: F401
 from trase_amd.edit import (render_composite, rescale, rotate_by_euler_angles, rotate_by_matrix, rotmat2qvec,  # noqa: F401
                             rx, ry, rz, transform, translation)
 
@@ -12,5 +13,5 @@ try:   # render.py:30 imports GaussianModel through this module; available when 
 except Exception:   # pragma: no cover
     pass
 
-__all__ = ["render", "render_composite", "rotmat2qvec", "rx", "ry", "rz", "rescale", "rotate_by_euler_angles",
+__all__ = ["render", "render_layers", "render_composite", "rotmat2qvec", "rx", "ry", "rz", "rescale", "rotate_by_euler_angles",
            "rotate_by_matrix", "translation", "transform"]

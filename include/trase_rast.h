@@ -993,6 +993,28 @@ typedef struct TraseEvalFrame {
 } TraseEvalFrame;
 int trase_evaluate_frame(const TraseEvalFrame* f, const TraseRastWorkspace* ws, int32_t device, trase_stream_t stream);
 
+/* ---- colour layers: the view and up to ten per-Gaussian colour tables from one pass (render.py:197, :240, :296) -------------
+ * A per-Gaussian colour placed in feature channels 3l .. 3l+2 of an F = 32 forward is composited by exactly the arithmetic
+ * of the colour channels; what the feature channels lack is the background term of the colour epilogue.
+ * trase_layers_pack: ONE launch; out (P,32) fp32, 16-byte aligned: row i = [tables[0][i].rgb, tables[1][i].rgb, ..., 0 ... 0].
+ *   tables: HOST array of L device pointers to (P,3) fp32 tables, contiguous, each only 4-byte aligned.  Columns 3L .. 31
+ *   are +0.0f; nothing at or past row P is read or written.  P == 0 launches nothing.
+ * trase_layers_finish: ONE launch over a W x H frame, a thread owns 4 consecutive pixels of a row (16-byte accesses where the
+ *   planes allow it, scalar ones for row tails and W % 4 != 0).  planes: (32,H,W) fp32, the feature output of that forward.
+ *   For l < L, c < 3:  planes[3l + c] = fmaf(T, bg[c], planes[3l + c]) in place, with T the final_T of `ws` -- the img
+ *   workspace of a forward that ran WITHOUT TRASE_VARIANT_FORWARD_ONLY (it begins with the W * H fp32 values of final_T) --
+ *   and bg 3 fp32 on the device.  Planes 3L .. 31 are not touched.  image_u8 ((H,W,3) bytes, needs image (3,H,W) fp32) and
+ *   layers_u8 ((L,H,W,3) bytes), each optional: to8b = trunc(255 * clip(x, 0, 1)) in fp32, a NaN gives 0, of the image and
+ *   of the finished layers -- trase_evaluate_frame's quantiser.  ws == NULL: the planes are final already, only the 8-bit
+ *   frames are written (bg may be NULL then).  No atomics: bitwise reproducible.  W == 0 or H == 0 launches nothing.
+ * Both return TRASE_ERR_INVALID before a device is touched for a NULL pointer, L outside 1 .. TRASE_LAYERS_MAX, a negative
+ * size (finish: W * H >= 2^31), an `out` off a 16-byte boundary, tables, planes or image off a 4-byte boundary, an image_u8
+ * without an image, or (finish) nothing to do; finish returns TRASE_ERR_WORKSPACE for an img workspace that is too small. */
+#define TRASE_LAYERS_MAX 10
+int trase_layers_pack(const float* const* tables, int32_t L, int32_t P, float* out, int32_t device, trase_stream_t stream);
+int trase_layers_finish(float* planes, const TraseRastWorkspace* ws, const float* bg, int32_t L, int32_t W, int32_t H,
+                        const float* image, uint8_t* image_u8, uint8_t* layers_u8, int32_t device, trase_stream_t stream);
+
 /* ---- trajectory view and frame finish (utils/time_utils.py:375-396; gui.py:1154-1191, :1080-1122) ---------------------------
  * Scratch of these entry points is passed as explicit buffers whose sizes are the constants below.
  * trase_fps_sample: farthest-point sampling of the rows of `points` (fp32 (N,3)) with mask == NULL or mask[i] != 0, the

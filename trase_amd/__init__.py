@@ -6,5 +6,6 @@ Only what the hot path needs: ``csrc/`` (HIP kernels + C ABI, include/trase_rast
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, distCUDA2,  # noqa: F401
                          rasterize_gaussians)
+from .layers import render_layers  # noqa: F401
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "distCUDA2"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "distCUDA2", "render_layers"]

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("TRASE_RAST_LIB") or os.path.join(_HERE, "lib", "libtr
 
 c_float_p = C.POINTER(C.c_float)
 FRAME_PLANAR = 1            # TRASE_FRAME_PLANAR: the src_layout of trase_frame_resize for the planes of a frame
+LAYERS_MAX = 10            # TRASE_LAYERS_MAX: colour tables one render_layers pass carries (three feature channels each)
 RIGID_STATE_FLOATS = 16    # TRASE_RIGID_STATE_FLOATS of include/trase_rast.h: floats per row between the rigid fit's two passes
 
 
@@ -346,6 +347,9 @@ SYMBOLS = [
     ("trase_compose_part", C.c_int, [C.POINTER(ComposePart), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("trase_evaluate_frame", C.c_int, [C.POINTER(EvalFrame), C.POINTER(RastWorkspace), C.c_int32, C.c_void_p]),
+    ("trase_layers_pack", C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    ("trase_layers_finish", C.c_int, [C.c_void_p, C.POINTER(RastWorkspace), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     ("trase_fps_sample", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int32, C.c_void_p]),
     ("trase_trajectory_append", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),

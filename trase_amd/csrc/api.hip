@@ -833,4 +833,47 @@ int trase_evaluate_frame(const TraseEvalFrame* f, const TraseRastWorkspace* ws, 
   return launch_evaluate(*f, final_T, (hipStream_t)stream_);
 }
 
+// ---- colour layers through the feature channels (layers.hip) -----------------------------------------------------------------
+static inline bool off_boundary(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+int trase_layers_pack(const float* const* tables, int32_t L, int32_t P, float* out, int32_t device, trase_stream_t stream_) {
+  if (!tables || !out) { set_error("trase_layers_pack: null tables / out"); return TRASE_ERR_INVALID; }
+  if (L < 1 || L > TRASE_LAYERS_MAX) { set_error("trase_layers_pack: need 1 <= L <= %d (got %d)", TRASE_LAYERS_MAX, L); return TRASE_ERR_INVALID; }
+  if (P < 0) { set_error("trase_layers_pack: negative P (%d)", P); return TRASE_ERR_INVALID; }
+  for (int l = 0; l < L; ++l) {
+    if (!tables[l]) { set_error("trase_layers_pack: table %d is null", l); return TRASE_ERR_INVALID; }
+    if (off_boundary(tables[l], 4)) { set_error("trase_layers_pack: table %d is not 4-byte aligned", l); return TRASE_ERR_INVALID; }
+  }
+  if (off_boundary(out, 16)) { set_error("trase_layers_pack: out must be 16-byte aligned"); return TRASE_ERR_INVALID; }
+  if (P == 0) return TRASE_OK;
+  TRASE_CHECK(hipSetDevice(device));
+  return launch_layers_pack(tables, L, P, out, (hipStream_t)stream_);
+}
+
+int trase_layers_finish(float* planes, const TraseRastWorkspace* ws, const float* bg, int32_t L, int32_t W, int32_t H,
+                        const float* image, uint8_t* image_u8, uint8_t* layers_u8, int32_t device, trase_stream_t stream_) {
+  if (!planes) { set_error("trase_layers_finish: null planes"); return TRASE_ERR_INVALID; }
+  if (L < 1 || L > TRASE_LAYERS_MAX) { set_error("trase_layers_finish: need 1 <= L <= %d (got %d)", TRASE_LAYERS_MAX, L); return TRASE_ERR_INVALID; }
+  if (W < 0 || H < 0 || (int64_t)W * H >= ((int64_t)1 << 31)) {
+    set_error("trase_layers_finish: need W, H >= 0, W * H < 2^31 (got W %d, H %d)", W, H);
+    return TRASE_ERR_INVALID;
+  }
+  if (ws && !bg) { set_error("trase_layers_finish: the background step needs bg"); return TRASE_ERR_INVALID; }
+  if (!ws && !image_u8 && !layers_u8) { set_error("trase_layers_finish: no workspace and no 8-bit output: nothing to do"); return TRASE_ERR_INVALID; }
+  if (image_u8 && !image) { set_error("trase_layers_finish: image_u8 needs the image"); return TRASE_ERR_INVALID; }
+  if (off_boundary(planes, 4) || off_boundary(image, 4) || off_boundary(bg, 4)) {
+    set_error("trase_layers_finish: planes, image and bg must be 4-byte aligned"); return TRASE_ERR_INVALID;
+  }
+  const float* final_T = nullptr;
+  if (ws) {
+    // (a frame has no settings record: the one workspace it reads is carved here, as trase_evaluate_frame does)
+    if (!ws->img || ws->img_bytes < img_bytes(W, H)) { set_error("trase_layers_finish: img workspace missing/too small"); return TRASE_ERR_WORKSPACE; }
+    ImgBuf im; img_layout(ws->img, W, H, im);
+    final_T = im.final_T;
+  }
+  if (W == 0 || H == 0) return TRASE_OK;
+  TRASE_CHECK(hipSetDevice(device));
+  return launch_layers_finish(planes, final_T, bg, L, W, H, image, image_u8, layers_u8, (hipStream_t)stream_);
+}
+
 }  // extern "C"

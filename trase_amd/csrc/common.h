@@ -485,6 +485,12 @@ size_t label_sums_layout(void* ws, int N, int D, int S, LabelSumsWs& w);
 int launch_label_sums(const float* X, int N, int D, const int32_t* ids, const int32_t* sel, int S, const LabelSumsWs& w, hipStream_t stream);
 // one pass over a frame: cut-out, mask, 8-bit frames and the frame's score record (evaluate.hip)
 int launch_evaluate(const TraseEvalFrame& f, const float* final_T, hipStream_t stream);
+// colour layers through the feature channels (layers.hip): the feature block of up to TRASE_LAYERS_MAX (P,3) tables, and the
+// background step of the finished planes with their 8-bit frames (final_T == nullptr: the 8-bit frames only)
+constexpr int LAYERS_F = 32;
+int launch_layers_pack(const float* const* tables, int L, int P, float* out, hipStream_t stream);
+int launch_layers_finish(float* planes, const float* final_T, const float* bg, int L, int W, int H, const float* image,
+                         uint8_t* image_u8, uint8_t* layers_u8, hipStream_t stream);
 int launch_split_pair_ids(const LaunchCtx& c, const uint32_t* sorted, int P, uint32_t* ids0, uint32_t* ids1);
 int radix_passes(int bit_lo, int bit_hi, int digit_bits = 8);
 // whether a sort of nb workgroups over `passes` digits takes the short sorts' fused passes (RS_SMALL_NB; TRASE_SORT_SMALL=0, read

@@ -169,8 +169,9 @@ class _RenderRaw(torch.autograd.Function):
         # fwd_only: render() was called under torch.no_grad() -- nobody will differentiate this forward, and the state only a
         # backward reads is not written (TRASE_VARIANT_FORWARD_ONLY).  (Decided by the caller: inside an autograd Function's
         # forward the grad mode is always off.)
-        # keep_img (a dict; trase_amd.evaluate.render_segment): the caller reads the transmittance this forward leaves in its img
-        # workspace, so the store that FORWARD_ONLY skips stays, and the workspace is handed over under "img"
+        # keep_img (a dict; trase_amd.evaluate.render_segment, trase_amd.layers.render_layers): the caller reads the transmittance
+        # this forward leaves in its img workspace, so the store that FORWARD_ONLY skips stays, and the workspace is handed over
+        # under "img"
         if fwd_only and keep_img is None:
             s.variant |= _r_VARIANT_FORWARD_ONLY
 
@@ -441,8 +442,10 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, d_xyz, d_rotation
            scaling_modifier=1.0, override_color=None, mask=None, norm_gaussian_features=True,
            is_smooth_gaussian_features=False, smooth_K=16, _keep_img=None):
     """Same contract as the reference's render() (gaussian_renderer/__init__.py:37-155).  ``_keep_img`` is private to
-    ``trase_amd.evaluate.render_segment``: the fused forward keeps its per-pixel transmittance and hands its img workspace
-    over in that dict; only the rasterizer's four outputs come back, with full-size radii, and nothing synchronises."""
+    ``trase_amd.evaluate.render_segment`` and ``trase_amd.layers.render_layers``: the fused forward keeps its per-pixel
+    transmittance and hands its img workspace over in that dict (``"img"``); only the rasterizer's four outputs and the
+    screen-space dummy come back, with full-size radii, and nothing synchronises.  A ``"gfeat"`` entry the caller puts into the
+    dict, an (N, F) block, is composited in place of the model's Gaussian features, whatever the forward scope."""
     xyz = pc.get_xyz
     # The reference builds `zeros_like(xyz, requires_grad=True) + 0` (gaussian_renderer/__init__.py:48-52): a dummy whose VALUES
     # nobody reads -- the rasterizer returns the screen-space gradient through it and train.py reads `.grad`.  Here: a fresh
@@ -466,6 +469,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, d_xyz, d_rotation
         else:
             gfeat = smoothed_gaussian_features(pc, K=smooth_K, dropout=0.5) if is_smooth_gaussian_features \
                 else pc._gaussian_features
+        if _keep_img is not None and _keep_img.get("gfeat") is not None:
+            gfeat = _keep_img["gfeat"]         # (render_layers: colour tables in the feature channels)
         cov_python = bool(getattr(pipe, "compute_cov3D_python", False))
         # pipe.compute_cov3D_python (gaussian_renderer/__init__.py:93-94): pc.get_covariance(scaling_modifier) is built from the
         # UNDEFORMED scaling and rotation (scene/gaussian_model.py:216-217) -- the kernels' own Sigma = R S S R^T of exp(_scaling) *
@@ -478,7 +483,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, d_xyz, d_rotation
             raster_settings, norm_gaussian_features, override_color, mask, T(d_xyz) if is_6dof else None, sh_py,
             not torch.is_grad_enabled(), _keep_img)
         if _keep_img is not None:
-            return {"render": rendered_image, "radii": radii, "render_gaussian_features": rendered_feats, "depth": depth}
+            return {"render": rendered_image, "viewspace_points": screenspace_points, "radii": radii,
+                    "render_gaussian_features": rendered_feats, "depth": depth}
     else:
         if _keep_img is not None:
             raise ValueError("render_segment: these arguments do not take the fused forward (see trase_amd.renderer._fusable)")
