@@ -387,7 +387,7 @@ static int stage2(const TraseRastSettings* s, int P, int F, const float* feat_ro
     if (rc) return rc;
     return launch_render_fwd(c, *s, in, *out, g, b, k.im, t.pair_gauss, (uint32_t)cap);
   }
-  launch_zero_bytes(b.ranges, sizeof(uint2) * ((size_t)T + 1), stream);
+  if (int zrc = launch_zero_bytes(b.ranges, sizeof(uint2) * ((size_t)T + 1), stream)) return zrc;
   return launch_render_fwd(c, *s, in, *out, g, b, k.im);
 }
 
@@ -411,7 +411,7 @@ static int compose_bwd(const Call& k, const TraseRastSettings* s, const Cotangen
   const BwdBuf& bw = k.bw;
   if ((ct.in.F == 32 || ct.in.F == 0) && !valu_backward(s))
     return launch_render_bwd_hw(k.c, *s, ct.in, k.g, k.b, k.im, ct.g, bw.rows, bw.row_flags, bw.flags_bytes, out_depth);
-  launch_zero_bytes(bw.row_flags, (size_t)k.cap, k.c.stream);
+  if (int zrc = launch_zero_bytes(bw.row_flags, (size_t)k.cap, k.c.stream)) return zrc;
   return launch_render_bwd_gs(k.c, *s, ct.in, k.g, k.b, k.im, ct.g, bw.rows, bw.row_flags, out_depth);
 }
 
@@ -545,16 +545,17 @@ static int backward_impl(const TraseRastSettings* s, const TraseRastInputs* in, 
   const Cotangents ct = scope_cotangents(s, in->P, in->F, in->sh_objs, gr->dL_dimage, gr->dL_dfeats, gr->dL_ddepth);
   float* const d_feats = gr->dL_dfeats ? gr->dL_dsh_objs : nullptr;
   // feature map unused by the loss: the gradient of its rows is zero
-  if (!gr->dL_dfeats && gr->dL_dsh_objs && in->F > 0) launch_zero_bytes(gr->dL_dsh_objs, sizeof(float) * (size_t)in->F * in->P, stream);
-  rc = compose_bwd(k, s, ct, out->depth);
+  if (!gr->dL_dfeats && gr->dL_dsh_objs && in->F > 0) rc = launch_zero_bytes(gr->dL_dsh_objs, sizeof(float) * (size_t)in->F * in->P, stream);
+  if (!rc) rc = compose_bwd(k, s, ct, out->depth);
   if (rc) return rc;
   // a tile-row strip: the forward compacted the ids of the Gaussians with a pair in the strip in front of the depth order and
   // sorted only those -- the ranks behind them hold nothing, so the reduction walks the live ranks only; the rows it does not
   // write -- Gaussians without a pair: zero gradient -- start at zero.
   const int live_only = strip_mode(s) ? 1 : 0;
   if (live_only) {
-    launch_zero_bytes(k.bw.acc, sizeof(float) * BWD_ACC * (size_t)in->P, stream);
-    if (d_feats) launch_zero_bytes(d_feats, sizeof(float) * (size_t)ct.in.F * in->P, stream);
+    rc = launch_zero_bytes(k.bw.acc, sizeof(float) * BWD_ACC * (size_t)in->P, stream);
+    if (!rc && d_feats) rc = launch_zero_bytes(d_feats, sizeof(float) * (size_t)ct.in.F * in->P, stream);
+    if (rc) return rc;
   }
   rc = launch_reduce_rows(k.c, k.g, k.pre, in->P, ct.in.F, k.bw.rows, k.bw.row_flags, k.bw.acc, d_feats, nullptr, 0, -1, -1, live_only);
   if (rc) return rc;
@@ -615,7 +616,7 @@ static int forward_raw_pair_impl(const TraseRastSettings* const s[2], const Tras
   PairSortWs pw; pair_ws_layout(pair_ws, P, pw);
   const SortBufs& cs = pw.sort;
   uint32_t* const n_word = pw.n_word;
-  launch_fill_u32(n_word, (uint32_t)n, stream);
+  if (int frc = launch_fill_u32(n_word, (uint32_t)n, stream)) return frc;
   for (int v = 0; v < 2; ++v) {
     const int rc = launch_preprocess_fwd_raw(k[v].c, *s[v], *raw[v], out[v]->radii, k[v].g, cs.keys[0] + (size_t)v * P, false,
                                              v ? 0x80000000u : 0u, v ? 0xffffffffu : 0x7fffffffu);
@@ -626,7 +627,8 @@ static int forward_raw_pair_impl(const TraseRastSettings* const s[2], const Tras
   int rc = radix_sort_pairs(c0, cs, n_word, (uint32_t)n, 0, 32, true, &idx, 8, 0);      // ids generated on the fly: 0 .. 2 P - 1
   if (rc) return rc;
   if (idx != 0) { set_error("internal: pair depth sort ended in buffer %d", idx); return TRASE_ERR_INVALID; }
-  launch_split_pair_ids(c0, cs.vals[0], P, k[0].pre.sort.vals[0], k[1].pre.sort.vals[0]);
+  rc = launch_split_pair_ids(c0, cs.vals[0], P, k[0].pre.sort.vals[0], k[1].pre.sort.vals[0]);
+  if (rc) return rc;
   for (int v = 0; v < 2; ++v) {
     rc = launch_scan_tiles(k[v].c, k[v].g, k[v].pre.sort.vals[0], P, k[v].pre, 0xffffffffu, out[v]->radii, (s[v]->image_width + TILE - 1) / TILE,
                            (s[v]->image_height + TILE - 1) / TILE, list_pack_bits(s[v], P));
@@ -702,8 +704,8 @@ static int backward_raw_phases(const TraseRastSettings* s, const TraseRastRawInp
   const bool sparse = strip_mode(s) && !ranged && (s->variant & TRASE_VARIANT_SPARSE_STRIP_GRADS) != 0;
   if (phase & 1) {
     if (!gr->dL_dfeats && gr->dL_dgaussian_features && raw->F > 0 && !sparse)
-      launch_zero_bytes(gr->dL_dgaussian_features, sizeof(float) * (size_t)raw->F * raw->P, stream);
-    rc = compose_bwd(k, s, ct, out->depth);
+      rc = launch_zero_bytes(gr->dL_dgaussian_features, sizeof(float) * (size_t)raw->F * raw->P, stream);
+    if (!rc) rc = compose_bwd(k, s, ct, out->depth);
     if (rc) return rc;
   }
   if (phase & 2) {

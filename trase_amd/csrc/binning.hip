@@ -341,6 +341,7 @@ int launch_zero_bytes(void* p, size_t bytes, hipStream_t stream) {
   const size_t n16 = bytes >> 4;
   const unsigned blocks = (unsigned)(n16 / 256 / 4 + 1 < 4096 ? n16 / 256 / 4 + 1 : 4096);
   hipLaunchKernelGGL(zero_bytes_kernel, dim3(blocks), dim3(256), 0, stream, (uint8_t*)p, bytes);
+  TRASE_POST_LAUNCH("zero_bytes", stream, 0);            // the check alone: a scope would add a key to the profiler report
   return TRASE_OK;
 }
 
@@ -348,6 +349,7 @@ int launch_zero_bytes(void* p, size_t bytes, hipStream_t stream) {
 __global__ void fill_u32_kernel(uint32_t* p, uint32_t v) { if (threadIdx.x == 0 && blockIdx.x == 0) *p = v; }
 int launch_fill_u32(uint32_t* p, uint32_t v, hipStream_t stream) {
   hipLaunchKernelGGL(fill_u32_kernel, dim3(1), dim3(64), 0, stream, p, v);
+  TRASE_POST_LAUNCH("fill_u32", stream, 0);              // the check alone: a scope would add a key to the profiler report
   return TRASE_OK;
 }
 // the sorted (view, depth) order of 2 P keys back into the two views' own id lists: entries [0, P) are view 0's Gaussians in
@@ -360,8 +362,7 @@ __global__ __launch_bounds__(256) void split_pair_ids_kernel(const uint32_t* __r
   if (i < P) ids0[i] = v; else ids1[i - P] = v - (uint32_t)P;
 }
 int launch_split_pair_ids(const LaunchCtx& c, const uint32_t* sorted, int P, uint32_t* ids0, uint32_t* ids1) {
-  ProfScope ps("split_pair_ids", c.stream);
-  hipLaunchKernelGGL(split_pair_ids_kernel, dim3((2 * P + 255) / 256), dim3(256), 0, c.stream, sorted, P, ids0, ids1);
+  TRASE_LAUNCH("split_pair_ids", c.stream, c.debug, split_pair_ids_kernel, dim3((2 * P + 255) / 256), dim3(256), 0, sorted, P, ids0, ids1);
   return TRASE_OK;
 }
 
@@ -393,23 +394,17 @@ static int radix_sort_pairs_t(const LaunchCtx& c, const SortBufs& t, const uint3
       const int nbits_n = (bit_hi - shift_n) < DB ? (bit_hi - shift_n) : DB;
       uint32_t* hist_p = t.hist + hw * p;
       uint32_t* hist_n = (p + 1 < passes) ? t.hist + hw * (p + 1) : nullptr;
-      if (p == 0) {
-        ProfScope ps("radix_hist", c.stream);
-        hipLaunchKernelGGL((radix_hist_kernel<DB, true>), dim3(nb), dim3(RS_THREADS), 0, c.stream, t.keys[cur], n_ptr, n_cap, shift, mask, hist_p,
-                           t.digit_total, t.nb_max, flag_key, flag_word, t.hist + hw, (uint32_t)(hw * (passes - 1)));
-      }
-      TRASE_POST_LAUNCH("radix_hist", c.stream, c.debug);
-      {
-        ProfScope ps("radix_scatter", c.stream);
-        const uint32_t mask_n = hist_n ? ((1u << nbits_n) - 1u) : 0u;
+      if (p == 0)
+        TRASE_LAUNCH("radix_hist", c.stream, c.debug, (radix_hist_kernel<DB, true>), dim3(nb), dim3(RS_THREADS), 0, t.keys[cur], n_ptr, n_cap, shift, mask, hist_p,
+                     t.digit_total, t.nb_max, flag_key, flag_word, t.hist + hw, (uint32_t)(hw * (passes - 1)));
+      const uint32_t mask_n = hist_n ? ((1u << nbits_n) - 1u) : 0u;
+      TRASE_LAUNCHES("radix_scatter", c.stream, c.debug,
         if (vals_are_iota && p == 0)
           hipLaunchKernelGGL((radix_scatter_kernel<true, DB, true>), dim3(nb), dim3(RS_THREADS), 0, c.stream, t.keys[cur], t.vals[cur],
                              t.keys[cur ^ 1], t.vals[cur ^ 1], n_ptr, n_cap, shift, mask, hist_p, t.digit_total, t.nb_max, hist_n, shift_n, mask_n);
         else
           hipLaunchKernelGGL((radix_scatter_kernel<false, DB, true>), dim3(nb), dim3(RS_THREADS), 0, c.stream, t.keys[cur], t.vals[cur],
-                             t.keys[cur ^ 1], t.vals[cur ^ 1], n_ptr, n_cap, shift, mask, hist_p, t.digit_total, t.nb_max, hist_n, shift_n, mask_n);
-      }
-      TRASE_POST_LAUNCH("radix_scatter", c.stream, c.debug);
+                             t.keys[cur ^ 1], t.vals[cur ^ 1], n_ptr, n_cap, shift, mask, hist_p, t.digit_total, t.nb_max, hist_n, shift_n, mask_n));
       cur ^= 1;
     }
     *out_idx = cur;
@@ -421,27 +416,16 @@ static int radix_sort_pairs_t(const LaunchCtx& c, const SortBufs& t, const uint3
     const uint32_t mask = (1u << nbits) - 1u;
     uint32_t* dt = t.digit_total + ND * p;
     uint32_t* vout = t.vals[cur ^ 1];
-    {
-      ProfScope ps("radix_hist", c.stream);
-      hipLaunchKernelGGL(radix_hist_kernel<DB>, dim3(nb), dim3(RS_THREADS), 0, c.stream, t.keys[cur], n_ptr, n_cap, shift,
-                         mask, t.hist, dt, t.nb_max, flag_key, p == 0 ? flag_word : (uint32_t*)nullptr);
-    }
-    TRASE_POST_LAUNCH("radix_hist", c.stream, c.debug);
-    {
-      ProfScope ps("radix_scan", c.stream);
-      hipLaunchKernelGGL(radix_scan_kernel, dim3(ND), dim3(256), 0, c.stream, n_ptr, n_cap, t.hist, dt, t.nb_max);
-    }
-    TRASE_POST_LAUNCH("radix_scan", c.stream, c.debug);
-    {
-      ProfScope ps("radix_scatter", c.stream);
+    TRASE_LAUNCH("radix_hist", c.stream, c.debug, radix_hist_kernel<DB>, dim3(nb), dim3(RS_THREADS), 0, t.keys[cur], n_ptr, n_cap, shift,
+                 mask, t.hist, dt, t.nb_max, flag_key, p == 0 ? flag_word : (uint32_t*)nullptr);
+    TRASE_LAUNCH("radix_scan", c.stream, c.debug, radix_scan_kernel, dim3(ND), dim3(256), 0, n_ptr, n_cap, t.hist, dt, t.nb_max);
+    TRASE_LAUNCHES("radix_scatter", c.stream, c.debug,
       if (vals_are_iota && p == 0)
         hipLaunchKernelGGL((radix_scatter_kernel<true, DB>), dim3(nb), dim3(RS_THREADS), 0, c.stream, t.keys[cur],
                            t.vals[cur], t.keys[cur ^ 1], vout, n_ptr, n_cap, shift, mask, t.hist, dt, t.nb_max);
       else
         hipLaunchKernelGGL((radix_scatter_kernel<false, DB>), dim3(nb), dim3(RS_THREADS), 0, c.stream, t.keys[cur],
-                           t.vals[cur], t.keys[cur ^ 1], vout, n_ptr, n_cap, shift, mask, t.hist, dt, t.nb_max);
-    }
-    TRASE_POST_LAUNCH("radix_scatter", c.stream, c.debug);
+                           t.vals[cur], t.keys[cur ^ 1], vout, n_ptr, n_cap, shift, mask, t.hist, dt, t.nb_max));
     cur ^= 1;
   }
   *out_idx = cur;
@@ -541,13 +525,10 @@ __global__ __launch_bounds__(SC_THREADS) void compact_scatter_kernel(const uint3
 int launch_compact_live(const LaunchCtx& c, const GeomBuf& g, int P, const PreBuf& t, const uint32_t* keys_raw,
                         uint32_t* keys_out, uint32_t* ids_out) {
   const int nblocks = (P + SC_TILE - 1) / SC_TILE;
-  {
-    ProfScope ps("compact_live", c.stream);
+  TRASE_LAUNCHES("compact_live", c.stream, c.debug,
     hipLaunchKernelGGL(compact_count_kernel, dim3(nblocks), dim3(SC_THREADS), 0, c.stream, g.tiles, P, t.block_sums);
     hipLaunchKernelGGL(compact_scatter_kernel, dim3(nblocks), dim3(SC_THREADS), 0, c.stream, g.tiles, keys_raw, P, t.block_sums,
-                       nblocks, keys_out, ids_out, t.live_ids, g.hdr);
-  }
-  TRASE_POST_LAUNCH("compact_live", c.stream, c.debug);
+                       nblocks, keys_out, ids_out, t.live_ids, g.hdr));
   return TRASE_OK;
 }
 
@@ -678,14 +659,11 @@ __global__ __launch_bounds__(SC_THREADS) void scan_sums_kernel(uint32_t* __restr
 int launch_scan_tiles(const LaunchCtx& c, const GeomBuf& g, const uint32_t* sorted_ids, int P, const PreBuf& t, uint32_t cap,
                       const int32_t* radii, int gx, int gy, int pack_bits) {
   const int nblocks = (P + SC_TILE - 1) / SC_TILE;
-  {
-    ProfScope ps("scan_tiles", c.stream);
+  TRASE_LAUNCHES("scan_tiles", c.stream, c.debug,
     hipLaunchKernelGGL(scan_partial_kernel, dim3(nblocks), dim3(SC_THREADS), 0, c.stream, g.tiles, sorted_ids, P,
                        t.offsets, t.block_sums, radii, g.xy, gx, gy, t.block_R, t.block_max, g.hdr + (HDR_WORDS - 1));
     hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SC_THREADS), 0, c.stream, t.block_sums, nblocks, g.hdr, cap, t.block_R,
-                       t.block_max, pack_bits);
-  }
-  TRASE_POST_LAUNCH("scan_tiles", c.stream, c.debug);
+                       t.block_max, pack_bits));
   return TRASE_OK;
 }
 
@@ -834,14 +812,10 @@ int launch_emit_pairs(const LaunchCtx& c, const TraseRastSettings& s, const Geom
   const int gx = (s.image_width + TILE - 1) / TILE, gy = (s.image_height + TILE - 1) / TILE;
   int sy_lo, sy_hi;
   strip_subtile_rows(s, sy_lo, sy_hi);
-  {
-    ProfScope ps("emit_pairs", c.stream);
-    hipLaunchKernelGGL(emit_pairs_kernel, dim3((4 * P + 255) / 256), dim3(256), 0, c.stream, sorted_ids, P, t.offsets, g.xy,
-                       g.conic_o, radii, g.tiles, s.image_width, s.image_height, gx, gy, keys, pair_gauss, cap, g.hdr,
-                       (uint32_t)(((s.image_width + SUB - 1) / SUB) * ((s.image_height + SUB - 1) / SUB)), ranges_to_clear,
-                       sy_lo, sy_hi, vals, (uint32_t*)g.geo, t.block_sums, t.id_end);
-  }
-  TRASE_POST_LAUNCH("emit_pairs", c.stream, c.debug);
+  TRASE_LAUNCH("emit_pairs", c.stream, c.debug, emit_pairs_kernel, dim3((4 * P + 255) / 256), dim3(256), 0, sorted_ids, P, t.offsets, g.xy,
+               g.conic_o, radii, g.tiles, s.image_width, s.image_height, gx, gy, keys, pair_gauss, cap, g.hdr,
+               (uint32_t)(((s.image_width + SUB - 1) / SUB) * ((s.image_height + SUB - 1) / SUB)), ranges_to_clear,
+               sy_lo, sy_hi, vals, (uint32_t*)g.geo, t.block_sums, t.id_end);
   return TRASE_OK;
 }
 
@@ -976,9 +950,7 @@ int launch_reduce_rows(const LaunchCtx& c, const GeomBuf& g, const PreBuf& pre, 
   // (S5: 156 k workgroups, 0.46 -> 0.43 ms with 16 k striding ones; no effect at 300 k)
   const int grid_cap = live_only ? 8192 : 16384;
   const int blocks = (last - first + GPB - 1) / GPB; // 4 waves x 4 (GW = 16) or 5 (GW = 12) Gaussians per block
-  {
-    ProfScope ps("reduce_rows", c.stream);
-#define TRASE_RR(ROW)                                                                                                         \
+#define TRASE_RR(ROW)                                                                                                        \
   do {                                                                                                                        \
     if (by_id)                                                                                                                \
       hipLaunchKernelGGL((reduce_rows_kernel<ROW, true, GW, false>), dim3(blocks), dim3(256), 0, c.stream, pre.sort.vals[0], pre.id_end, \
@@ -990,15 +962,14 @@ int launch_reduce_rows(const LaunchCtx& c, const GeomBuf& g, const PreBuf& pre, 
       hipLaunchKernelGGL((reduce_rows_kernel<ROW, false, GW, false>), dim3(blocks), dim3(256), 0, c.stream, pre.sort.vals[0],            \
                          pre.offsets, g.tiles, first, last, g.hdr, rows, row_flags, acc, d_feats, raw_feats, norm_features, pre.block_sums, live_only);  \
   } while (0)
+  TRASE_LAUNCHES("reduce_rows", c.stream, c.debug,
     switch (F) {
       case 0: TRASE_RR(12); break;
       case 16: TRASE_RR(28); break;
       case 32: TRASE_RR(44); break;
       default: set_error("reduce_rows: feature width %d not compiled in", F); return TRASE_ERR_UNSUPPORTED;
-    }
+    });
 #undef TRASE_RR
-  }
-  TRASE_POST_LAUNCH("reduce_rows", c.stream, c.debug);
   return TRASE_OK;
 }
 
@@ -1052,18 +1023,15 @@ __global__ __launch_bounds__(256) void tile_ranges4_kernel(const uint32_t* __res
 
 int launch_tile_ranges(const LaunchCtx& c, const uint32_t* keys, const uint32_t* n_ptr, uint32_t cap, uint2* ranges, int T,
                        uint32_t* dbg, bool clear) {
-  if (clear) launch_zero_bytes(ranges, sizeof(uint2) * (size_t)T, c.stream);
+  if (clear) if (int rc = launch_zero_bytes(ranges, sizeof(uint2) * (size_t)T, c.stream)) return rc;
   int blocks = (int)((cap + 1023) / 1024);
   if (blocks < 1) blocks = 1;
-  {
-    ProfScope ps("tile_ranges", c.stream);
+  TRASE_LAUNCHES("tile_ranges", c.stream, c.debug,
     if ((reinterpret_cast<uintptr_t>(keys) & 15) == 0)
       hipLaunchKernelGGL(tile_ranges4_kernel, dim3(blocks), dim3(256), 0, c.stream, keys, n_ptr, cap, ranges, (uint32_t)T, dbg);
     else
       hipLaunchKernelGGL(tile_ranges_kernel, dim3(blocks < 4096 ? blocks : 4096), dim3(256), 0, c.stream, keys, n_ptr, cap,
-                         ranges, (uint32_t)T, dbg);
-  }
-  TRASE_POST_LAUNCH("tile_ranges", c.stream, c.debug);
+                         ranges, (uint32_t)T, dbg));
   return TRASE_OK;
 }
 

@@ -264,6 +264,16 @@ bool prof_on();
     }                                                                                   \
   } while (0)
 
+// The launch convention, written once: the statements run inside the profiler scope `scope`, the scope closes, then the launch
+// check runs under the literal `check` (and returns the error code from the enclosing function).  TRASE_LAUNCHES names both
+// alike and takes any statements: an if / else between instantiations, several launches that share one scope, a local dispatch
+// macro.  TRASE_LAUNCH is the one unconditional launch.  (No preprocessor directive inside the arguments.)
+#define TRASE_LAUNCHES_AS(scope, check, stream, debug, ...) \
+  do { { ::trase::ProfScope _ps(scope, stream); __VA_ARGS__; } TRASE_POST_LAUNCH(check, stream, debug); } while (0)
+#define TRASE_LAUNCHES(name, stream, debug, ...) TRASE_LAUNCHES_AS(name, name, stream, debug, __VA_ARGS__)
+#define TRASE_LAUNCH(name, stream, debug, kernel, grid, block, lds, ...) \
+  TRASE_LAUNCHES(name, stream, debug, hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__))
+
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 // the buffer contract of every entry point that reads or writes a packed mask stream (maskbits.hip, the *_bits head): a 16-byte

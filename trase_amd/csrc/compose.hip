@@ -163,11 +163,7 @@ int trase_compose_part(const TraseComposePart* part, int64_t row_offset, int64_t
   for (int k = 0; k < 9; ++k) a.edit.R[k] = p.R[k];
   for (int k = 0; k < 4; ++k) a.edit.q[k] = p.q_edit[k];
   for (int k = 0; k < 3; ++k) a.edit.t[k] = p.offset[k];
-  {
-    ProfScope ps("compose_part", stream);
-    hipLaunchKernelGGL(compose_part_kernel, dim3((p.m + CMP_THREADS - 1) / CMP_THREADS), dim3(CMP_THREADS), 0, stream, a);
-  }
-  TRASE_POST_LAUNCH("compose_part", stream, 0);
+  TRASE_LAUNCH("compose_part", stream, 0, compose_part_kernel, dim3((p.m + CMP_THREADS - 1) / CMP_THREADS), dim3(CMP_THREADS), 0, a);
   return TRASE_OK;
 }
 

@@ -136,16 +136,13 @@ int trase_contrastive_forward(const float* C, const float* C_F, const float* wei
   if (!ws || ws_bytes < contrastive_layout(ws, S, w)) { set_error("trase_contrastive_forward: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  launch_zero_bytes(w.col, sizeof(int) * (size_t)S, stream);
+  if (int rc = launch_zero_bytes(w.col, sizeof(int) * (size_t)S, stream)) return rc;
   const dim3 grid((S + 255) / 256, (S + CT_ROWS - 1) / CT_ROWS);
-  {
-    ProfScope ps("contrastive_fwd", stream);
+  TRASE_LAUNCHES("contrastive_fwd", stream, 0,
     if ((kind >> 1) != 2)
       hipLaunchKernelGGL(contrastive_flags_kernel, grid, dim3(256), 0, stream, C, C_F, S, threshold, kind, w.col);
     hipLaunchKernelGGL(contrastive_sum_kernel, grid, dim3(256), 0, stream, C, C_F, weights, S, threshold, kind, w.col, w.partial);
-    hipLaunchKernelGGL(contrastive_final_kernel, dim3(1), dim3(256), 0, stream, w.partial, w.nblocks, w.col, S, kind, out2);
-  }
-  TRASE_POST_LAUNCH("contrastive_fwd", stream, 0);
+    hipLaunchKernelGGL(contrastive_final_kernel, dim3(1), dim3(256), 0, stream, w.partial, w.nblocks, w.col, S, kind, out2));
   return TRASE_OK;
 }
 
@@ -158,13 +155,8 @@ int trase_contrastive_backward(const float* C, const float* C_F, const float* we
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const dim3 grid((S + 255) / 256, (S + CT_ROWS - 1) / CT_ROWS);
-  {
-    ProfScope ps("contrastive_bwd", stream);
-    hipLaunchKernelGGL(contrastive_bwd_kernel, grid, dim3(256), 0, stream, C, C_F, weights, S, threshold, kind, w.col, out2,
-                       g,
-                       dL_dC_F);
-  }
-  TRASE_POST_LAUNCH("contrastive_bwd", stream, 0);
+  TRASE_LAUNCH("contrastive_bwd", stream, 0, contrastive_bwd_kernel, grid, dim3(256), 0, C, C_F, weights, S, threshold, kind, w.col, out2,
+               g, dL_dC_F);
   return TRASE_OK;
 }
 

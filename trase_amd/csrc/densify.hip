@@ -243,12 +243,8 @@ int trase_densify_stats_guarded(const float* viewspace_grad, const int32_t* radi
   if (P == 0) return TRASE_OK;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("densify_stats", stream);
-    hipLaunchKernelGGL(densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, viewspace_grad, radii,
-                       xyz_gradient_accum, denom, max_radii2D, P, (const uint32_t*)guard);
-  }
-  TRASE_POST_LAUNCH("densify_stats", stream, 0);
+  TRASE_LAUNCH("densify_stats", stream, 0, densify_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, viewspace_grad, radii,
+               xyz_gradient_accum, denom, max_radii2D, P, (const uint32_t*)guard);
   return TRASE_OK;
 }
 
@@ -271,15 +267,12 @@ int trase_densify_plan(const float* xyz_gradient_accum, const float* denom, cons
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const int nblk = (P + 255) / 256;
-  launch_zero_bytes(w.totals, sizeof(uint32_t) * 8, stream);
-  {
-    ProfScope ps("densify_plan", stream);
+  if (int rc = launch_zero_bytes(w.totals, sizeof(uint32_t) * 8, stream)) return rc;
+  TRASE_LAUNCHES("densify_plan", stream, 0,
     hipLaunchKernelGGL(densify_plan_kernel, dim3(nblk), dim3(256), 0, stream, xyz_gradient_accum, denom, scaling, opacity, P,
                        grad_threshold, dense_extent, min_opacity, use_screen_size, big_extent, w.flags, w.blk, w.totals);
     hipLaunchKernelGGL(densify_scan_kernel, dim3(1), dim3(256), 0, stream, w.blk, nblk, w.totals, counts);
-    hipLaunchKernelGGL(densify_map_kernel, dim3(nblk), dim3(256), 0, stream, w.flags, w.blk, w.totals, P, w.map, w.aux);
-  }
-  TRASE_POST_LAUNCH("densify_plan", stream, 0);
+    hipLaunchKernelGGL(densify_map_kernel, dim3(nblk), dim3(256), 0, stream, w.flags, w.blk, w.totals, P, w.map, w.aux));
   return TRASE_OK;
 }
 
@@ -308,15 +301,12 @@ int trase_densify_apply(int32_t count, const void* const* src, void* const* dst,
   t.count = k; t.first_block[k] = blocks;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("densify_apply", stream);
+  TRASE_LAUNCHES("densify_apply", stream, 0,
     if (k > 0) hipLaunchKernelGGL(densify_gather_kernel, dim3(blocks), dim3(256), 0, stream, t, w.map, (long long)new_P);
     // the children are at most new_P rows; the kernel reads their exact range from the totals
     if (normal_samples)
       hipLaunchKernelGGL(densify_children_kernel, dim3((new_P + 255) / 256), dim3(256), 0, stream, w.map, w.aux, w.totals, xyz,
-                         scaling, rotation, normal_samples, new_xyz, new_scaling);
-  }
-  TRASE_POST_LAUNCH("densify_apply", stream, 0);
+                         scaling, rotation, normal_samples, new_xyz, new_scaling));
   return TRASE_OK;
 }
 

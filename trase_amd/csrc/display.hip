@@ -261,26 +261,12 @@ int trase_splat_points(const float* points, int32_t N, const uint8_t* mask, cons
   SplatProj P;
   for (int c = 0; c < 3; ++c)
     for (int r = 0; r < 4; ++r) P.m[4 * c + r] = full_proj[4 * r + (c == 2 ? 3 : c)];
-  {
-    ProfScope ps("splat_fill", stream);
-    hipLaunchKernelGGL(splat_fill_kernel, dim3((HW + 255) / 256), dim3(256), 0, stream, winner, HW);
-  }
-  TRASE_POST_LAUNCH("splat_fill", stream, 0);
-  if (N > 0) {
-    {
-      ProfScope ps("splat_project", stream);
-      hipLaunchKernelGGL(splat_project_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, points, N, mask, P, W, H, winner);
-    }
-    TRASE_POST_LAUNCH("splat_project", stream, 0);
-  }
-  if (L > 0 || index_out) {
-    {
-      ProfScope ps("splat_resolve", stream);
-      hipLaunchKernelGGL(splat_resolve_kernel, dim3(((HW + 3) / 4 + 255) / 256), dim3(256), 0, stream, winner, HW, L, S,
-                         white_background ? 0.f : 1.f, white_background ? 1.f : 0.f, index_out);
-    }
-    TRASE_POST_LAUNCH("splat_resolve", stream, 0);
-  }
+  TRASE_LAUNCH("splat_fill", stream, 0, splat_fill_kernel, dim3((HW + 255) / 256), dim3(256), 0, winner, HW);
+  if (N > 0)
+    TRASE_LAUNCH("splat_project", stream, 0, splat_project_kernel, dim3((N + 255) / 256), dim3(256), 0, points, N, mask, P, W, H, winner);
+  if (L > 0 || index_out)
+    TRASE_LAUNCH("splat_resolve", stream, 0, splat_resolve_kernel, dim3(((HW + 3) / 4 + 255) / 256), dim3(256), 0, winner, HW, L, S,
+                 white_background ? 0.f : 1.f, white_background ? 1.f : 0.f, index_out);
   return TRASE_OK;
 }
 
@@ -314,27 +300,11 @@ int trase_feature_gram(const float* X, int32_t N, int32_t D, float* gram_mean_ou
     else if (dp == 32) hipLaunchKernelGGL((KERNEL<32>), dim3(G), dim3(DISP_THREADS), 0, stream, __VA_ARGS__);       \
     else hipLaunchKernelGGL((KERNEL<64>), dim3(G), dim3(DISP_THREADS), 0, stream, __VA_ARGS__);                     \
   } while (0)
-  {
-    ProfScope ps("feature_colsum", stream);
-    TRASE_DISP_DP(disp_colsum_kernel, X, N, D, chunk, slabs);
-  }
-  TRASE_POST_LAUNCH("feature_colsum", stream, 0);
-  {
-    ProfScope ps("feature_mean", stream);
-    hipLaunchKernelGGL(disp_reduce_kernel, dim3((D + 255) / 256), dim3(256), 0, stream, slabs, G, D, 1.0 / (double)N, mean);
-  }
-  TRASE_POST_LAUNCH("feature_mean", stream, 0);
-  {
-    ProfScope ps("feature_gram", stream);
-    TRASE_DISP_DP(disp_gram_kernel, X, N, D, chunk, mean, slabs);
-  }
-  TRASE_POST_LAUNCH("feature_gram", stream, 0);
+  TRASE_LAUNCHES("feature_colsum", stream, 0, TRASE_DISP_DP(disp_colsum_kernel, X, N, D, chunk, slabs));
+  TRASE_LAUNCH("feature_mean", stream, 0, disp_reduce_kernel, dim3((D + 255) / 256), dim3(256), 0, slabs, G, D, 1.0 / (double)N, mean);
+  TRASE_LAUNCHES("feature_gram", stream, 0, TRASE_DISP_DP(disp_gram_kernel, X, N, D, chunk, mean, slabs));
 #undef TRASE_DISP_DP
-  {
-    ProfScope ps("feature_gram_reduce", stream);
-    hipLaunchKernelGGL(disp_reduce_kernel, dim3((D * D + 255) / 256), dim3(256), 0, stream, slabs, G, D * D, 1.0, gram);
-  }
-  TRASE_POST_LAUNCH("feature_gram_reduce", stream, 0);
+  TRASE_LAUNCH("feature_gram_reduce", stream, 0, disp_reduce_kernel, dim3((D * D + 255) / 256), dim3(256), 0, slabs, G, D * D, 1.0, gram);
   return TRASE_OK;
 }
 
@@ -347,22 +317,10 @@ int trase_feature_project(const float* X, int32_t N, int32_t D, const float* axe
   if (!X || !axes || !mean || !colors_out || !minmax) { set_error("trase_feature_project: null pointer"); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("feature_minmax_init", stream);
-    hipLaunchKernelGGL(disp_minmax_init_kernel, dim3(1), dim3(1), 0, stream, minmax);
-  }
-  TRASE_POST_LAUNCH("feature_minmax_init", stream, 0);
-  {
-    ProfScope ps("feature_project", stream);
-    hipLaunchKernelGGL(disp_project_kernel, dim3((N + DISP_THREADS - 1) / DISP_THREADS), dim3(DISP_THREADS), 0, stream, X, N, D,
-                       axes, mean, colors_out, minmax);
-  }
-  TRASE_POST_LAUNCH("feature_project", stream, 0);
-  {
-    ProfScope ps("feature_normalise", stream);
-    hipLaunchKernelGGL(disp_normalise_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, stream, colors_out, 3 * N, minmax);
-  }
-  TRASE_POST_LAUNCH("feature_normalise", stream, 0);
+  TRASE_LAUNCH("feature_minmax_init", stream, 0, disp_minmax_init_kernel, dim3(1), dim3(1), 0, minmax);
+  TRASE_LAUNCH("feature_project", stream, 0, disp_project_kernel, dim3((N + DISP_THREADS - 1) / DISP_THREADS), dim3(DISP_THREADS), 0, X, N, D,
+               axes, mean, colors_out, minmax);
+  TRASE_LAUNCH("feature_normalise", stream, 0, disp_normalise_kernel, dim3((3 * N + 255) / 256), dim3(256), 0, colors_out, 3 * N, minmax);
   return TRASE_OK;
 }
 

@@ -217,11 +217,7 @@ int launch_evaluate(const TraseEvalFrame& f, const float* final_T, hipStream_t s
   const int items = ((f.W + 3) / 4) * f.H;
   int blocks = (items + EVAL_THREADS - 1) / EVAL_THREADS;
   if (blocks > EVAL_MAX_BLOCKS) blocks = EVAL_MAX_BLOCKS;
-  {
-    ProfScope ps("evaluate", stream);
-    hipLaunchKernelGGL(evaluate_kernel, dim3(blocks), dim3(EVAL_THREADS), 0, stream, a);
-  }
-  TRASE_POST_LAUNCH("evaluate", stream, 0);
+  TRASE_LAUNCH("evaluate", stream, 0, evaluate_kernel, dim3(blocks), dim3(EVAL_THREADS), 0, a);
   return TRASE_OK;
 }
 

@@ -354,13 +354,10 @@ int trase_frame_pack(const uint8_t* hwc, int32_t H, int32_t W, int32_t channels,
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const dim3 grid((unsigned)(((long long)H * (pitch / 4) + 255) / 256));
-  {
-    ProfScope ps("frame_pack", stream);
+  TRASE_LAUNCHES("frame_pack", stream, 0,
     if (channels == 3) hipLaunchKernelGGL((frame_pack_kernel<3, false>), grid, dim3(256), 0, stream, hwc, H, W, pitch, bg, planes);
     else if (!background) hipLaunchKernelGGL((frame_pack_kernel<4, false>), grid, dim3(256), 0, stream, hwc, H, W, pitch, bg, planes);
-    else hipLaunchKernelGGL((frame_pack_kernel<4, true>), grid, dim3(256), 0, stream, hwc, H, W, pitch, bg, planes);
-  }
-  TRASE_POST_LAUNCH("frame_pack", stream, 0);
+    else hipLaunchKernelGGL((frame_pack_kernel<4, true>), grid, dim3(256), 0, stream, hwc, H, W, pitch, bg, planes));
   return TRASE_OK;
 }
 
@@ -405,14 +402,11 @@ int trase_frame_resize(const uint8_t* src, int32_t src_H, int32_t src_W, int32_t
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const dim3 grid((unsigned)tiles);
-  {
-    ProfScope ps("frame_resize", stream);
+  TRASE_LAUNCHES("frame_resize", stream, 0,
     if (src_layout == 3) hipLaunchKernelGGL((frame_resize_kernel<SrcRgb>), grid, dim3(256), lds, stream, a);
     else if (src_layout == TRASE_FRAME_PLANAR) hipLaunchKernelGGL((frame_resize_kernel<SrcPlanes>), grid, dim3(256), lds, stream, a);
     else if (!background) hipLaunchKernelGGL((frame_resize_kernel<SrcRgba<false>>), grid, dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL((frame_resize_kernel<SrcRgba<true>>), grid, dim3(256), lds, stream, a);
-  }
-  TRASE_POST_LAUNCH("frame_resize", stream, 0);
+    else hipLaunchKernelGGL((frame_resize_kernel<SrcRgba<true>>), grid, dim3(256), lds, stream, a));
   return TRASE_OK;
 }
 
@@ -426,7 +420,7 @@ int trase_selftest_resize_tables(int32_t in, int32_t out, int32_t* coeffs, int32
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   hipLaunchKernelGGL(resize_tables_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0, stream, in, out, coeffs, bounds);
-  TRASE_POST_LAUNCH("resize_tables", stream, 0);
+  TRASE_POST_LAUNCH("resize_tables", stream, 0);         // the check alone: a test entry point, never a key of the profiler report
   return TRASE_OK;
 }
 
@@ -436,12 +430,8 @@ int trase_frame_unpack(const uint8_t* planes, int32_t H, int32_t W, int32_t pitc
   if (int rc = frame_ok(who, planes, H, W, pitch)) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("frame_unpack", stream);
-    hipLaunchKernelGGL(frame_unpack_kernel, dim3((unsigned)((3ll * H * ((W + 3) / 4) + 255) / 256)), dim3(256), 0, stream, planes, H, W, pitch,
-                       chw);
-  }
-  TRASE_POST_LAUNCH("frame_unpack", stream, 0);
+  TRASE_LAUNCH("frame_unpack", stream, 0, frame_unpack_kernel, dim3((unsigned)((3ll * H * ((W + 3) / 4) + 255) / 256)), dim3(256), 0, planes, H, W, pitch,
+               chw);
   return TRASE_OK;
 }
 
@@ -453,12 +443,8 @@ int trase_frame_black_mask(const uint8_t* planes, int32_t H, int32_t W, int32_t 
   if (h < 1 || w < 1 || (long long)h * w > 0x7fffffffll) { set_error("%s: need h, w >= 1 and h * w < 2^31 (got %d x %d)", who, h, w); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("frame_black_mask", stream);
-    hipLaunchKernelGGL(frame_black_mask_kernel, dim3((unsigned)(((long long)h * w + 255) / 256)), dim3(256), 0, stream, planes, H, W, pitch, h, w,
-                       (float)H / (float)h, (float)W / (float)w, mask);
-  }
-  TRASE_POST_LAUNCH("frame_black_mask", stream, 0);
+  TRASE_LAUNCH("frame_black_mask", stream, 0, frame_black_mask_kernel, dim3((unsigned)(((long long)h * w + 255) / 256)), dim3(256), 0, planes, H, W, pitch, h, w,
+               (float)H / (float)h, (float)W / (float)w, mask);
   return TRASE_OK;
 }
 

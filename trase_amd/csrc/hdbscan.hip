@@ -337,23 +337,16 @@ int trase_hdbscan_core(const float* X, int32_t n, int32_t D, int32_t k, float* c
   HdWs w; hd_layout(ws, n, k, w);
   const int S = hd_splits(n), chunk = hd_chunk(n), dp = hd_dpad(D);
   const dim3 grid(hd_row_blocks(n), S), block(HD_ROWS);
-  {
-    ProfScope ps("hdbscan_core", stream);
 #define TRASE_HD_CORE(DPV, KCV) hipLaunchKernelGGL((hd_core_kernel<DPV, KCV>), grid, block, 0, stream, X, n, D, k, chunk, S, w.part)
 #define TRASE_HD_CORE_K(DPV) do { if (k <= 16) TRASE_HD_CORE(DPV, 16); else TRASE_HD_CORE(DPV, 64); } while (0)
+  TRASE_LAUNCHES("hdbscan_core", stream, 0,
     if (dp == 8) TRASE_HD_CORE_K(8);
     else if (dp == 16) TRASE_HD_CORE_K(16);
     else if (dp == 32) TRASE_HD_CORE_K(32);
-    else TRASE_HD_CORE_K(64);
+    else TRASE_HD_CORE_K(64));
 #undef TRASE_HD_CORE_K
 #undef TRASE_HD_CORE
-  }
-  TRASE_POST_LAUNCH("hdbscan_core", stream, 0);
-  {
-    ProfScope ps("hdbscan_core_merge", stream);
-    hipLaunchKernelGGL(hd_core_merge_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, w.part, n, k, S, core2_out);
-  }
-  TRASE_POST_LAUNCH("hdbscan_core_merge", stream, 0);
+  TRASE_LAUNCH("hdbscan_core_merge", stream, 0, hd_core_merge_kernel, dim3((n + 255) / 256), dim3(256), 0, w.part, n, k, S, core2_out);
   return TRASE_OK;
 }
 
@@ -370,25 +363,19 @@ int trase_hdbscan_mst(const float* X, int32_t n, int32_t D, const float* core2, 
   const dim3 grid(hd_row_blocks(n), S), block(HD_ROWS), grid1((n + 255) / 256), block1(256);
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(edge_keys_out);
   hipLaunchKernelGGL(hd_mst_init_kernel, grid1, block1, 0, stream, n, w.comp, w.best, keys, counts_out);
-  TRASE_POST_LAUNCH("hdbscan_mst_init", stream, 0);
-  for (int r = 0; r < rounds; ++r) {
-    {
-      ProfScope ps("hdbscan_min_edge", stream);
+  TRASE_POST_LAUNCH("hdbscan_mst_init", stream, 0);      // the check alone: this launch has never had a scope (a report key) of its own
 #define TRASE_HD_EDGE(DPV) hipLaunchKernelGGL((hd_min_edge_kernel<DPV>), grid, block, 0, stream, X, n, D, core2, w.comp, chunk, w.best, counts_out, r)
+  for (int r = 0; r < rounds; ++r) {
+    TRASE_LAUNCHES("hdbscan_min_edge", stream, 0,
       if (dp == 8) TRASE_HD_EDGE(8);
       else if (dp == 16) TRASE_HD_EDGE(16);
       else if (dp == 32) TRASE_HD_EDGE(32);
-      else TRASE_HD_EDGE(64);
-#undef TRASE_HD_EDGE
-    }
-    TRASE_POST_LAUNCH("hdbscan_min_edge", stream, 0);
-    {
-      ProfScope ps("hdbscan_hook", stream);
+      else TRASE_HD_EDGE(64));
+    TRASE_LAUNCHES("hdbscan_hook", stream, 0,
       hipLaunchKernelGGL(hd_hook_kernel, grid1, block1, 0, stream, n, w.comp, w.best, w.next, keys, counts_out, r);
-      hipLaunchKernelGGL(hd_jump_kernel, grid1, block1, 0, stream, n, w.next, w.comp, w.best, counts_out, r);
-    }
-    TRASE_POST_LAUNCH("hdbscan_hook", stream, 0);
+      hipLaunchKernelGGL(hd_jump_kernel, grid1, block1, 0, stream, n, w.next, w.comp, w.best, counts_out, r));
   }
+#undef TRASE_HD_EDGE
   return TRASE_OK;
 }
 
@@ -415,13 +402,12 @@ int trase_label_centres(const float* X, int32_t N, int32_t D, const int32_t* lab
   TRASE_CHECK(hipSetDevice(device));
   for (int base = 0; base < C; base += LABEL_SUMS_MAX) {          // the per-cluster sums of K-means, 128 labels at a time
     const int S = C - base < LABEL_SUMS_MAX ? C - base : LABEL_SUMS_MAX;
-    ProfScope ps("label_centres", stream);
-    hipLaunchKernelGGL(hd_iota_kernel, dim3(1), dim3(256), 0, stream, w.sel, S, base);
-    if (S < LABEL_SUMS_MAX) label_sums_layout(ws, N, D, S, w.sums);      // a last, shorter batch packs its slabs closer: inside the full batch's bytes
-    const int rc = launch_label_sums(X, N, D, labels, w.sel, S, w.sums, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(hd_centre_kernel, dim3(S), dim3(64), 0, stream, w.sums.total, S, D, base, centres_out);
-    TRASE_POST_LAUNCH("label_centres", stream, 0);
+    TRASE_LAUNCHES("label_centres", stream, 0,
+      hipLaunchKernelGGL(hd_iota_kernel, dim3(1), dim3(256), 0, stream, w.sel, S, base);
+      if (S < LABEL_SUMS_MAX) label_sums_layout(ws, N, D, S, w.sums);      // a last, shorter batch packs its slabs closer: inside the full batch's bytes
+      const int rc = launch_label_sums(X, N, D, labels, w.sel, S, w.sums, stream);
+      if (rc) return rc;
+      hipLaunchKernelGGL(hd_centre_kernel, dim3(S), dim3(64), 0, stream, w.sums.total, S, D, base, centres_out));
   }
   return TRASE_OK;
 }

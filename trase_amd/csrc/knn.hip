@@ -503,14 +503,11 @@ static int knn_build(const LaunchCtx& c, const float* points, int32_t N, KnnWs& 
                      float occ = 4.0f) {
   hipStream_t stream = c.stream;
   const int blocks = (N + 255) / 256;
-  {
-    ProfScope ps("knn_bbox", stream);
+  TRASE_LAUNCHES_AS("knn_bbox", "knn_keys", stream, 0,
     hipLaunchKernelGGL(knn_init_kernel, dim3(1), dim3(1), 0, stream, w.prm, (uint32_t)N);
     hipLaunchKernelGGL(knn_bbox_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, stream, points, N, w.prm);
     hipLaunchKernelGGL(knn_params_kernel, dim3(1), dim3(1), 0, stream, w.prm, occ);
-    hipLaunchKernelGGL(knn_keys_kernel, dim3(blocks), dim3(256), 0, stream, points, N, w.prm, mask, w.sort.keys[0]);
-  }
-  TRASE_POST_LAUNCH("knn_keys", stream, 0);
+    hipLaunchKernelGGL(knn_keys_kernel, dim3(blocks), dim3(256), 0, stream, points, N, w.prm, mask, w.sort.keys[0]));
   int rc = radix_sort_pairs(c, w.sort, &w.prm->n, (uint32_t)N, 0, bits, true, idx_out);
   if (rc) return rc;
   return launch_tile_ranges(c, w.sort.keys[*idx_out], &w.prm->n, (uint32_t)N, w.buckets, 1 << bits);
@@ -530,12 +527,8 @@ int trase_knn_dist2(const float* points, int32_t N, float* out, void* ws, size_t
   int idx = 0;
   int rc = knn_build(c, points, N, w, mask, bits, &idx);
   if (rc) return rc;
-  {
-    ProfScope ps("knn_query", stream);
-    hipLaunchKernelGGL(knn_query_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, points, N, w.prm, mask, w.sort.vals[idx],
-                       w.buckets, out);
-  }
-  TRASE_POST_LAUNCH("knn_query", stream, 0);
+  TRASE_LAUNCH("knn_query", stream, 0, knn_query_kernel, dim3((N + 255) / 256), dim3(256), 0, points, N, w.prm, mask, w.sort.vals[idx],
+               w.buckets, out);
   return TRASE_OK;
 }
 
@@ -557,9 +550,8 @@ int trase_knn_points(const float* p1, int32_t N1, const float* p2, int32_t N2, i
   LaunchCtx c{stream, 0, 0};
   const int blocks = (N1 + 255) / 256;
   if (N2 == 0) {   // nothing to find: pytorch3d pads with idx 0 / dist 0 -- keep that convention
-    launch_zero_bytes(idx_out, sizeof(int64_t) * (size_t)N1 * K, stream);
-    launch_zero_bytes(dist_out, sizeof(float) * (size_t)N1 * K, stream);
-    return TRASE_OK;
+    if (int rc = launch_zero_bytes(idx_out, sizeof(int64_t) * (size_t)N1 * K, stream)) return rc;
+    return launch_zero_bytes(dist_out, sizeof(float) * (size_t)N1 * K, stream);
   }
   KnnWs w; knn_layout(ws, N2, w);
   const int bits = knn_bits(N2);
@@ -572,21 +564,14 @@ int trase_knn_points(const float* p1, int32_t N1, const float* p2, int32_t N2, i
   if (wide) {
     int total = 128;
     while (total < 2 * K + WAVE && total < KW_KEYS) total <<= 1;
-    {
-      ProfScope ps("knn_points_wide", stream);
-      hipLaunchKernelGGL(knn_points_wide_kernel, dim3((N1 + KW_WAVES - 1) / KW_WAVES), dim3(WAVE * KW_WAVES), 0, stream, p1, N1,
-                         p2, N2, K, total, w.prm, mask, w.sort.vals[idx], w.buckets, idx_out, dist_out);
-    }
-    TRASE_POST_LAUNCH("knn_points_wide", stream, 0);
+    TRASE_LAUNCH("knn_points_wide", stream, 0, knn_points_wide_kernel, dim3((N1 + KW_WAVES - 1) / KW_WAVES), dim3(WAVE * KW_WAVES), 0, p1, N1,
+                 p2, N2, K, total, w.prm, mask, w.sort.vals[idx], w.buckets, idx_out, dist_out);
     return TRASE_OK;
   }
-  {
-    ProfScope ps("knn_points_query", stream);
 #define TRASE_KQ(KT) hipLaunchKernelGGL((knn_points_kernel<KT>), dim3(blocks), dim3(256), 0, stream, p1, N1, p2, N2, K, w.prm, mask, w.sort.vals[idx], w.buckets, idx_out, dist_out)
-    if (K <= 1) TRASE_KQ(1); else if (K <= 4) TRASE_KQ(4); else if (K <= 8) TRASE_KQ(8); else TRASE_KQ(16);
+  TRASE_LAUNCHES("knn_points_query", stream, 0,
+    if (K <= 1) TRASE_KQ(1); else if (K <= 4) TRASE_KQ(4); else if (K <= 8) TRASE_KQ(8); else TRASE_KQ(16));
 #undef TRASE_KQ
-  }
-  TRASE_POST_LAUNCH("knn_points_query", stream, 0);
   return TRASE_OK;
 }
 
@@ -620,7 +605,7 @@ int trase_lift_votes(const float* depth, int32_t W, int32_t H, const double* inv
   if (N > 0 && (!ws || ws_bytes < knn_ws_bytes(N))) { set_error("trase_lift_votes: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  if (bins > 0) launch_zero_bytes(votes_out, sizeof(int32_t) * (size_t)bins, stream);
+  if (int rc = launch_zero_bytes(votes_out, sizeof(int32_t) * (size_t)bins, stream)) return rc;   // (bins == 0: no launch)
   if (click && M == 0) return TRASE_OK;
   LiftCam cam;
   const double za = zfar / (zfar - znear), zb = zfar * znear / (zfar - znear);
@@ -646,15 +631,11 @@ int trase_lift_votes(const float* depth, int32_t W, int32_t H, const double* inv
   const int units = click ? (M + LIFT_BLOCK - 1) / LIFT_BLOCK
                           : ((W + LIFT_TILE - 1) / LIFT_TILE) * ((H + LIFT_TILE - 1) / LIFT_TILE);
   const int blocks = units < LIFT_MAX_BLOCKS ? units : LIFT_MAX_BLOCKS;
-  {
-    ProfScope ps("lift_votes", stream);
 #define TRASE_LIFT(CLICK) hipLaunchKernelGGL((lift_kernel<CLICK>), dim3(blocks), dim3(LIFT_BLOCK), 0, stream, depth, prompt_mask, \
                                              pixels, M, W, H, cam, points, N, w.prm, mask, N > 0 ? w.sort.vals[idx] : nullptr, \
                                              w.buckets, cluster_ids, bins, votes_out, index_out, points_out)
-    if (click) TRASE_LIFT(true); else TRASE_LIFT(false);
+  TRASE_LAUNCHES("lift_votes", stream, 0, if (click) TRASE_LIFT(true); else TRASE_LIFT(false));
 #undef TRASE_LIFT
-  }
-  TRASE_POST_LAUNCH("lift_votes", stream, 0);
   return TRASE_OK;
 }
 

@@ -57,11 +57,7 @@ int launch_layers_pack(const float* const* tables, int L, int P, float* out, hip
   for (int l = 0; l < TRASE_LAYERS_MAX; ++l) a.tab[l] = l < L ? tables[l] : nullptr;
   a.out = out; a.P = P; a.L = L;
   const int blocks = (P + LAYERS_ROWS - 1) / LAYERS_ROWS;
-  {
-    ProfScope ps("layers_pack", stream);
-    hipLaunchKernelGGL(layers_pack_kernel, dim3(blocks), dim3(LAYERS_THREADS), 0, stream, a);
-  }
-  TRASE_POST_LAUNCH("layers_pack", stream, 0);
+  TRASE_LAUNCH("layers_pack", stream, 0, layers_pack_kernel, dim3(blocks), dim3(LAYERS_THREADS), 0, a);
   return TRASE_OK;
 }
 
@@ -133,11 +129,7 @@ int launch_layers_finish(float* planes, const float* final_T, const float* bg, i
   const int items = ((W + 3) / 4) * H;
   int blocks = (items + LAYERS_THREADS - 1) / LAYERS_THREADS;
   if (blocks > LAYERS_MAX_BLOCKS) blocks = LAYERS_MAX_BLOCKS;
-  {
-    ProfScope ps("layers_finish", stream);
-    hipLaunchKernelGGL(layers_finish_kernel, dim3(blocks), dim3(LAYERS_THREADS), 0, stream, a);
-  }
-  TRASE_POST_LAUNCH("layers_finish", stream, 0);
+  TRASE_LAUNCH("layers_finish", stream, 0, layers_finish_kernel, dim3(blocks), dim3(LAYERS_THREADS), 0, a);
   return TRASE_OK;
 }
 

@@ -319,17 +319,9 @@ static int loss_forward_launch(const char* who, const float* img, const GT& gt, 
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const dim3 grid((W + LT - 1) / LT, (H + LT - 1) / LT, C);
-  {
-    ProfScope ps("ssim_fwd", stream);
-    hipLaunchKernelGGL(ssim_fwd_kernel<GT>, grid, dim3(256), 0, stream, img, gt, H, W, make_window(), w.dmaps, w.partial);
-  }
-  TRASE_POST_LAUNCH("ssim_fwd", stream, 0);
-  {
-    ProfScope ps("loss_reduce", stream);
-    hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, stream, w.partial, w.nblocks, 1.0f / ((float)C * H * W), out2,
-                       (float)lambda_dssim, (float)(1.0 - lambda_dssim));
-  }
-  TRASE_POST_LAUNCH("loss_reduce", stream, 0);
+  TRASE_LAUNCH("ssim_fwd", stream, 0, ssim_fwd_kernel<GT>, grid, dim3(256), 0, img, gt, H, W, make_window(), w.dmaps, w.partial);
+  TRASE_LAUNCH("loss_reduce", stream, 0, loss_reduce_kernel, dim3(1), dim3(256), 0, w.partial, w.nblocks, 1.0f / ((float)C * H * W), out2,
+               (float)lambda_dssim, (float)(1.0 - lambda_dssim));
   return TRASE_OK;
 }
 
@@ -366,12 +358,8 @@ static int loss_backward_launch(const char* who, const float* img, const GT& gt,
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const dim3 grid((W + LT - 1) / LT, (H + LT - 1) / LT, C);
-  {
-    ProfScope ps("ssim_bwd", stream);
-    hipLaunchKernelGGL(ssim_bwd_kernel<GT>, grid, dim3(256), 0, stream, img, gt, H, W, make_window(), w.dmaps, g2,
-                       1.0f / ((float)C * H * W), dL_dimg, g_stride, s_l1, s_ssim);
-  }
-  TRASE_POST_LAUNCH("ssim_bwd", stream, 0);
+  TRASE_LAUNCH("ssim_bwd", stream, 0, ssim_bwd_kernel<GT>, grid, dim3(256), 0, img, gt, H, W, make_window(), w.dmaps, g2,
+               1.0f / ((float)C * H * W), dL_dimg, g_stride, s_l1, s_ssim);
   return TRASE_OK;
 }
 

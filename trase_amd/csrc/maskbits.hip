@@ -202,15 +202,11 @@ int trase_mask_stats_bits(const uint8_t* bits, size_t bits_bytes, int32_t N, int
   while ((1 << nplanes) <= N) ++nplanes;                     // floor(log2 N) + 1: every count <= N fits
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  launch_zero_bytes(mask_size, sizeof(uint32_t) * (size_t)N, stream);
-  {
-    ProfScope ps("mask_stats_bits", stream);
-    const int64_t per_block = 256 * MB_PIX;
-    hipLaunchKernelGGL(mask_stats_bits_kernel, dim3((unsigned)((HW + per_block - 1) / per_block)), dim3(256), sizeof(uint32_t) * (size_t)N,
-                       stream, reinterpret_cast<const uint32_t*>(bits), (unsigned long long)(bits_bytes / 4), N, (long long)HW, nplanes,
-                       cover_count, mask_size);
-  }
-  TRASE_POST_LAUNCH("mask_stats_bits", stream, 0);
+  if (int rc = launch_zero_bytes(mask_size, sizeof(uint32_t) * (size_t)N, stream)) return rc;
+  const int64_t per_block = 256 * MB_PIX;
+  TRASE_LAUNCH("mask_stats_bits", stream, 0, mask_stats_bits_kernel, dim3((unsigned)((HW + per_block - 1) / per_block)), dim3(256),
+               sizeof(uint32_t) * (size_t)N, reinterpret_cast<const uint32_t*>(bits), (unsigned long long)(bits_bytes / 4), N, (long long)HW, nplanes,
+               cover_count, mask_size);
   return TRASE_OK;
 }
 
@@ -222,12 +218,8 @@ int trase_pack_masks(const uint8_t* sam_masks, int32_t N, int64_t HW, uint8_t* b
   if (blocks > 0x7fffffffull) { set_error("trase_pack_masks: %zu stream bytes are more than one launch covers", bits_bytes); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("pack_masks", stream);
-    hipLaunchKernelGGL(pack_masks_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, sam_masks,
-                       (unsigned long long)N * (unsigned long long)HW, reinterpret_cast<uint32_t*>(bits), ndw);
-  }
-  TRASE_POST_LAUNCH("pack_masks", stream, 0);
+  TRASE_LAUNCH("pack_masks", stream, 0, pack_masks_kernel, dim3((unsigned)blocks), dim3(256), 0, sam_masks,
+               (unsigned long long)N * (unsigned long long)HW, reinterpret_cast<uint32_t*>(bits), ndw);
   return TRASE_OK;
 }
 
@@ -239,12 +231,8 @@ int trase_unpack_masks(const uint8_t* bits, size_t bits_bytes, int32_t N, int64_
   if (blocks > 0x7fffffffull) { set_error("trase_unpack_masks: %llu elements are more than one launch covers", total); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("unpack_masks", stream);
-    hipLaunchKernelGGL(unpack_masks_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, reinterpret_cast<const uint32_t*>(bits), total,
-                       sam_masks);
-  }
-  TRASE_POST_LAUNCH("unpack_masks", stream, 0);
+  TRASE_LAUNCH("unpack_masks", stream, 0, unpack_masks_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<const uint32_t*>(bits), total,
+               sam_masks);
   return TRASE_OK;
 }
 

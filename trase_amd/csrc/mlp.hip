@@ -1368,11 +1368,7 @@ static int mlp_pack_forward(const TraseMlpWeights* w, void* ws, MlpNet& net, hip
   pa.w_scale = w->w_scaling; pa.b_scale = w->b_scaling;
   pa.emb = w->is_blender ? EMB_B : EMB_T;
   net.temb = nullptr;
-  {
-    ProfScope ps("mlp_pack", stream);
-    hipLaunchKernelGGL(mlp_pack_kernel, dim3((MW * (EMBP + MW) + 255) / 256, MD + 1), dim3(256), 0, stream, pa);
-  }
-  TRASE_POST_LAUNCH("mlp_pack", stream, 0);
+  TRASE_LAUNCH("mlp_pack", stream, 0, mlp_pack_kernel, dim3((MW * (EMBP + MW) + 255) / 256, MD + 1), dim3(256), 0, pa);
   return TRASE_OK;
 }
 
@@ -1386,11 +1382,7 @@ static int mlp_pack_rc(const TraseMlpWeights* w, void* ws, RcNet& net, hipStream
   pa.emb = w->is_blender ? EMB_B : EMB_T;
   MlpFwdWs f; mlp_fwd_layout(ws, f);
   net.wstream = f.rc_stream; net.bias = f.rc_bias; net.temb = nullptr;
-  {
-    ProfScope ps("mlp_pack", stream);
-    hipLaunchKernelGGL(mlp_pack_rc_kernel, dim3((RC_FWD_FRAGS * 512 + 255) / 256), dim3(256), 0, stream, pa, f.rc_stream, f.rc_bias);
-  }
-  TRASE_POST_LAUNCH("mlp_pack", stream, 0);
+  TRASE_LAUNCH("mlp_pack", stream, 0, mlp_pack_rc_kernel, dim3((RC_FWD_FRAGS * 512 + 255) / 256), dim3(256), 0, pa, f.rc_stream, f.rc_bias);
   return TRASE_OK;
 }
 
@@ -1428,11 +1420,7 @@ int trase_mlp_forward(const TraseMlpWeights* w, const float* x, const float* t, 
   RcNet rnet;
   if (int rc = mlp_pack_rc(w, ws, rnet, stream)) return rc;
   if (w->is_blender) rnet.temb = t;                        // t = the 30 timenet outputs shared by all rows
-  {
-    ProfScope ps("mlp_fwd", stream);
-    hipLaunchKernelGGL(mlp_fwd_rc_kernel, dim3((N + RC_ROWS - 1) / RC_ROWS), dim3(256), 0, stream, rnet, x, t, t_stride, N, d_xyz, d_rotation, d_scaling);
-  }
-  TRASE_POST_LAUNCH("mlp_fwd", stream, 0);
+  TRASE_LAUNCH("mlp_fwd", stream, 0, mlp_fwd_rc_kernel, dim3((N + RC_ROWS - 1) / RC_ROWS), dim3(256), 0, rnet, x, t, t_stride, N, d_xyz, d_rotation, d_scaling);
   return TRASE_OK;
 }
 
@@ -1459,13 +1447,8 @@ int trase_mlp_forward_train_rows(const TraseMlpWeights* w, const float* x, const
   MlpNet net;
   if (int rc = mlp_pack_forward(w, ws, net, stream)) return rc;
   if (w->is_blender) net.temb = t;
-  {
-    ProfScope ps("mlp_fwd_train", stream);
-    const dim3 block(MWAVES * WAVE);
-    hipLaunchKernelGGL(mlp_fwd_train_kernel_blk, dim3((N + BROWS - 1) / BROWS), block, 0, stream, net, x, t, t_stride, N,
-                       d_xyz, d_rotation, d_scaling, sv.actsT, sv.gates, (const int*)row_order, sv.peT);
-  }
-  TRASE_POST_LAUNCH("mlp_fwd_train", stream, 0);
+  TRASE_LAUNCH("mlp_fwd_train", stream, 0, mlp_fwd_train_kernel_blk, dim3((N + BROWS - 1) / BROWS), dim3(MWAVES * WAVE), 0, net, x, t, t_stride, N,
+               d_xyz, d_rotation, d_scaling, sv.actsT, sv.gates, (const int*)row_order, sv.peT);
   return TRASE_OK;
 }
 
@@ -1505,26 +1488,15 @@ int trase_mlp_backward_rows(const TraseMlpWeights* w, int32_t N, const int32_t* 
   pa.w_warp = w->w_warp; pa.w_rot = w->w_rotation; pa.w_scale = w->w_scaling;
   const int EMB = w->is_blender ? EMB_B : EMB_T;           // input columns of the encoding block
   pa.emb = EMB;
-  {
-    ProfScope ps("mlp_pack_t", stream);
-    hipLaunchKernelGGL(mlp_pack_t_kernel, dim3(MW * MW / 256, MD), dim3(256), 0, stream, pa);
-  }
-  TRASE_POST_LAUNCH("mlp_pack_t", stream, 0);
-  {   // "dead rows": the tiles that hold a row with a non-zero cotangent, as an ascending list
-    ProfScope ps("mlp_live_tiles", stream);
+  TRASE_LAUNCH("mlp_pack_t", stream, 0, mlp_pack_t_kernel, dim3(MW * MW / 256, MD), dim3(256), 0, pa);
+  // "dead rows": the tiles that hold a row with a non-zero cotangent, as an ascending list
+  TRASE_LAUNCHES("mlp_live_tiles", stream, 0,
     hipLaunchKernelGGL(mlp_tile_flags_kernel, dim3((tiles + 3) / 4), dim3(256), 0, stream, dL_dd_xyz, dL_dd_rotation, dL_dd_scaling,
                        N, (const int*)row_order, bp.tile_flags);
-    hipLaunchKernelGGL(mlp_tile_list_kernel, dim3(1), dim3(1024), 0, stream, (const int*)bp.tile_flags, tiles, bp.live_list, bp.n_live);
-  }
-  TRASE_POST_LAUNCH("mlp_live_tiles", stream, 0);
-  {
-    ProfScope ps("mlp_bwd_data", stream);
-    const dim3 block(MWAVES * WAVE);
-    hipLaunchKernelGGL(mlp_bwd_data_kernel_blk, dim3((N + BROWS - 1) / BROWS), block, 0, stream, net, dL_dd_xyz, dL_dd_rotation,
-                       dL_dd_scaling, N, (const uint32_t*)sv.gates, bp.dzT, bp.gT, (const int*)row_order, (const int*)bp.live_list,
-                       (const int*)bp.n_live);
-  }
-  TRASE_POST_LAUNCH("mlp_bwd_data", stream, 0);
+    hipLaunchKernelGGL(mlp_tile_list_kernel, dim3(1), dim3(1024), 0, stream, (const int*)bp.tile_flags, tiles, bp.live_list, bp.n_live));
+  TRASE_LAUNCH("mlp_bwd_data", stream, 0, mlp_bwd_data_kernel_blk, dim3((N + BROWS - 1) / BROWS), dim3(MWAVES * WAVE), 0, net, dL_dd_xyz, dL_dd_rotation,
+               dL_dd_scaling, N, (const uint32_t*)sv.gates, bp.dzT, bp.gT, (const int*)row_order, (const int*)bp.live_list,
+               (const int*)bp.n_live);
   const size_t img = (size_t)tiles * MW * 32;              // one layer's transposed image, elements
   WreduceJobs rj;
   int nr = 0;
@@ -1546,11 +1518,9 @@ int trase_mlp_backward_rows(const TraseMlpWeights* w, int32_t N, const int32_t* 
       const int kin = l == SKIP ? EMB + MW : MW;
       reduce_job(j.partial, j.bias_partial, grads->weight[l], grads->bias[l], MW, MW, kin, l == SKIP ? EMB : 0, MW, MW, bp.Gh);
     }
-    ProfScope ps("mlp_wgrad_hidden", stream);
-    hipLaunchKernelGGL((mlp_wgrad_lds_kernel<8, 8, 2, 2, 9, true, true>), dim3(bp.Gh, MD - 1), dim3(256), 0, stream, jobs, (const int*)bp.live_list,
-                       (const int*)bp.n_live, bp.Gh);
+    TRASE_LAUNCH("mlp_wgrad_hidden", stream, 0, (mlp_wgrad_lds_kernel<8, 8, 2, 2, 9, true, true>), dim3(bp.Gh, MD - 1), dim3(256), 0, jobs, (const int*)bp.live_list,
+                 (const int*)bp.n_live, bp.Gh);
   }
-  TRASE_POST_LAUNCH("mlp_wgrad_hidden", stream, 0);
   {   // encoding inputs: layer 0 and the first 84 columns of the skip layer
     WgradJobs jobs;
     const int ls[2] = {0, SKIP};
@@ -1562,11 +1532,9 @@ int trase_mlp_backward_rows(const TraseMlpWeights* w, int32_t N, const int32_t* 
       reduce_job(j.partial, j.bias_partial, grads->weight[ls[k]], k == 0 ? grads->bias[0] : nullptr, MW, EMBP,
                  k == 0 ? EMB : EMB + MW, 0, EMB, MW, bp.Gp);
     }
-    ProfScope ps("mlp_wgrad_pe", stream);
-    hipLaunchKernelGGL((mlp_wgrad_lds_kernel<8, 3, 4, 1, 12, true, false>), dim3(bp.Gp, 2), dim3(256), 0, stream, jobs, (const int*)bp.live_list,
-                       (const int*)bp.n_live, bp.Gp);
+    TRASE_LAUNCH("mlp_wgrad_pe", stream, 0, (mlp_wgrad_lds_kernel<8, 3, 4, 1, 12, true, false>), dim3(bp.Gp, 2), dim3(256), 0, jobs, (const int*)bp.live_list,
+                 (const int*)bp.n_live, bp.Gp);
   }
-  TRASE_POST_LAUNCH("mlp_wgrad_pe", stream, 0);
   {   // heads: cotangent image (32 padded columns) x activations of the last layer
     WgradJobs jobs;
     WgradJob& j = jobs.j[0];
@@ -1575,16 +1543,10 @@ int trase_mlp_backward_rows(const TraseMlpWeights* w, int32_t N, const int32_t* 
     r.head = 1;
     r.head_w[0] = grads->w_warp; r.head_w[1] = grads->w_rotation; r.head_w[2] = grads->w_scaling;
     r.head_b[0] = grads->b_warp; r.head_b[1] = grads->b_rotation; r.head_b[2] = grads->b_scaling;
-    ProfScope ps("mlp_wgrad_head", stream);
-    hipLaunchKernelGGL((mlp_wgrad_lds_kernel<1, 8, 1, 4, 12, false, false>), dim3(bp.Gd, 1), dim3(256), 0, stream, jobs, (const int*)bp.live_list,
-                       (const int*)bp.n_live, bp.Gd);
+    TRASE_LAUNCH("mlp_wgrad_head", stream, 0, (mlp_wgrad_lds_kernel<1, 8, 1, 4, 12, false, false>), dim3(bp.Gd, 1), dim3(256), 0, jobs, (const int*)bp.live_list,
+                 (const int*)bp.n_live, bp.Gd);
   }
-  TRASE_POST_LAUNCH("mlp_wgrad_head", stream, 0);
-  {
-    ProfScope ps("mlp_wreduce", stream);
-    hipLaunchKernelGGL(mlp_wreduce_kernel, dim3(MW * MW / 256, nr), dim3(256), 0, stream, rj);
-  }
-  TRASE_POST_LAUNCH("mlp_wreduce", stream, 0);
+  TRASE_LAUNCH("mlp_wreduce", stream, 0, mlp_wreduce_kernel, dim3(MW * MW / 256, nr), dim3(256), 0, rj);
   return TRASE_OK;
 }
 

@@ -376,17 +376,9 @@ int trase_mlp_forward_split(const TraseMlpWeights* w, const float* x, const floa
   pa.emb = w->is_blender ? EMB_B : EMB_T;
   net.stream = f.stream; net.b_head = f.b_head;
   net.temb = w->is_blender ? t : nullptr;                  // t = the 30 timenet outputs shared by all rows
-  {
-    ProfScope ps("mlp_pack_split", stream);
-    hipLaunchKernelGGL(mlp_pack_split_kernel, dim3(SP_SLABS * (SP_PLANE / 256) + SP_HEAD_ELEMS / 2 / 256), dim3(256), 0, stream, pa);
-  }
-  TRASE_POST_LAUNCH("mlp_pack_split", stream, 0);
-  {
-    ProfScope ps("mlp_fwd_split", stream);
-    hipLaunchKernelGGL(mlp_fwd_split_kernel, dim3((N + SP_ROWS - 1) / SP_ROWS), dim3(256), 0, stream, net, x, t, t_stride, N,
-                       d_xyz, d_rotation, d_scaling);
-  }
-  TRASE_POST_LAUNCH("mlp_fwd_split", stream, 0);
+  TRASE_LAUNCH("mlp_pack_split", stream, 0, mlp_pack_split_kernel, dim3(SP_SLABS * (SP_PLANE / 256) + SP_HEAD_ELEMS / 2 / 256), dim3(256), 0, pa);
+  TRASE_LAUNCH("mlp_fwd_split", stream, 0, mlp_fwd_split_kernel, dim3((N + SP_ROWS - 1) / SP_ROWS), dim3(256), 0, net, x, t, t_stride, N,
+               d_xyz, d_rotation, d_scaling);
   return TRASE_OK;
 }
 

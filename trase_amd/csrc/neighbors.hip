@@ -417,22 +417,14 @@ int trase_graph_reverse(const int32_t* idx, int32_t N, int32_t k, int32_t* rev_r
   rev_layout(ws, N, k, w);
   LaunchCtx c{stream, 0, 0};
   const uint32_t M = (uint32_t)N * (uint32_t)k;
-  {
-    ProfScope ps("graph_rev_keys", stream);
-    hipLaunchKernelGGL(rev_keys_kernel, dim3(blocks_of(M)), dim3(256), 0, stream, idx, M, (uint32_t)N, w.sort.keys[0], w.n);
-  }
-  TRASE_POST_LAUNCH("graph_rev_keys", stream, 0);
+  TRASE_LAUNCH("graph_rev_keys", stream, 0, rev_keys_kernel, dim3(blocks_of(M)), dim3(256), 0, idx, M, (uint32_t)N, w.sort.keys[0], w.n);
   int out = 0;
   int rc = radix_sort_pairs(c, w.sort, w.n, M, 0, rev_bits(N), true, &out);
   if (rc) return rc;
   rc = launch_tile_ranges(c, w.sort.keys[out], w.n, M, w.ranges, N + 1);
   if (rc) return rc;
-  {
-    ProfScope ps("graph_rev_finish", stream);
-    hipLaunchKernelGGL(rev_finish_kernel, dim3(blocks_of(M > (uint32_t)N ? M : (uint32_t)N)), dim3(256), 0, stream, w.sort.vals[out],
-                       w.ranges, M, (uint32_t)N, rev_edges, rev_ranges);
-  }
-  TRASE_POST_LAUNCH("graph_rev_finish", stream, 0);
+  TRASE_LAUNCH("graph_rev_finish", stream, 0, rev_finish_kernel, dim3(blocks_of(M > (uint32_t)N ? M : (uint32_t)N)), dim3(256), 0, w.sort.vals[out],
+               w.ranges, M, (uint32_t)N, rev_edges, rev_ranges);
   return TRASE_OK;
 }
 
@@ -466,15 +458,12 @@ int trase_feat3d_forward(const float* feats, const int32_t* idx, int32_t N, int3
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   array_layout<double>(ws, (size_t)blocks_of(ND) + 1, partial);
-  {
-    ProfScope ps("feat3d_forward", stream);
+  TRASE_LAUNCHES("feat3d_forward", stream, 0,
     hipLaunchKernelGGL(f3_table_kernel, dim3(blocks_of(ND)), dim3(256), 0, stream, feats, ND, s_tab, l_tab);
     hipLaunchKernelGGL(f3_forward_kernel, dim3(blocks_of(ND)), dim3(256), 0, stream, s_tab, l_tab, idx, (uint32_t)N, (uint32_t)D,
                        (uint32_t)k, partial);
     hipLaunchKernelGGL(f3_reduce_kernel, dim3(1), dim3(256), 0, stream, partial, (uint32_t)blocks_of(ND),
-                       1.0 / ((double)N * (double)k * (double)D), loss);
-  }
-  TRASE_POST_LAUNCH("feat3d_forward", stream, 0);
+                       1.0 / ((double)N * (double)k * (double)D), loss));
   return TRASE_OK;
 }
 
@@ -489,12 +478,8 @@ int trase_feat3d_backward(const float* s_tab, const float* l_tab, const int32_t*
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const uint32_t ND = (uint32_t)N * (uint32_t)D;
-  {
-    ProfScope ps("feat3d_backward", stream);
-    hipLaunchKernelGGL(f3_backward_kernel, dim3(blocks_of(ND)), dim3(256), 0, stream, s_tab, l_tab, idx, rev_ranges, rev_edges,
-                       (uint32_t)N, (uint32_t)D, (uint32_t)k, g_loss, (float)(1.0 / ((double)N * (double)k * (double)D)), g_feats);
-  }
-  TRASE_POST_LAUNCH("feat3d_backward", stream, 0);
+  TRASE_LAUNCH("feat3d_backward", stream, 0, f3_backward_kernel, dim3(blocks_of(ND)), dim3(256), 0, s_tab, l_tab, idx, rev_ranges, rev_edges,
+               (uint32_t)N, (uint32_t)D, (uint32_t)k, g_loss, (float)(1.0 / ((double)N * (double)k * (double)D)), g_feats);
   return TRASE_OK;
 }
 
@@ -505,12 +490,8 @@ int trase_edge_moments_forward(const float* p1, const float* p2, const int32_t* 
   if (!p1 || !p2 || !idx || !S) { set_error("trase_edge_moments_forward: null pointer"); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("edge_moments_fwd", stream);
-    hipLaunchKernelGGL(edge_moments_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, idx, (uint32_t)N,
-                       (uint32_t)k, S);
-  }
-  TRASE_POST_LAUNCH("edge_moments_fwd", stream, 0);
+  TRASE_LAUNCH("edge_moments_fwd", stream, 0, edge_moments_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, p1, p2, idx, (uint32_t)N,
+               (uint32_t)k, S);
   return TRASE_OK;
 }
 
@@ -524,12 +505,8 @@ int trase_edge_moments_backward(const float* p1, const float* p2, const int32_t*
   }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("edge_moments_bwd", stream);
-    hipLaunchKernelGGL(edge_moments_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, idx, rev_ranges,
-                       rev_edges, (uint32_t)N, (uint32_t)k, gS, g1, g2);
-  }
-  TRASE_POST_LAUNCH("edge_moments_bwd", stream, 0);
+  TRASE_LAUNCH("edge_moments_bwd", stream, 0, edge_moments_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, p1, p2, idx, rev_ranges,
+               rev_edges, (uint32_t)N, (uint32_t)k, gS, g1, g2);
   return TRASE_OK;
 }
 
@@ -540,12 +517,8 @@ int trase_edge_residual_forward(const float* p1, const float* p2, const int32_t*
   if (!p1 || !p2 || !idx || !R || !out) { set_error("trase_edge_residual_forward: null pointer"); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("edge_residual_fwd", stream);
-    hipLaunchKernelGGL(edge_residual_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, idx, R, (uint32_t)N,
-                       (uint32_t)k, out);
-  }
-  TRASE_POST_LAUNCH("edge_residual_fwd", stream, 0);
+  TRASE_LAUNCH("edge_residual_fwd", stream, 0, edge_residual_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, p1, p2, idx, R, (uint32_t)N,
+               (uint32_t)k, out);
   return TRASE_OK;
 }
 
@@ -559,12 +532,8 @@ int trase_edge_residual_backward(const float* p1, const float* p2, const int32_t
   }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("edge_residual_bwd", stream);
-    hipLaunchKernelGGL(edge_residual_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, idx, rev_ranges,
-                       rev_edges, R, (uint32_t)N, (uint32_t)k, g, g1, g2, gR);
-  }
-  TRASE_POST_LAUNCH("edge_residual_bwd", stream, 0);
+  TRASE_LAUNCH("edge_residual_bwd", stream, 0, edge_residual_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, p1, p2, idx, rev_ranges,
+               rev_edges, R, (uint32_t)N, (uint32_t)k, g, g1, g2, gR);
   return TRASE_OK;
 }
 
@@ -574,11 +543,7 @@ int trase_polar3_forward(const float* S, int32_t N, float* R, int32_t device, tr
   if (!S || !R) { set_error("trase_polar3_forward: null pointer"); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("polar3_fwd", stream);
-    hipLaunchKernelGGL(polar3_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, S, (uint32_t)N, R);
-  }
-  TRASE_POST_LAUNCH("polar3_fwd", stream, 0);
+  TRASE_LAUNCH("polar3_fwd", stream, 0, polar3_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, S, (uint32_t)N, R);
   return TRASE_OK;
 }
 
@@ -589,11 +554,7 @@ int trase_polar3_backward(const float* S, const float* R, const float* gR, int32
   if (!S || !R || !gR || !gS) { set_error("trase_polar3_backward: null pointer"); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("polar3_bwd", stream);
-    hipLaunchKernelGGL(polar3_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, S, R, gR, (uint32_t)N, gS);
-  }
-  TRASE_POST_LAUNCH("polar3_bwd", stream, 0);
+  TRASE_LAUNCH("polar3_bwd", stream, 0, polar3_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, S, R, gR, (uint32_t)N, gS);
   return TRASE_OK;
 }
 
@@ -604,12 +565,8 @@ int trase_rigid_fit_forward(const float* p1, const float* p2, const int32_t* idx
   if (!p1 || !p2 || !idx || !out || !R || !state) { set_error("trase_rigid_fit_forward: null pointer"); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("rigid_fit_fwd", stream);
-    hipLaunchKernelGGL(rigid_fit_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, idx, (uint32_t)N,
-                       (uint32_t)k, out, R, state);
-  }
-  TRASE_POST_LAUNCH("rigid_fit_fwd", stream, 0);
+  TRASE_LAUNCH("rigid_fit_fwd", stream, 0, rigid_fit_fwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, p1, p2, idx, (uint32_t)N,
+               (uint32_t)k, out, R, state);
   return TRASE_OK;
 }
 
@@ -623,13 +580,9 @@ int trase_rigid_fit_backward(const float* p1, const float* p2, const int32_t* id
   }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    // (the row's own edges come from the saved sums: idx is not walked)
-    ProfScope ps("rigid_fit_bwd", stream);
-    hipLaunchKernelGGL(rigid_fit_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, stream, p1, p2, rev_ranges, rev_edges, R,
-                       state, g, (uint32_t)N, (uint32_t)k, g1, g2);
-  }
-  TRASE_POST_LAUNCH("rigid_fit_bwd", stream, 0);
+  // (the row's own edges come from the saved sums: idx is not walked)
+  TRASE_LAUNCH("rigid_fit_bwd", stream, 0, rigid_fit_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, p1, p2, rev_ranges, rev_edges, R,
+               state, g, (uint32_t)N, (uint32_t)k, g1, g2);
   return TRASE_OK;
 }
 

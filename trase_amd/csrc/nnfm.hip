@@ -276,12 +276,11 @@ int trase_nnfm_forward(const float* feat1, const float* feats2, int32_t C, int32
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   LaunchCtx c{stream, 0, 0};
-  { ProfScope ps("nnfm_prep", stream);
+  TRASE_LAUNCHES("nnfm_prep", stream, c.debug,
     hipLaunchKernelGGL(nnfm_prep_kernel, dim3((N1 + 63) / 64), dim3(256), 0, stream, feat1, C, N1, w.A, w.inv1);
-    hipLaunchKernelGGL(nnfm_prep_kernel, dim3((N2 + 63) / 64), dim3(256), 0, stream, feats2, C, N2, w.B, w.inv2); }
-  TRASE_POST_LAUNCH("nnfm_prep", stream, c.debug);
-  { ProfScope ps("nnfm_match", stream);
-    const dim3 grid((N1 + 32 * NN_WPB - 1) / (32 * NN_WPB)), block(NN_WPB * WAVE);
+    hipLaunchKernelGGL(nnfm_prep_kernel, dim3((N2 + 63) / 64), dim3(256), 0, stream, feats2, C, N2, w.B, w.inv2));
+  const dim3 grid((N1 + 32 * NN_WPB - 1) / (32 * NN_WPB)), block(NN_WPB * WAVE);
+  TRASE_LAUNCHES("nnfm_match", stream, c.debug,
     switch (C / 64) {
       case 1: hipLaunchKernelGGL(nnfm_match_kernel<4>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
       case 2: hipLaunchKernelGGL(nnfm_match_kernel<8>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
@@ -291,13 +290,11 @@ int trase_nnfm_forward(const float* feat1, const float* feats2, int32_t C, int32
       case 6: hipLaunchKernelGGL(nnfm_match_kernel<24>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
       case 7: hipLaunchKernelGGL(nnfm_match_kernel<28>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
       default: hipLaunchKernelGGL(nnfm_match_kernel<32>, grid, block, 0, stream, w.A, N1, w.B, N2, w.bj, w.sj); break;
-    } }
-  TRASE_POST_LAUNCH("nnfm_match", stream, c.debug);
+    });
   const int nb = (N1 + 255) / 256;
-  { ProfScope ps("nnfm_finish", stream);
+  TRASE_LAUNCHES("nnfm_finish", stream, c.debug,
     hipLaunchKernelGGL(nnfm_finish_kernel, dim3(nb), dim3(256), 0, stream, feat1, feats2, C, N1, N2, w.inv1, w.inv2, w.bj, w.sj, w.cosv, w.partial);
-    hipLaunchKernelGGL(nnfm_sum_kernel, dim3(1), dim3(256), 0, stream, w.partial, nb, N1, loss); }
-  TRASE_POST_LAUNCH("nnfm_finish", stream, c.debug);
+    hipLaunchKernelGGL(nnfm_sum_kernel, dim3(1), dim3(256), 0, stream, w.partial, nb, N1, loss));
   return TRASE_OK;
 }
 
@@ -309,11 +306,8 @@ int trase_nnfm_backward(const float* feat1, const float* feats2, int32_t C, int3
   if (!feat1 || !feats2 || !g_loss || !dL_dfeat1 || !ws || ws_bytes < nn_layout(const_cast<void*>(ws), C, N1, N2, w)) { set_error("nnfm_backward: bad arguments / workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  { ProfScope ps("nnfm_bwd", stream);
-    hipLaunchKernelGGL(nnfm_bwd_kernel, dim3((N1 + 255) / 256, 8), dim3(256), 0, stream, feat1, feats2, C, N1, N2,
-                       w.inv1, w.inv2, w.bj, w.cosv,
-                       g_loss, dL_dfeat1); }
-  TRASE_POST_LAUNCH("nnfm_bwd", stream, 0);
+  TRASE_LAUNCH("nnfm_bwd", stream, 0, nnfm_bwd_kernel, dim3((N1 + 255) / 256, 8), dim3(256), 0, feat1, feats2, C, N1, N2,
+               w.inv1, w.inv2, w.bj, w.cosv, g_loss, dL_dfeat1);
   return TRASE_OK;
 }
 

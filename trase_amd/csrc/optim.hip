@@ -87,13 +87,9 @@ int trase_adam_step_guarded(int32_t count, float* const* params, const float* co
   if (k == 0) return TRASE_OK;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("adam", stream);
-    // 1 - beta in double, then rounded (as Python does for torch): 1.0f - 0.999f would lose five digits
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, stream, t, (float)(1.0 - beta1), (float)beta2,
-                       (float)(1.0 - beta2), eps, (const uint32_t*)guard);
-  }
-  TRASE_POST_LAUNCH("adam", stream, 0);
+  // 1 - beta in double, then rounded (as Python does for torch): 1.0f - 0.999f would lose five digits
+  TRASE_LAUNCH("adam", stream, 0, adam_kernel, dim3(blocks), dim3(256), 0, t, (float)(1.0 - beta1), (float)beta2,
+               (float)(1.0 - beta2), eps, (const uint32_t*)guard);
   return TRASE_OK;
 }
 

@@ -809,17 +809,14 @@ int trase_mask_stats(const uint8_t* sam_masks, int32_t N, int64_t HW, int32_t* c
   if (!sam_masks || !cover_count || !mask_size || N < 1 || N > 8192 || HW < 1) { set_error("trase_mask_stats: bad arguments"); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  launch_zero_bytes(mask_size, sizeof(uint32_t) * (size_t)N, stream);
-  {
-    ProfScope ps("mask_stats", stream);
+  if (int rc = launch_zero_bytes(mask_size, sizeof(uint32_t) * (size_t)N, stream)) return rc;
+  TRASE_LAUNCHES("mask_stats", stream, 0,
     if ((HW & 15) == 0 && (((size_t)sam_masks | (size_t)cover_count) & 15) == 0)
       hipLaunchKernelGGL(mask_stats16_kernel, dim3((unsigned)((HW + 4095) / 4096)), dim3(256), sizeof(uint32_t) * (size_t)N, stream,
                          sam_masks, N, (long long)HW, cover_count, mask_size);
     else
       hipLaunchKernelGGL(mask_stats_kernel, dim3((unsigned)((HW + 1023) / 1024)), dim3(256), sizeof(uint32_t) * (size_t)N, stream,
-                         sam_masks, N, (long long)HW, cover_count, mask_size);
-  }
-  TRASE_POST_LAUNCH("mask_stats", stream, 0);
+                         sam_masks, N, (long long)HW, cover_count, mask_size));
   return TRASE_OK;
 }
 
@@ -838,13 +835,10 @@ int trase_compact_pixels(const uint8_t* flags, int64_t HW, int32_t* pix, int32_t
   if (!ws || ws_bytes < array_layout(ws, (size_t)nblocks, counts)) { set_error("trase_compact_pixels: workspace too small"); return TRASE_ERR_WORKSPACE; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("compact_pixels", stream);
+  TRASE_LAUNCHES("compact_pixels", stream, 0,
     hipLaunchKernelGGL(cp_count_kernel, dim3(nblocks), dim3(256), 0, stream, flags, (long long)HW, counts);
     hipLaunchKernelGGL(cp_scatter_kernel, dim3(nblocks), dim3(256), 0, stream, flags, (long long)HW, counts, nblocks, pix, cap,
-                       count2);
-  }
-  TRASE_POST_LAUNCH("compact_pixels", stream, 0);
+                       count2));
   return TRASE_OK;
 }
 
@@ -916,9 +910,9 @@ static int pairhead_forward(const PairCall& c, const float* feats, const uint8_t
   hipStream_t stream = (hipStream_t)c.stream;
   TRASE_CHECK(hipSetDevice(c.device));
   // colP and colN are neighbours in the workspace (pair_ws_layout): one fill for both
-  launch_zero_bytes(w.colP, (size_t)((char*)w.colN - (char*)w.colP) + sizeof(int) * (size_t)S, stream);
+  if (int rc = launch_zero_bytes(w.colP, (size_t)((char*)w.colN - (char*)w.colP) + sizeof(int) * (size_t)S, stream)) return rc;
   const dim3 grid((S + 255) / 256, (S + PH_ROWS - 1) / PH_ROWS);
-  {
+  {     // on the primitive: the name is chosen at run time, and the check takes a literal
     ProfScope ps(c.resized ? "pairhead_fwd_resized" : "pairhead_fwd", stream);
     hipLaunchKernelGGL(ph_rank_kernel, dim3(1), dim3(256), 0, stream, sampled_mask, N, w.rank, w.consts);
     if (c.resized) {      // what the backward gathers through: written here, where the workspace is still the caller's to write
@@ -964,8 +958,9 @@ static int pairhead_backward(const PairCall& c, const float* out8, const float* 
   const int* S_dev = c.S_dev;
   hipStream_t stream = (hipStream_t)c.stream;
   TRASE_CHECK(hipSetDevice(c.device));
-  if (!c.resized && !accumulate) launch_zero_bytes(dL_dfeats, sizeof(float) * (size_t)c.F * (size_t)c.HW, stream);
-  {
+  if (!c.resized && !accumulate)
+    if (int rc = launch_zero_bytes(dL_dfeats, sizeof(float) * (size_t)c.F * (size_t)c.HW, stream)) return rc;
+  {     // on the primitive: the name is chosen at run time, and the resized head is checked once, after its spread
     ProfScope ps(c.resized ? "pairhead_bwd_resized" : "pairhead_bwd", stream);
     hipLaunchKernelGGL(ph_bwd_kernel, dim3((S + 255) / 256, PH_CHUNKS), dim3(256), 0, stream, w.fn, w.bits, w.a, w.consts, S, S_dev, c.positive_th,
                        c.negative_th, c.mode, c.use_weights, w.colP, w.colN, out8, g2, w.dpart);
@@ -973,12 +968,9 @@ static int pairhead_backward(const PairCall& c, const float* out8, const float* 
                        w.fn, w.rinv, c.pix, S, S_dev, c.resized ? 0ll : (long long)c.HW, c.resized ? 0 : accumulate, c.resized ? w.v : dL_dfeats);
   }
   if (!c.resized) { TRASE_POST_LAUNCH("pairhead_bwd", stream, 0); return TRASE_OK; }
-  {
-    ProfScope ps("pairhead_spread", stream);
+  TRASE_LAUNCHES_AS("pairhead_spread", "pairhead_bwd_resized", stream, 0,
     hipLaunchKernelGGL(reg ? ph_spread_kernel<true> : ph_spread_kernel<false>, dim3((unsigned)(((int64_t)c.g.Hr * c.g.Wr + 255) / 256)), dim3(256), 0,
-                       stream, w.v, w.slot, w.row_first, w.row_count, w.col_first, w.col_count, c.g, feats, out2, g_reg, dL_dfeats);
-  }
-  TRASE_POST_LAUNCH("pairhead_bwd_resized", stream, 0);
+                       stream, w.v, w.slot, w.row_first, w.row_count, w.col_first, w.col_count, c.g, feats, out2, g_reg, dL_dfeats));
   return TRASE_OK;
 }
 
@@ -1076,11 +1068,7 @@ int trase_pairhead_columns_resized(const float* feats, int32_t F, int32_t Hr, in
   if (int rc = channels_ok("trase_pairhead_columns_resized", F)) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("pairhead_columns_resized", stream);
-    hipLaunchKernelGGL(ph_columns_kernel, dim3((S * 8 + 255) / 256), dim3(256), 0, stream, feats, resize_geom(Hr, Wr, h, w), pix, S, columns);
-  }
-  TRASE_POST_LAUNCH("pairhead_columns_resized", stream, 0);
+  TRASE_LAUNCH("pairhead_columns_resized", stream, 0, ph_columns_kernel, dim3((S * 8 + 255) / 256), dim3(256), 0, feats, resize_geom(Hr, Wr, h, w), pix, S, columns);
   return TRASE_OK;
 }
 
@@ -1099,12 +1087,9 @@ int trase_featnorm_forward(const float* feats, int32_t F, int64_t HW, float* out
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const int nblk = (int)std::min<long long>(1024, (HW + 255) / 256);
-  {
-    ProfScope ps("featnorm_fwd", stream);
+  TRASE_LAUNCHES("featnorm_fwd", stream, 0,
     hipLaunchKernelGGL(featnorm_fwd_kernel, dim3(nblk), dim3(256), 0, stream, feats, (long long)HW, F, partial);
-    hipLaunchKernelGGL(featnorm_final_kernel, dim3(1), dim3(256), 0, stream, partial, nblk, (long long)HW, out2);
-  }
-  TRASE_POST_LAUNCH("featnorm_fwd", stream, 0);
+    hipLaunchKernelGGL(featnorm_final_kernel, dim3(1), dim3(256), 0, stream, partial, nblk, (long long)HW, out2));
   return TRASE_OK;
 }
 
@@ -1113,12 +1098,8 @@ int trase_featnorm_backward(const float* feats, int32_t F, int64_t HW, const flo
   if (!feats || !out2 || !g || !dL_dfeats || F < 1 || HW < 1) { set_error("trase_featnorm_backward: bad arguments"); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("featnorm_bwd", stream);
-    hipLaunchKernelGGL(featnorm_bwd_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, stream, feats, (long long)HW, F, out2, g,
-                       dL_dfeats);
-  }
-  TRASE_POST_LAUNCH("featnorm_bwd", stream, 0);
+  TRASE_LAUNCH("featnorm_bwd", stream, 0, featnorm_bwd_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, feats, (long long)HW, F, out2, g,
+               dL_dfeats);
   return TRASE_OK;
 }
 

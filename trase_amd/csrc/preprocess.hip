@@ -132,14 +132,11 @@ int launch_preprocess_fwd(const LaunchCtx& c, const TraseRastSettings& s, const 
   a.key27 = key27 ? 1 : 0;
   const dim3 grid((in.P + 255) / 256), block(256);
   const bool cov = in.cov3D_precomp != nullptr, sh = in.shs != nullptr;
-  {
-    ProfScope ps("preprocess_fwd", c.stream);
 #define TRASE_PRE_FWD(C, S) hipLaunchKernelGGL((preprocess_fwd_kernel<C, S>), grid, block, 0, c.stream, a, radii, g.xy, g.conic_o, g.rgbd, g.geo, g.tiles, g.clamped, depth_keys, g.hdr)
+  TRASE_LAUNCHES("preprocess_fwd", c.stream, c.debug,
     if (cov) { if (sh) TRASE_PRE_FWD(true, true); else TRASE_PRE_FWD(true, false); }
-    else { if (sh) TRASE_PRE_FWD(false, true); else TRASE_PRE_FWD(false, false); }
+    else { if (sh) TRASE_PRE_FWD(false, true); else TRASE_PRE_FWD(false, false); });
 #undef TRASE_PRE_FWD
-  }
-  TRASE_POST_LAUNCH("preprocess_fwd", c.stream, c.debug);
   if (in.F == 32) return launch_feature_table(c, in.sh_objs, g.tiles, in.P, g.ftab);
   return TRASE_OK;
 }
@@ -161,11 +158,7 @@ __global__ __launch_bounds__(256) void feature_table_kernel(const float* __restr
 }
 int launch_feature_table(const LaunchCtx& c, const float* feats, const uint32_t* tiles, int P, uint32_t* ftab) {
   if (P <= 0) return TRASE_OK;
-  {
-    ProfScope ps("feature_table", c.stream);
-    hipLaunchKernelGGL(feature_table_kernel, dim3((P * 8 + 255) / 256), dim3(256), 0, c.stream, feats, tiles, P, ftab);
-  }
-  TRASE_POST_LAUNCH("feature_table", c.stream, c.debug);
+  TRASE_LAUNCH("feature_table", c.stream, c.debug, feature_table_kernel, dim3((P * 8 + 255) / 256), dim3(256), 0, feats, tiles, P, ftab);
   return TRASE_OK;
 }
 
@@ -278,14 +271,11 @@ int launch_preprocess_bwd(const LaunchCtx& c, const TraseRastSettings& s, const 
   o.d_cov3d = in.cov3D_precomp ? gr.dL_dcov3D : nullptr;
   const dim3 grid((in.P + 255) / 256), block(256);
   const bool cov = in.cov3D_precomp != nullptr, sh = in.shs != nullptr;
-  {
-    ProfScope ps("preprocess_bwd", c.stream);
 #define TRASE_PRE_BWD(C, S) hipLaunchKernelGGL((preprocess_bwd_kernel<C, S>), grid, block, 0, c.stream, a, radii, g.clamped, g.tiles, acc, o)
+  TRASE_LAUNCHES("preprocess_bwd", c.stream, c.debug,
     if (cov) { if (sh) TRASE_PRE_BWD(true, true); else TRASE_PRE_BWD(true, false); }
-    else { if (sh) TRASE_PRE_BWD(false, true); else TRASE_PRE_BWD(false, false); }
+    else { if (sh) TRASE_PRE_BWD(false, true); else TRASE_PRE_BWD(false, false); });
 #undef TRASE_PRE_BWD
-  }
-  TRASE_POST_LAUNCH("preprocess_bwd", c.stream, c.debug);
   return TRASE_OK;
 }
 

@@ -336,21 +336,18 @@ int launch_preprocess_fwd_raw(const LaunchCtx& c, const TraseRastSettings& s, co
   const bool infer = a.colors || a.mask || a.se3 || a.sh_dir_raw;
   const int blk = a.strip ? 256 : RAW_BLOCK;
   const dim3 grid((raw.P + blk - 1) / blk), block(blk);
-  {
-    ProfScope ps("preprocess_fwd", c.stream);
 #define TRASE_PRF2(FF, BB, II) hipLaunchKernelGGL((preprocess_fwd_raw_kernel<FF, BB, II>), grid, block, 0, c.stream, a, radii, g.xy, g.conic_o, g.rgbd, g.geo, g.ftab, g.tiles, g.clamped, depth_keys, g.hdr)
 #define TRASE_PRF(FF) do { if (a.strip) { if (infer) TRASE_PRF2(FF, 256, true); else TRASE_PRF2(FF, 256, false); } \
                            else { if (infer) TRASE_PRF2(FF, RAW_BLOCK, true); else TRASE_PRF2(FF, RAW_BLOCK, false); } } while (0)
+  TRASE_LAUNCHES("preprocess_fwd", c.stream, c.debug,
     switch (raw.F) {
       case 0: TRASE_PRF(0); break;
       case 16: TRASE_PRF(16); break;
       case 32: TRASE_PRF(32); break;
       default: set_error("preprocess_fwd_raw: feature width %d not compiled in (0,16,32)", raw.F); return TRASE_ERR_UNSUPPORTED;
-    }
+    });
 #undef TRASE_PRF
 #undef TRASE_PRF2
-  }
-  TRASE_POST_LAUNCH("preprocess_fwd", c.stream, c.debug);
   return TRASE_OK;
 }
 
@@ -575,13 +572,9 @@ int launch_zero_live_rows(const LaunchCtx& c, const GeomBuf& g, const PreBuf& pr
   add(gr.dL_dopacity, 1); add(gr.dL_dscaling, 3); add(gr.dL_dd_scaling, 3); add(gr.dL_drotation, 4); add(gr.dL_dd_rotation, 4);
   add(gr.dL_dgaussian_features, F);
   if (z.n == 0 || P == 0) return TRASE_OK;
-  {
-    ProfScope ps("zero_live_rows", c.stream);
-    const size_t nb = ((size_t)P * 16 + 255) / 256;
-    hipLaunchKernelGGL(zero_live_rows_kernel, dim3((int)(nb < 4096 ? nb : 4096)), dim3(256), 0, c.stream, z, pre.live_ids,
-                       g.hdr + (HDR_WORDS - 1), P);
-  }
-  TRASE_POST_LAUNCH("zero_live_rows", c.stream, c.debug);
+  const size_t nb = ((size_t)P * 16 + 255) / 256;
+  TRASE_LAUNCH("zero_live_rows", c.stream, c.debug, zero_live_rows_kernel, dim3((int)(nb < 4096 ? nb : 4096)), dim3(256), 0, z, pre.live_ids,
+               g.hdr + (HDR_WORDS - 1), P);
   return TRASE_OK;
 }
 
@@ -610,9 +603,8 @@ int launch_preprocess_bwd_raw(const LaunchCtx& c, const TraseRastSettings& s, co
   a.colors = raw.colors_precomp; a.mask = raw.mask; a.se3 = raw.d_xyz_se3; a.sh_dir_raw = raw.sh_dir_undeformed; a.fwd_only = 0;
   const bool infer = a.colors || a.se3 || a.sh_dir_raw;       // (a mask needs nothing here: a masked-out Gaussian has radii == 0)
   a.strip = 0;
-  {
-    ProfScope ps("preprocess_bwd", c.stream);
-    if (live_ids) {   // sparse strip gradients: the live list only (grid for P -- the count lives on the device; whole waves behind it leave at once)
+  TRASE_LAUNCHES("preprocess_bwd", c.stream, c.debug,
+    if (live_ids) {  // sparse strip gradients: the live list only (grid for P -- the count lives on the device; whole waves behind it leave at once)
       if (infer) { set_error("preprocess_bwd_raw: sparse strip gradients are a training path (no override_color / is_6dof / convert_SHs_python)"); return TRASE_ERR_UNSUPPORTED; }
       hipLaunchKernelGGL((preprocess_bwd_raw_kernel<true, 256>), dim3((raw.P + 255) / 256), dim3(256), 0, c.stream, a, radii, g.clamped, g.tiles,
                          acc, o, live_ids, g.hdr + (HDR_WORDS - 1));
@@ -621,9 +613,7 @@ int launch_preprocess_bwd_raw(const LaunchCtx& c, const TraseRastSettings& s, co
                          c.stream, a, radii, g.clamped, g.tiles, acc, o, nullptr, nullptr);
     else
       hipLaunchKernelGGL((preprocess_bwd_raw_kernel<false, RAW_BLOCK>), dim3((p_end - p_begin + RAW_BLOCK - 1) / RAW_BLOCK), dim3(RAW_BLOCK), 0,
-                         c.stream, a, radii, g.clamped, g.tiles, acc, o, nullptr, nullptr);
-  }
-  TRASE_POST_LAUNCH("preprocess_bwd", c.stream, c.debug);
+                         c.stream, a, radii, g.clamped, g.tiles, acc, o, nullptr, nullptr));
   return TRASE_OK;
 }
 

@@ -168,16 +168,13 @@ int launch_render_fwd(const LaunchCtx& c, const TraseRastSettings& s, const Tras
   a.hdr = g.hdr;
   if (a.ntiles <= 0) return TRASE_OK;                    // an empty strip
   const int T = (a.ntiles + WPB - 1) / WPB;
-  {
-    ProfScope ps("render_fwd", c.stream);
+  TRASE_LAUNCHES("render_fwd", c.stream, c.debug,
     switch (in.F) {
       case 0: hipLaunchKernelGGL(render_fwd_kernel<0>, dim3(T), dim3(RB), 0, c.stream, a, out.image, out.feats, out.depth, im.final_T, im.n_contrib); break;
       case 16: hipLaunchKernelGGL(render_fwd_kernel<16>, dim3(T), dim3(RB), 0, c.stream, a, out.image, out.feats, out.depth, im.final_T, im.n_contrib); break;
       case 32: hipLaunchKernelGGL(render_fwd_kernel<32>, dim3(T), dim3(RB), 0, c.stream, a, out.image, out.feats, out.depth, im.final_T, im.n_contrib); break;
       default: set_error("render_fwd: feature width %d not compiled in (0,16,32)", in.F); return TRASE_ERR_UNSUPPORTED;
-    }
-  }
-  TRASE_POST_LAUNCH("render_fwd", c.stream, c.debug);
+    });
   return TRASE_OK;
 }
 

@@ -240,17 +240,14 @@ int launch_render_bwd_gs(const LaunchCtx& c, const TraseRastSettings& s, const T
   { int lo, hi; strip_subtile_rows(s, lo, hi); a.tile0 = lo * a.gx8; a.ntiles = (hi - lo) * a.gx8; }
   if (a.ntiles <= 0) return TRASE_OK;                    // an empty strip: no rows (the caller has cleared the flags)
   const int blocks = (a.ntiles + GWPB - 1) / GWPB;
-  {
-    ProfScope ps("render_bwd", c.stream);
-    switch (in.F) {
 #define TRASE_BWD_GS(FF) hipLaunchKernelGGL((render_bwd_gs_kernel<FF, true>), dim3(blocks), dim3(GWPB * WAVE), 0, c.stream, a)
+  TRASE_LAUNCHES("render_bwd", c.stream, c.debug,
+    switch (in.F) {
       case 0: TRASE_BWD_GS(0); break;
       case 16: TRASE_BWD_GS(16); break;
       case 32: TRASE_BWD_GS(32); break;
       default: set_error("render_bwd: feature width %d not compiled in (0,16,32)", in.F); return TRASE_ERR_UNSUPPORTED;
-    }
-  }
-  TRASE_POST_LAUNCH("render_bwd", c.stream, c.debug);
+    });
   return TRASE_OK;
 }
 

@@ -571,9 +571,9 @@ int launch_render_bwd_hw(const LaunchCtx& c, const TraseRastSettings& s, const T
   a.W = s.image_width; a.H = s.image_height;
   a.gx8 = (a.W + SUB - 1) / SUB;
   { int lo, hi; strip_subtile_rows(s, lo, hi); a.tile0 = lo * a.gx8; a.ntiles = (hi - lo) * a.gx8; }
-  launch_zero_bytes(row_flags, flag_bytes, c.stream);   // (a kernel, not a memset node: common.h)
+  if (int rc = launch_zero_bytes(row_flags, flag_bytes, c.stream)) return rc;   // (a kernel, not a memset node: common.h)
   if (a.ntiles <= 0) return TRASE_OK;                    // an empty strip: no rows (the flags are cleared)
-  {
+  {                                                      // on the primitive: an #ifdef cannot stand inside a macro argument
     ProfScope ps("render_bwd", c.stream);
     const dim3 grid((a.ntiles + HW_WPB - 1) / HW_WPB), block(HW_WPB * WAVE);
     if (in.F == 0) hipLaunchKernelGGL((render_bwd_hw_kernel<false, false, false, true>), grid, block, 0, c.stream, a);   // image-only scope

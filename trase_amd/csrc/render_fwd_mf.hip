@@ -419,9 +419,9 @@ int launch_render_fwd_mf(const LaunchCtx& c, const TraseRastSettings& s, const T
   a.gx8 = (a.W + SUB - 1) / SUB;
   { int lo, hi; strip_subtile_rows(s, lo, hi); a.tile0 = lo * a.gx8; a.ntiles = (hi - lo) * a.gx8; }
   if (a.ntiles <= 0) return TRASE_OK;                    // an empty strip
-  {
+  {                                                      // on the primitive: an #ifdef cannot stand inside a macro argument
     ProfScope ps("render_fwd", c.stream);
-#ifdef TRASE_AB                                          // diagnostic instantiation: `make AB=1`
+#ifdef TRASE_AB                                       // diagnostic instantiation: `make AB=1`
     a.prof = g.hdr + 48;
     if (c.variant & TRASE_VARIANT_AB_COUNT) hipLaunchKernelGGL(render_fwd_mf_count_kernel, dim3(a.ntiles), dim3(FM_WAVES * WAVE), 0, c.stream, a);
     else

@@ -388,6 +388,7 @@ size_t label_sums_layout(void* ws, int N, int D, int S, LabelSumsWs& w) { return
 int launch_label_sums(const float* X, int N, int D, const int32_t* ids, const int32_t* sel, int S, const LabelSumsWs& w, hipStream_t stream) {
   static_assert(LABEL_SUMS_MAX == SEG_MAX_S, "label sums go through the query mask's accumulate kernel");
   const int G = seg_blocks(N), E = seg_slab_floats(S, D);
+  // on the primitive: these two launches run inside the caller's profiler scope, not in one of their own
   seg_launch_accum(1, X, N, D, S, nullptr, ids, sel, w.slot, w.slabs, nullptr, stream);
   TRASE_POST_LAUNCH("label_sums_accum", stream, 0);
   hipLaunchKernelGGL(seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, stream, w.slabs, G, E, w.total, nullptr);
@@ -422,22 +423,11 @@ int trase_kmeans_steps(const float* X, int32_t N, int32_t D, int32_t K, float* c
   const int G = seg_blocks(N), E = seg_slab_floats(K, D);
   LabelSumsWs w; seg_layout(ws, N, D, K, false, w);
   for (int step = 0; step < n_steps; ++step) {
-    {
-      ProfScope ps("kmeans_assign_accum", stream);
-      seg_launch_accum(0, X, N, D, K, centres, nullptr, nullptr, ids_out, w.slabs, state, stream);
-    }
-    TRASE_POST_LAUNCH("kmeans_assign_accum", stream, 0);
-    {
-      ProfScope ps("kmeans_reduce", stream);
-      hipLaunchKernelGGL(seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, stream, w.slabs, G, E, w.total, state);
-    }
-    TRASE_POST_LAUNCH("kmeans_reduce", stream, 0);
-    {
-      ProfScope ps("kmeans_finalize", stream);
-      hipLaunchKernelGGL(kmeans_finalize_kernel, dim3(1), dim3(1024), 0, stream, X, N, D, K, w.total, centres, reseed_key, tol,
-                         iter_limit, state);
-    }
-    TRASE_POST_LAUNCH("kmeans_finalize", stream, 0);
+    TRASE_LAUNCHES("kmeans_assign_accum", stream, 0,
+                   seg_launch_accum(0, X, N, D, K, centres, nullptr, nullptr, ids_out, w.slabs, state, stream));
+    TRASE_LAUNCH("kmeans_reduce", stream, 0, seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, w.slabs, G, E, w.total, state);
+    TRASE_LAUNCH("kmeans_finalize", stream, 0, kmeans_finalize_kernel, dim3(1), dim3(1024), 0, X, N, D, K, w.total, centres, reseed_key, tol,
+                 iter_limit, state);
   }
   return TRASE_OK;
 }
@@ -465,21 +455,9 @@ int trase_segment_mask(const float* X, int32_t N, int32_t D, const int32_t* ids,
   if (S == 0) return launch_zero_bytes(mask_out, (size_t)N, stream);
   const int G = seg_blocks(N), E = seg_slab_floats(S, D);
   LabelSumsWs w; seg_layout(ws, N, D, S, true, w);
-  {
-    ProfScope ps("segment_accum", stream);
-    seg_launch_accum(1, X, N, D, S, nullptr, ids, sel, w.slot, w.slabs, nullptr, stream);
-  }
-  TRASE_POST_LAUNCH("segment_accum", stream, 0);
-  {
-    ProfScope ps("segment_reduce", stream);
-    hipLaunchKernelGGL(seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, stream, w.slabs, G, E, w.total, nullptr);
-  }
-  TRASE_POST_LAUNCH("segment_reduce", stream, 0);
-  {
-    ProfScope ps("segment_mask", stream);
-    hipLaunchKernelGGL(seg_mask_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, X, N, D, S, w.total, w.slot, threshold, mask_out);
-  }
-  TRASE_POST_LAUNCH("segment_mask", stream, 0);
+  TRASE_LAUNCHES("segment_accum", stream, 0, seg_launch_accum(1, X, N, D, S, nullptr, ids, sel, w.slot, w.slabs, nullptr, stream));
+  TRASE_LAUNCH("segment_reduce", stream, 0, seg_reduce_kernel, dim3((E + 15) / 16), dim3(256), 0, w.slabs, G, E, w.total, nullptr);
+  TRASE_LAUNCH("segment_mask", stream, 0, seg_mask_kernel, dim3((N + 255) / 256), dim3(256), 0, X, N, D, S, w.total, w.slot, threshold, mask_out);
   return TRASE_OK;
 }
 
@@ -505,14 +483,11 @@ int trase_assign_clusters(const float* X, int32_t N, int32_t D, const float* cen
   TRASE_CHECK(hipSetDevice(device));
   const int dp = seg_dpad(D);
   const dim3 grid((N + ASSIGN_THREADS - 1) / ASSIGN_THREADS), block(ASSIGN_THREADS);
-  {
-    ProfScope ps("assign_clusters", stream);
+  TRASE_LAUNCHES("assign_clusters", stream, 0,
     if (dp == 8) hipLaunchKernelGGL((seg_assign_cosine_kernel<8>), grid, block, 0, stream, X, N, D, K, centres, ids_out, scores_out);
     else if (dp == 16) hipLaunchKernelGGL((seg_assign_cosine_kernel<16>), grid, block, 0, stream, X, N, D, K, centres, ids_out, scores_out);
     else if (dp == 32) hipLaunchKernelGGL((seg_assign_cosine_kernel<32>), grid, block, 0, stream, X, N, D, K, centres, ids_out, scores_out);
-    else hipLaunchKernelGGL((seg_assign_cosine_kernel<64>), grid, block, 0, stream, X, N, D, K, centres, ids_out, scores_out);
-  }
-  TRASE_POST_LAUNCH("assign_clusters", stream, 0);
+    else hipLaunchKernelGGL((seg_assign_cosine_kernel<64>), grid, block, 0, stream, X, N, D, K, centres, ids_out, scores_out));
   return TRASE_OK;
 }
 

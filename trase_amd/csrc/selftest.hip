@@ -72,12 +72,17 @@ extern "C" int trase_selftest(int32_t device, trase_stream_t stream_, char* msg,
   TRASE_CHECK(hipMalloc((void**)&df, 16 * sizeof(float)));
   TRASE_CHECK(hipMalloc((void**)&du, 4 * sizeof(unsigned long long)));
   TRASE_CHECK(hipMalloc((void**)&dm, 1024 * sizeof(float)));
+  // checked by hand, not through TRASE_POST_LAUNCH: an early return would leak the three buffers
   hipLaunchKernelGGL(selftest_wave_kernel, dim3(1), dim3(64), 0, stream, df, du);
-  hipLaunchKernelGGL(selftest_mfma_kernel, dim3(1), dim3(64), 0, stream, dm);
+  int rc = check_hip(hipGetLastError(), "selftest_wave");
+  if (!rc) {
+    hipLaunchKernelGGL(selftest_mfma_kernel, dim3(1), dim3(64), 0, stream, dm);
+    rc = check_hip(hipGetLastError(), "selftest_mfma");
+  }
   float hf[16];
   unsigned long long hu[4];
   static float hm[1024];
-  int rc = check_hip(hipMemcpyAsync(hf, df, sizeof(hf), hipMemcpyDeviceToHost, stream), "selftest copy");
+  if (!rc) rc = check_hip(hipMemcpyAsync(hf, df, sizeof(hf), hipMemcpyDeviceToHost, stream), "selftest copy");
   if (!rc) rc = check_hip(hipMemcpyAsync(hu, du, sizeof(hu), hipMemcpyDeviceToHost, stream), "selftest copy");
   if (!rc) rc = check_hip(hipMemcpyAsync(hm, dm, sizeof(hm), hipMemcpyDeviceToHost, stream), "selftest copy");
   if (!rc) rc = check_hip(hipStreamSynchronize(stream), "selftest sync");

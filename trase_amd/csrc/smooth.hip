@@ -104,16 +104,8 @@ int trase_smooth_forward(const float* features, const int64_t* knn_idx, int32_t 
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const dim3 grid((unsigned)(((size_t)P * 8 + 255) / 256)), block(256);
-  {
-    ProfScope ps("smooth_inv_norm", stream);
-    hipLaunchKernelGGL(smooth_inv_norm_kernel, grid, block, 0, stream, features, P, inv_norm);
-  }
-  TRASE_POST_LAUNCH("smooth_inv_norm", stream, 0);
-  {
-    ProfScope ps("smooth_fwd", stream);
-    hipLaunchKernelGGL(smooth_fwd_kernel, grid, block, 0, stream, features, inv_norm, knn_idx, P, K, select, S, out);
-  }
-  TRASE_POST_LAUNCH("smooth_fwd", stream, 0);
+  TRASE_LAUNCH("smooth_inv_norm", stream, 0, smooth_inv_norm_kernel, grid, block, 0, features, P, inv_norm);
+  TRASE_LAUNCH("smooth_fwd", stream, 0, smooth_fwd_kernel, grid, block, 0, features, inv_norm, knn_idx, P, K, select, S, out);
   return TRASE_OK;
 }
 
@@ -127,12 +119,8 @@ int trase_smooth_backward(const float* features, const float* inv_norm, int32_t 
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const dim3 grid((unsigned)(((size_t)P * 8 + 255) / 256)), block(256);
-  {
-    ProfScope ps("smooth_bwd", stream);
-    hipLaunchKernelGGL(smooth_bwd_kernel, grid, block, 0, stream, features, inv_norm, rev_ptr, rev_src, P, K, select_mask, S,
-                       dL_dout, dL_dfeatures);
-  }
-  TRASE_POST_LAUNCH("smooth_bwd", stream, 0);
+  TRASE_LAUNCH("smooth_bwd", stream, 0, smooth_bwd_kernel, grid, block, 0, features, inv_norm, rev_ptr, rev_src, P, K, select_mask, S,
+               dL_dout, dL_dfeatures);
   return TRASE_OK;
 }
 

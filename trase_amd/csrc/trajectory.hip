@@ -309,14 +309,13 @@ int trase_fps_sample(const float* points, int32_t N, const uint8_t* mask, int32_
   TRASE_CHECK(hipSetDevice(device));
   const int G = fps_blocks(N), chunk = (int)(((int64_t)N + G - 1) / G);
   unsigned long long* half[2] = {(unsigned long long*)partial, (unsigned long long*)partial + FPS_MAX_BLOCKS};
-  ProfScope ps("fps_sample", stream);
-  for (int i = 0; i < npoint; ++i) {
-    const bool last = i == npoint - 1;
-    hipLaunchKernelGGL(fps_step_kernel, dim3(last ? 1 : G), dim3(FPS_THREADS), 0, stream, points, N, mask, dist,
-                       i ? half[(i - 1) & 1] : nullptr, G, last ? nullptr : half[i & 1], chunk, start, i ? nullptr : start_dev,
-                       out + i);
-  }
-  TRASE_POST_LAUNCH("fps_sample", stream, 0);
+  TRASE_LAUNCHES("fps_sample", stream, 0,
+    for (int i = 0; i < npoint; ++i) {
+      const bool last = i == npoint - 1;
+      hipLaunchKernelGGL(fps_step_kernel, dim3(last ? 1 : G), dim3(FPS_THREADS), 0, stream, points, N, mask, dist,
+                         i ? half[(i - 1) & 1] : nullptr, G, last ? nullptr : half[i & 1], chunk, start, i ? nullptr : start_dev,
+                         out + i);
+    });
   return TRASE_OK;
 }
 
@@ -329,11 +328,7 @@ int trase_trajectory_append(const float* points, int32_t N, const int64_t* rows,
   if ((N > 0 && !points) || !rows || !slot_out) { set_error("trase_trajectory_append: null pointer"); return TRASE_ERR_INVALID; }
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("trajectory_append", stream);
-    hipLaunchKernelGGL(traj_append_kernel, dim3((G + 255) / 256), dim3(256), 0, stream, points, N, rows, G, slot_out);
-  }
-  TRASE_POST_LAUNCH("trajectory_append", stream, 0);
+  TRASE_LAUNCH("trajectory_append", stream, 0, traj_append_kernel, dim3((G + 255) / 256), dim3(256), 0, points, N, rows, G, slot_out);
   return TRASE_OK;
 }
 
@@ -355,28 +350,15 @@ int trase_trajectory_draw(const float* coords, int32_t S, int32_t G, int32_t fir
   TrajProj P;
   load_proj(full_proj, P);
   const int HW = W * H;
-  {
-    ProfScope ps("trajectory_fill", stream);
-    hipLaunchKernelGGL(traj_fill_kernel, dim3((HW + 255) / 256), dim3(256), 0, stream, winner, HW);
-  }
-  TRASE_POST_LAUNCH("trajectory_fill", stream, 0);
+  TRASE_LAUNCH("trajectory_fill", stream, 0, traj_fill_kernel, dim3((HW + 255) / 256), dim3(256), 0, winner, HW);
   if (S > 0) {
     const int segs = G * (S > 1 ? S - 1 : 1);          // <= 2^16 * 2^10
-    {
-      ProfScope ps("trajectory_draw", stream);
-      hipLaunchKernelGGL(traj_draw_kernel, dim3((segs + TRAJ_WAVES - 1) / TRAJ_WAVES), dim3(TRAJ_THREADS), 0, stream, coords, S, G,
-                         first, cap, P, W, H, winner);
-    }
-    TRASE_POST_LAUNCH("trajectory_draw", stream, 0);
+    TRASE_LAUNCH("trajectory_draw", stream, 0, traj_draw_kernel, dim3((segs + TRAJ_WAVES - 1) / TRAJ_WAVES), dim3(TRAJ_THREADS), 0, coords, S, G,
+                 first, cap, P, W, H, winner);
   }
-  if (overlay_out) {
-    {
-      ProfScope ps("trajectory_resolve", stream);
-      hipLaunchKernelGGL(traj_resolve_kernel, dim3((HW + 255) / 256), dim3(256), 0, stream, winner, HW, colors, overlay_out,
-                         (int)((reinterpret_cast<uintptr_t>(overlay_out) & 15) == 0));
-    }
-    TRASE_POST_LAUNCH("trajectory_resolve", stream, 0);
-  }
+  if (overlay_out)
+    TRASE_LAUNCH("trajectory_resolve", stream, 0, traj_resolve_kernel, dim3((HW + 255) / 256), dim3(256), 0, winner, HW, colors, overlay_out,
+                 (int)((reinterpret_cast<uintptr_t>(overlay_out) & 15) == 0));
   return TRASE_OK;
 }
 
@@ -394,23 +376,16 @@ int trase_present_frame(const float* image, int32_t h, int32_t w, int32_t depth,
     const int n = h * w;
     int blocks = (n + 255) / 256;
     if (blocks > 1024) blocks = 1024;
-    {
-      ProfScope ps("present_minmax", stream);
+    TRASE_LAUNCHES("present_minmax", stream, 0,
       hipLaunchKernelGGL(present_minmax_init_kernel, dim3(1), dim3(1), 0, stream, minmax);
-      hipLaunchKernelGGL(present_minmax_kernel, dim3(blocks), dim3(256), 0, stream, image, n, minmax);
-    }
-    TRASE_POST_LAUNCH("present_minmax", stream, 0);
+      hipLaunchKernelGGL(present_minmax_kernel, dim3(blocks), dim3(256), 0, stream, image, n, minmax));
   }
   PresentArgs a;
   a.image = image; a.h = h; a.w = w; a.H = H; a.W = W; a.depth = depth ? 1 : 0; a.minmax = minmax;
   a.control = control_overlay; a.overlay = overlay; a.tint = tint; a.tint_weight = tint_weight;
   a.scale_h = (float)h / (float)H; a.scale_w = (float)w / (float)W;
   a.out = out;
-  {
-    ProfScope ps("present_frame", stream);
-    hipLaunchKernelGGL(present_kernel, dim3((H * W + 255) / 256), dim3(256), 0, stream, a);
-  }
-  TRASE_POST_LAUNCH("present_frame", stream, 0);
+  TRASE_LAUNCH("present_frame", stream, 0, present_kernel, dim3((H * W + 255) / 256), dim3(256), 0, a);
   return TRASE_OK;
 }
 

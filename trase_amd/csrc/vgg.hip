@@ -544,22 +544,32 @@ static size_t vg_pack_layout(void* p, VgPackSpec d, VgPack& f) {
   return c.bytes();
 }
 
-static void vg_launch_copy(const float* src, float* dst, int n, hipStream_t stream) {
+// (the launch helpers of this file run inside their callers' profiler scopes: each launch gets the check alone, on the primitive)
+static int vg_launch_copy(const float* src, float* dst, int n, hipStream_t stream) {
   hipLaunchKernelGGL(vgg_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, src, dst, n);
+  TRASE_POST_LAUNCH("vgg_copy", stream, 0);
+  return TRASE_OK;
 }
 // fills a pack from fp32 weights (Cout, Cin, 3, 3), biases and (where the pack has them) lin vectors, all on the device
-static void vg_launch_pack(VgPackSpec d, const float* const* weights, const float* const* biases, const float* const* lin, const VgPack& p,
-                           hipStream_t stream) {
-  vg_launch_copy(weights[0], p.w1, 64 * 27, stream);
-  if (d.backward) hipLaunchKernelGGL(vgg_w1t_kernel, dim3(9), dim3(64), 0, stream, weights[0], p.w1t);
-  for (int l = 1; l <= d.layers; ++l) vg_launch_copy(biases[l - 1], p.bias[l], vg_chan(l), stream);
+static int vg_launch_pack(VgPackSpec d, const float* const* weights, const float* const* biases, const float* const* lin, const VgPack& p,
+                          hipStream_t stream) {
+  if (int rc = vg_launch_copy(weights[0], p.w1, 64 * 27, stream)) return rc;
+  if (d.backward) {
+    hipLaunchKernelGGL(vgg_w1t_kernel, dim3(9), dim3(64), 0, stream, weights[0], p.w1t);
+    TRASE_POST_LAUNCH("vgg_w1t", stream, 0);
+  }
+  for (int l = 1; l <= d.layers; ++l)
+    if (int rc = vg_launch_copy(biases[l - 1], p.bias[l], vg_chan(l), stream)) return rc;
   for (int l = 2; l <= d.layers; ++l) {
     const unsigned nb = (unsigned)((vg_stream_elems(l) / 2 + 255) / 256);
     hipLaunchKernelGGL(vgg_pack_kernel, dim3(nb), dim3(256), 0, stream, weights[l - 1], vg_chan(l - 1), vg_chan(l), 0, p.fwd[l]);
     if (d.backward) hipLaunchKernelGGL(vgg_pack_kernel, dim3(nb), dim3(256), 0, stream, weights[l - 1], vg_chan(l - 1), vg_chan(l), 1, p.bwd[l]);
+    TRASE_POST_LAUNCH("vgg_pack_weights", stream, 0);
   }
   if (d.lin)
-    for (int t = 0; t < LP_TAPS; ++t) vg_launch_copy(lin[t], p.lin[t], vg_chan(LP_TAP_LAYER[t]), stream);
+    for (int t = 0; t < LP_TAPS; ++t)
+      if (int rc = vg_launch_copy(lin[t], p.lin[t], vg_chan(LP_TAP_LAYER[t]), stream)) return rc;
+  return TRASE_OK;
 }
 
 // ---- host side: the workspaces -----------------------------------------------------------------------------------------------
@@ -682,15 +692,19 @@ static VgConv vg_forward_conv(int l, int H, int W, const VgPack& p) {
 }
 
 template <int EPI>
-static void vg_launch_conv(const VgConv& a, hipStream_t stream) {
+static int vg_launch_conv(const VgConv& a, hipStream_t stream) {
   const dim3 grid(((a.W + VG_TILE - 1) / VG_TILE) * ((a.H + VG_TILE - 1) / VG_TILE), a.Cout / VG_NB);
   hipLaunchKernelGGL(vgg_conv_kernel<EPI>, grid, dim3(256), 0, stream, a);
+  TRASE_POST_LAUNCH("vgg_conv", stream, 0);
+  return TRASE_OK;
 }
 
 // the means of the first n maps of `m`, in two steps
-static void lp_launch_means(const LpMeans& m, int n, double* parts, double* out, hipStream_t stream) {
+static int lp_launch_means(const LpMeans& m, int n, double* parts, double* out, hipStream_t stream) {
   hipLaunchKernelGGL(lpips_partial_kernel, dim3(LP_PARTS, n), dim3(256), 0, stream, m, parts);
   hipLaunchKernelGGL(lpips_mean_kernel, dim3(n), dim3(256), 0, stream, m, (const double*)parts, out);
+  TRASE_POST_LAUNCH("lpips_means", stream, 0);
+  return TRASE_OK;
 }
 
 // the profiling scopes' names: string literals, ProfScope keeps the pointer
@@ -744,9 +758,7 @@ int trase_vgg_pack(int32_t layers, const float* const* weights, const float* con
   if ((rc = vg_check_room(who, "pack buffer", pack_bytes, vg_pack_layout(pack, vg_pack_spec(layers), p)))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  ProfScope ps("vgg_pack", stream);
-  vg_launch_pack(vg_pack_spec(layers), weights, biases, nullptr, p, stream);
-  TRASE_POST_LAUNCH("vgg_pack", stream, 0);
+  TRASE_LAUNCHES("vgg_pack", stream, 0, if ((rc = vg_launch_pack(vg_pack_spec(layers), weights, biases, nullptr, p, stream))) return rc);
   return TRASE_OK;
 }
 
@@ -768,26 +780,23 @@ int trase_vgg_forward(int32_t layers, const void* pack, size_t pack_bytes, const
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
   const VgNorm nm = vg_norm(mean, inv_std);
-  {
-    ProfScope ps(VG_FWD_NAMES[1], stream);
-    const dim3 grid((unsigned)(((size_t)H * W + 255) / 256));
+  const dim3 grid((unsigned)(((size_t)H * W + 255) / 256));
+  TRASE_LAUNCHES_AS(VG_FWD_NAMES[1], "vgg_fwd_conv1_1", stream, 0,
     if (k == 1)
       hipLaunchKernelGGL(vgg_conv1_kernel<true>, grid, dim3(256), 0, stream, image, H, W, nm, p.w1, p.bias[1], (__bf16*)nullptr,
                          (__bf16*)nullptr, out, (uint16_t*)nullptr);
     else
       hipLaunchKernelGGL(vgg_conv1_kernel<false>, grid, dim3(256), 0, stream, image, H, W, nm, p.w1, p.bias[1], b.hi[1], b.lo[1],
-                         (float*)nullptr, saved ? s.relu[1] : nullptr);
-  }
-  TRASE_POST_LAUNCH("vgg_fwd_conv1_1", stream, 0);
+                         (float*)nullptr, saved ? s.relu[1] : nullptr));
   for (int l = 2; l <= k; ++l) {
     VgConv a = vg_forward_conv(l, H, W, p);
     a.in_hi = b.hi[(l - 1) & 1]; a.in_lo = b.lo[(l - 1) & 1];
     a.out_hi = b.hi[l & 1]; a.out_lo = b.lo[l & 1];
-    ProfScope ps(VG_FWD_NAMES[l], stream);
-    if (l == k) { a.out_f32 = out; vg_launch_conv<VG_FWD_OUT>(a, stream); }
-    else if (vg_pooled(l)) { a.pool_codes = saved ? s.pool[l] : nullptr; vg_launch_conv<VG_FWD_POOL>(a, stream); }
-    else { a.relu_bits = saved ? s.relu[l] : nullptr; vg_launch_conv<VG_FWD_RELU>(a, stream); }
-    TRASE_POST_LAUNCH("vgg_fwd_conv", stream, 0);
+    TRASE_LAUNCHES_AS(VG_FWD_NAMES[l], "vgg_fwd_conv", stream, 0,
+      if (l == k) { a.out_f32 = out; rc = vg_launch_conv<VG_FWD_OUT>(a, stream); }
+      else if (vg_pooled(l)) { a.pool_codes = saved ? s.pool[l] : nullptr; rc = vg_launch_conv<VG_FWD_POOL>(a, stream); }
+      else { a.relu_bits = saved ? s.relu[l] : nullptr; rc = vg_launch_conv<VG_FWD_RELU>(a, stream); }
+      if (rc) return rc);
   }
   return TRASE_OK;
 }
@@ -807,42 +816,35 @@ int trase_vgg_backward(int32_t layers, const void* pack, size_t pack_bytes, cons
   if ((rc = vg_check_room(who, "saved buffer", saved_bytes, vg_saved_layout(const_cast<void*>(saved), k, H, W, s)))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  {
-    ProfScope ps("vgg_bwd_split", stream);
-    const int hw = (int)vg_pixels(k, H, W);
-    hipLaunchKernelGGL(vgg_cot_split_kernel, dim3((hw + 255) / 256, vg_chan(k) / 8), dim3(256), 0, stream, d_out, vg_chan(k), hw,
-                       b.hi[k & 1], b.lo[k & 1]);
-  }
-  TRASE_POST_LAUNCH("vgg_bwd_split", stream, 0);
+  const int hw = (int)vg_pixels(k, H, W);
+  TRASE_LAUNCH("vgg_bwd_split", stream, 0, vgg_cot_split_kernel, dim3((hw + 255) / 256, vg_chan(k) / 8), dim3(256), 0, d_out, vg_chan(k), hw,
+               b.hi[k & 1], b.lo[k & 1]);
   for (int l = k; l >= 2; --l) {                   // the cotangent of layer l's output -> that of layer l - 1's
     VgConv a{};                                    // not vg_forward_conv: Cin and Cout are exchanged and there is no bias
     a.in_hi = b.hi[l & 1]; a.in_lo = b.lo[l & 1];
     a.stream = p.bwd[l]; a.bias = nullptr;
     a.H = H >> vg_shift(l); a.W = W >> vg_shift(l); a.Cin = vg_chan(l); a.Cout = vg_chan(l - 1); a.lg_steps = vg_lg(a.Cin / 16);
     a.out_hi = b.hi[(l - 1) & 1]; a.out_lo = b.lo[(l - 1) & 1];
-    ProfScope ps(VG_BWD_NAMES[l], stream);
-    if (vg_pooled(l - 1)) {
-      a.out_H = H >> vg_shift(l - 1); a.out_W = W >> vg_shift(l - 1);
-      if ((a.out_H | a.out_W) & 1) {               // an odd last row / column lies in no window
-        const size_t bytes = vg_pixels(l - 1, H, W) * vg_chan(l - 1) * sizeof(__bf16);
-        rc = launch_zero_bytes(a.out_hi, bytes, stream); if (rc) return rc;
-        rc = launch_zero_bytes(a.out_lo, bytes, stream); if (rc) return rc;
+    TRASE_LAUNCHES_AS(VG_BWD_NAMES[l], "vgg_bwd_conv", stream, 0,
+      if (vg_pooled(l - 1)) {
+        a.out_H = H >> vg_shift(l - 1); a.out_W = W >> vg_shift(l - 1);
+        if ((a.out_H | a.out_W) & 1) {               // an odd last row / column lies in no window
+          const size_t bytes = vg_pixels(l - 1, H, W) * vg_chan(l - 1) * sizeof(__bf16);
+          rc = launch_zero_bytes(a.out_hi, bytes, stream); if (rc) return rc;
+          rc = launch_zero_bytes(a.out_lo, bytes, stream); if (rc) return rc;
+        }
+        a.pool_codes = const_cast<uint64_t*>(s.pool[l - 1]);
+        rc = vg_launch_conv<VG_BWD_UNPOOL>(a, stream);
+      } else {
+        a.relu_bits = const_cast<uint16_t*>(s.relu[l - 1]);
+        rc = vg_launch_conv<VG_BWD_MASK>(a, stream);
       }
-      a.pool_codes = const_cast<uint64_t*>(s.pool[l - 1]);
-      vg_launch_conv<VG_BWD_UNPOOL>(a, stream);
-    } else {
-      a.relu_bits = const_cast<uint16_t*>(s.relu[l - 1]);
-      vg_launch_conv<VG_BWD_MASK>(a, stream);
-    }
-    TRASE_POST_LAUNCH("vgg_bwd_conv", stream, 0);
+      if (rc) return rc);
   }
-  {
-    ProfScope ps(VG_BWD_NAMES[1], stream);
-    const VgNorm nm = vg_norm(nullptr, inv_std);
+  const VgNorm nm = vg_norm(nullptr, inv_std);
+  TRASE_LAUNCHES_AS(VG_BWD_NAMES[1], "vgg_bwd_conv1_1", stream, 0,
     hipLaunchKernelGGL(vgg_image_grad_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, stream, b.hi[1], b.lo[1], H, W, nm,
-                       (const float4*)p.w1t, d_image);
-  }
-  TRASE_POST_LAUNCH("vgg_bwd_conv1_1", stream, 0);
+                       (const float4*)p.w1t, d_image));
   return TRASE_OK;
 }
 
@@ -871,9 +873,7 @@ int trase_lpips_pack(const float* const* weights, const float* const* biases, co
   if ((rc = vg_check_room(who, "pack buffer", pack_bytes, vg_pack_layout(pack, LP_PACK_SPEC, p)))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  ProfScope ps("lpips_pack", stream);
-  vg_launch_pack(LP_PACK_SPEC, weights, biases, lin, p, stream);
-  TRASE_POST_LAUNCH("lpips_pack", stream, 0);
+  TRASE_LAUNCHES("lpips_pack", stream, 0, if ((rc = vg_launch_pack(LP_PACK_SPEC, weights, biases, lin, p, stream))) return rc);
   return TRASE_OK;
 }
 
@@ -906,8 +906,7 @@ int trase_lpips_forward(const void* pack, size_t pack_bytes, const float* x, con
   size_t map_off = 0, tap_off = 0;
   for (int l = 1; l <= VG_LAYERS; ++l) {
     const int h = H >> vg_shift(l), w = W >> vg_shift(l), hw = h * w, c = vg_chan(l);
-    {
-      ProfScope ps(LP_CONV_NAMES[l], stream);
+    TRASE_LAUNCHES_AS(LP_CONV_NAMES[l], "lpips_conv", stream, 0,
       for (int im = 0; im < 2; ++im) {
         if (l == 1) {
           cur[im] = Planes{b.hi[im], b.lo[im]};
@@ -918,16 +917,13 @@ int trase_lpips_forward(const void* pack, size_t pack_bytes, const float* x, con
           VgConv a = vg_forward_conv(l, H, W, p);
           a.in_hi = cur[im].hi; a.in_lo = cur[im].lo;
           a.out_hi = dst.hi; a.out_lo = dst.lo;
-          vg_launch_conv<VG_FWD_RELU>(a, stream);
+          if ((rc = vg_launch_conv<VG_FWD_RELU>(a, stream))) return rc;
           cur[im] = dst;
         }
-      }
-    }
-    TRASE_POST_LAUNCH("lpips_conv", stream, 0);
+      });
     if (l > 2) deep = 3 - deep;
     if (l != LP_TAP_LAYER[tap]) continue;
-    {
-      ProfScope ps(LP_HEAD_NAMES[tap], stream);
+    TRASE_LAUNCHES_AS(LP_HEAD_NAMES[tap], "lpips_head", stream, 0,
       hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)((hw + 31) / 32)), dim3(256), 0, stream, cur[0].hi, cur[0].lo, cur[1].hi, cur[1].lo, c,
                          hw, p.lin[tap], map_base + map_off);
       for (int im = 0; im < 2; ++im) {
@@ -941,19 +937,13 @@ int trase_lpips_forward(const void* pack, size_t pack_bytes, const float* x, con
                              dst.lo);
           cur[im] = dst;
         }
-      }
-    }
-    TRASE_POST_LAUNCH("lpips_head", stream, 0);
+      });
     means.map[tap] = map_base + map_off; means.n[tap] = hw;
     map_off += (size_t)hw; tap_off += (size_t)hw * c;
     if (vg_pooled(l)) deep = l == 2 ? 1 : 3 - deep;
     ++tap;
   }
-  {
-    ProfScope ps("lpips_mean", stream);
-    lp_launch_means(means, LP_TAPS, b.parts, out_layers, stream);
-  }
-  TRASE_POST_LAUNCH("lpips_mean", stream, 0);
+  TRASE_LAUNCHES("lpips_mean", stream, 0, if ((rc = lp_launch_means(means, LP_TAPS, b.parts, out_layers, stream))) return rc);
   return TRASE_OK;
 }
 
@@ -971,16 +961,15 @@ int trase_lpips_head(const float* a, const float* b, const float* lin, int32_t C
   if ((rc = vg_check_room(who, "workspace", ws_bytes, lp_head_layout(ws, C, hw, w)))) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   TRASE_CHECK(hipSetDevice(device));
-  ProfScope ps("lpips_head", stream);
   const float* in[2] = {a, b};
-  for (int im = 0; im < 2; ++im)
-    hipLaunchKernelGGL(vgg_cot_split_kernel, dim3((hw + 255) / 256, C / 8), dim3(256), 0, stream, in[im], C, hw, w.hi[im], w.lo[im]);
   float* const m = map ? map : w.map;
-  hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)((hw + 31) / 32)), dim3(256), 0, stream, w.hi[0], w.lo[0], w.hi[1], w.lo[1], C, hw, lin, m);
   LpMeans means{};
   means.map[0] = m; means.n[0] = hw;
-  lp_launch_means(means, 1, w.parts, out_layer, stream);
-  TRASE_POST_LAUNCH("lpips_head", stream, 0);
+  TRASE_LAUNCHES("lpips_head", stream, 0,
+    for (int im = 0; im < 2; ++im)
+      hipLaunchKernelGGL(vgg_cot_split_kernel, dim3((hw + 255) / 256, C / 8), dim3(256), 0, stream, in[im], C, hw, w.hi[im], w.lo[im]);
+    hipLaunchKernelGGL(lpips_head_kernel, dim3((unsigned)((hw + 31) / 32)), dim3(256), 0, stream, w.hi[0], w.lo[0], w.hi[1], w.lo[1], C, hw, lin, m);
+    if ((rc = lp_launch_means(means, 1, w.parts, out_layer, stream))) return rc);
   return TRASE_OK;
 }
 
