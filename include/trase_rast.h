@@ -342,6 +342,42 @@ int trase_knn_points(const float* p1, int32_t N1, const float* p2, int32_t N2, i
 int trase_graph_reverse_ws_bytes(int32_t N, int32_t k, size_t* ws_bytes);
 int trase_graph_reverse(const int32_t* idx, int32_t N, int32_t k, int32_t* rev_ranges, int32_t* rev_edges, void* ws,
                         size_t ws_bytes, int32_t device, trase_stream_t stream);
+/* The same transpose for a graph whose `rows` source rows point into `targets` target rows (rows, targets >= 1, rows*k < 2^31):
+ * rev_ranges is (targets,2), rev_edges (rows*k); an id outside [0,targets) is an edge to nowhere.  With rows == targets the
+ * results are those of trase_graph_reverse bit for bit. */
+int trase_graph_reverse_to_ws_bytes(int32_t rows, int32_t k, int32_t targets, size_t* ws_bytes);
+int trase_graph_reverse_to(const int32_t* idx, int32_t rows, int32_t k, int32_t targets, int32_t* rev_ranges, int32_t* rev_edges,
+                           void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+/* Exact all-pairs top-k at both ends of the distance order without the M x N matrix (dense.hip): for every row of queries (M,D)
+ * the k_near nearest and the k_far farthest rows of points (N,D), fp32, 1 <= D <= 64, 0 <= k_near, k_far <= 32 with one of them
+ * positive and both <= N.  A squared distance is the chain s = fmaf(q_d - p_d, q_d - p_d, s) in dimension order; a NaN becomes
+ * 0x7FC00000.  Near end: ascending (bits(d2) << 32) | id; far end: ascending (~bits(d2) << 32) | id (larger distance first, then
+ * lower id); NaN ranks above +inf.  Outputs (M,k) fp32 squared distances and int64 ids; an end with k = 0 takes null pointers.
+ * M = 0 launches nothing.  splits (may be null) receives the number of column ranges S; with S > 1 a merge launch follows. */
+int trase_dense_topk_ws_bytes(int32_t M, int32_t N, int32_t D, int32_t k_near, int32_t k_far, size_t* ws_bytes, int32_t* splits);
+int trase_dense_topk(const float* queries, int32_t M, const float* points, int32_t N, int32_t D, int32_t k_near, int32_t k_far,
+                     float* near_d2, int64_t* near_idx, float* far_d2, int64_t* far_idx, void* ws, size_t ws_bytes, int32_t device,
+                     trase_stream_t stream);
+/* loss_feature3d: lambda_p mean over (i, slot < kp) of sigmoid(1 - c) + lambda_n mean over (i, slot >= kp) of sigmoid(c) with
+ * c = u_i . u_j, u = f / max(|f|, 1e-8), j = idx[i,slot], idx (rows, kp + kn) int32: the kp nearest rows, then the kn farthest.
+ * The forward writes u_tab (rows, DP), DP = 8 / 16 / 32 / 64 the padded D, and nrm (rows) for the backward, which also reads the
+ * transpose of idx; loss and g_loss are device scalars.  1 <= rows < 2^25, D <= 64, 1 <= kp, kn <= 32. */
+int trase_feature3d_ws_bytes(int32_t rows, size_t* ws_bytes);
+int trase_feature3d_forward(const float* feats, const int32_t* idx, int32_t rows, int32_t D, int32_t kp, int32_t kn, float lambda_p,
+                            float lambda_n, float* u_tab, float* nrm, float* loss, void* ws, size_t ws_bytes, int32_t device,
+                            trase_stream_t stream);
+int trase_feature3d_backward(const float* u_tab, const float* nrm, const int32_t* idx, const int32_t* rev_ranges,
+                             const int32_t* rev_edges, int32_t rows, int32_t D, int32_t kp, int32_t kn, float lambda_p, float lambda_n,
+                             const float* g_loss, float* g_feats, int32_t device, trase_stream_t stream);
+/* loss_cls_3d: lambda / (S k C) sum over (s,slot,c) of p_s (log(p_s + 1e-10) - log(p_j + 1e-10)), p_s = pred[sample[s]], pred (N,C),
+ * C <= 256, sample (S) and idx (S,k) int32 row numbers of pred.  The backward writes g_pred (N,C) from the transposes of idx
+ * (rev_*: S rows into N targets) and of sample as an (S,1) graph (srev_*). */
+int trase_cls3d_ws_bytes(int32_t S, int32_t C, size_t* ws_bytes);
+int trase_cls3d_forward(const float* pred, const int32_t* sample, const int32_t* idx, int32_t S, int32_t N, int32_t C, int32_t k,
+                        float lambda_val, float* loss, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+int trase_cls3d_backward(const float* pred, const int32_t* sample, const int32_t* idx, const int32_t* rev_ranges, const int32_t* rev_edges,
+                         const int32_t* srev_ranges, const int32_t* srev_edges, int32_t S, int32_t N, int32_t C, int32_t k,
+                         float lambda_val, const float* g_loss, float* g_pred, int32_t device, trase_stream_t stream);
 /* loss = mean over (i,slot,d) of s_i (log(s_i + 1e-10) - log(s_j + 1e-10)), s = sigmoid(feats), feats (N,D), D <= 64.
  * The forward writes the tables s_tab, l_tab (N,D each) that the backward reads; loss and g_loss are device scalars.
  * Workspace: trase_feat3d_ws_bytes(N, D). */

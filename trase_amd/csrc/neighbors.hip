@@ -19,12 +19,13 @@ static int rev_bits(int N) {
   while ((1u << bits) < (uint32_t)N + 1u) ++bits;      // keys 0 .. N (N = "no such row")
   return bits;
 }
-static size_t rev_layout(void* ws, int N, int k, RevWs& w) {
+// rows source rows of k edges each into `targets` target rows (the square graph: targets == rows)
+static size_t rev_layout(void* ws, int rows, int k, int targets, RevWs& w) {
   WsCursor c(ws);
-  const size_t M = (size_t)N * (size_t)k;
+  const size_t M = (size_t)rows * (size_t)k;
   w.n = c.take<uint32_t>(1);
   sort_layout(c, w.sort, M > 0 ? M : 1, SORT_ALL, 8, 1);
-  w.ranges = c.take<uint2>((size_t)N + 1);
+  w.ranges = c.take<uint2>((size_t)targets + 1);
   return c.bytes();
 }
 
@@ -381,6 +382,174 @@ __global__ __launch_bounds__(256) void rigid_fit_bwd_kernel(const float* __restr
   g2[3 * (size_t)i] = o2.x; g2[3 * (size_t)i + 1] = o2.y; g2[3 * (size_t)i + 2] = o2.z;
 }
 
+// ---- loss_feature3d (utils/loss_utils.py:154-175) ------------------------------------------------------------------------------
+//   loss = lambda_p mean over (i, slot < kp) of sigmoid(1 - c) + lambda_n mean over (i, slot >= kp) of sigmoid(c),
+//   c = u_i . u_j, u = f / max(|f|, 1e-8), j = idx[i, slot]: idx (rows, kp + kn) holds the kp nearest rows, then the kn farthest.
+// The table pass writes u zero padded to DP = 8 / 16 / 32 / 64 columns (float4 reads, no tail) and the clamped norms; forward
+// and backward are one thread per row with u_i in registers.  The backward accumulates g_u[i] = sum over the row's own slots of
+// w_e u_j + sum over the edges that point at i, in ascending edge order, of w_e u_src with w_e = d loss / d c_e (the dot product
+// is recomputed there), then applies the chain of the normalisation.
+constexpr float FC_EPS = 1e-8f;
+constexpr int FC_MAX_K = 32;
+static inline int fc_dpad(int D) { return D <= 8 ? 8 : D <= 16 ? 16 : D <= 32 ? 32 : 64; }
+__device__ __forceinline__ float fc_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+__global__ __launch_bounds__(256) void fc_table_kernel(const float* __restrict__ f, uint32_t rows, uint32_t D, uint32_t DP,
+                                                       float* __restrict__ u_tab, float* __restrict__ nrm) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= rows) return;
+  const float* fi = f + (size_t)i * D;
+  float n2 = 0.f;
+  for (uint32_t d = 0; d < D; ++d) n2 = fmaf(fi[d], fi[d], n2);
+  const float n = fmaxf(sqrtf(n2), FC_EPS);
+  nrm[i] = n;
+  for (uint32_t d = 0; d < DP; ++d) u_tab[(size_t)i * DP + d] = d < D ? fi[d] / n : 0.f;
+}
+
+template <int DP>
+__device__ __forceinline__ void fc_load(const float* __restrict__ u_tab, uint32_t i, float (&u)[DP]) {
+  const float4* p = reinterpret_cast<const float4*>(u_tab + (size_t)i * DP);
+#pragma unroll
+  for (int q = 0; q < DP / 4; ++q) { const float4 v = p[q]; u[4 * q] = v.x; u[4 * q + 1] = v.y; u[4 * q + 2] = v.z; u[4 * q + 3] = v.w; }
+}
+template <int DP>
+__device__ __forceinline__ float fc_dot(const float (&u)[DP], const float* __restrict__ u_tab, uint32_t j) {
+  const float4* p = reinterpret_cast<const float4*>(u_tab + (size_t)j * DP);
+  float c = 0.f;
+#pragma unroll
+  for (int q = 0; q < DP / 4; ++q) {
+    const float4 v = p[q];
+    c = fmaf(u[4 * q], v.x, c); c = fmaf(u[4 * q + 1], v.y, c); c = fmaf(u[4 * q + 2], v.z, c); c = fmaf(u[4 * q + 3], v.w, c);
+  }
+  return c;
+}
+template <int DP>
+__device__ __forceinline__ void fc_axpy(float w, const float* __restrict__ u_tab, uint32_t j, float (&g)[DP]) {
+  const float4* p = reinterpret_cast<const float4*>(u_tab + (size_t)j * DP);
+#pragma unroll
+  for (int q = 0; q < DP / 4; ++q) {
+    const float4 v = p[q];
+    g[4 * q] = fmaf(w, v.x, g[4 * q]); g[4 * q + 1] = fmaf(w, v.y, g[4 * q + 1]);
+    g[4 * q + 2] = fmaf(w, v.z, g[4 * q + 2]); g[4 * q + 3] = fmaf(w, v.w, g[4 * q + 3]);
+  }
+}
+// d loss / d c of one edge: a near edge is sigmoid(1 - c) * wp, a far edge sigmoid(c) * wn
+__device__ __forceinline__ float fc_weight(float c, bool near_edge, float wp, float wn) {
+  const float s = fc_sigmoid(near_edge ? 1.0f - c : c);
+  return (near_edge ? -wp : wn) * (s * (1.0f - s));
+}
+
+template <int DP>
+__global__ __launch_bounds__(256) void fc_forward_kernel(const float* __restrict__ u_tab, const int32_t* __restrict__ idx, uint32_t rows,
+                                                         uint32_t kp, uint32_t kn, double wp, double wn, double* __restrict__ partial) {
+  __shared__ double sh[256];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x, kt = kp + kn;
+  double v = 0.0;
+  if (i < rows) {
+    float u[DP];
+    fc_load<DP>(u_tab, i, u);
+    float a = 0.f, b = 0.f;
+    for (uint32_t slot = 0; slot < kt; ++slot) {
+      const uint32_t j = (uint32_t)idx[(size_t)i * kt + slot];
+      if (j >= rows) continue;
+      const float c = fc_dot<DP>(u, u_tab, j);
+      if (slot < kp) a += fc_sigmoid(1.0f - c); else b += fc_sigmoid(c);
+    }
+    v = wp * (double)a + wn * (double)b;
+  }
+  const double tot = block_sum_256(v, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+template <int DP>
+__global__ __launch_bounds__(256) void fc_backward_kernel(const float* __restrict__ u_tab, const float* __restrict__ nrm,
+                                                          const int32_t* __restrict__ idx, const int32_t* __restrict__ rev_ranges,
+                                                          const int32_t* __restrict__ rev_edges, uint32_t rows, uint32_t D, uint32_t kp,
+                                                          uint32_t kn, float wp, float wn, const float* __restrict__ g_loss,
+                                                          float* __restrict__ g_f) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x, kt = kp + kn;
+  if (i >= rows) return;
+  float u[DP], g[DP];
+  fc_load<DP>(u_tab, i, u);
+#pragma unroll
+  for (int d = 0; d < DP; ++d) g[d] = 0.f;
+  for (uint32_t slot = 0; slot < kt; ++slot) {
+    const uint32_t j = (uint32_t)idx[(size_t)i * kt + slot];
+    if (j >= rows) continue;
+    fc_axpy<DP>(fc_weight(fc_dot<DP>(u, u_tab, j), slot < kp, wp, wn), u_tab, j, g);
+  }
+  const uint32_t e0 = (uint32_t)rev_ranges[2 * (size_t)i], e1 = (uint32_t)rev_ranges[2 * (size_t)i + 1];
+  for (uint32_t q = e0; q < e1; ++q) {
+    const uint32_t e = (uint32_t)rev_edges[q], src = e / kt, slot = e - src * kt;
+    fc_axpy<DP>(fc_weight(fc_dot<DP>(u, u_tab, src), slot < kp, wp, wn), u_tab, src, g);
+  }
+  float ug = 0.f;
+#pragma unroll
+  for (int d = 0; d < DP; ++d) ug = fmaf(u[d], g[d], ug);
+  const float n = nrm[i], gl = *g_loss;
+  const bool clamped = !(n > FC_EPS);
+#pragma unroll
+  for (int d = 0; d < DP; ++d)
+    if ((uint32_t)d < D) g_f[(size_t)i * D + d] = gl * (clamped ? g[d] / FC_EPS : (g[d] - u[d] * ug) / n);
+}
+
+// ---- loss_cls_3d (utils/loss_utils.py:89-130) -----------------------------------------------------------------------------------
+//   loss = lambda / (S k C) sum over (s, slot, c) of p_s (log(p_s + 1e-10) - log(p_j + 1e-10)), p_s = pred[sample[s]],
+//   j = idx[s, slot] the k nearest rows of sample[s] in feature space.  The gradient goes to pred (N, C): a sampled row gets its
+//   direct term (found through the transpose of `sample` as an (S, 1) graph, so a row sampled twice sums in a fixed order),
+//   every neighbour row -w p_s / (p_j + 1e-10) gathered over the transpose of idx.
+constexpr int CL_MAX_C = 256;
+__global__ __launch_bounds__(256) void cls_forward_kernel(const float* __restrict__ pred, const int32_t* __restrict__ sample,
+                                                          const int32_t* __restrict__ idx, uint32_t S, uint32_t N, uint32_t C, uint32_t k,
+                                                          double* __restrict__ partial) {
+  __shared__ double sh[256];
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  float v = 0.f;
+  if (t < S * C) {
+    const uint32_t s = t / C, c = t - s * C, r = (uint32_t)sample[s];
+    if (r < N) {
+      const float p = pred[(size_t)r * C + c], lp = logf(p + F3_EPS);
+      float a = 0.f;
+      for (uint32_t slot = 0; slot < k; ++slot) {
+        const uint32_t j = (uint32_t)idx[(size_t)s * k + slot];
+        if (j < N) a += lp - logf(pred[(size_t)j * C + c] + F3_EPS);
+      }
+      v = p * a;
+    }
+  }
+  const double tot = block_sum_256((double)v, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void cls_backward_kernel(const float* __restrict__ pred, const int32_t* __restrict__ sample,
+                                                           const int32_t* __restrict__ idx, const int32_t* __restrict__ rev_ranges,
+                                                           const int32_t* __restrict__ rev_edges, const int32_t* __restrict__ srev_ranges,
+                                                           const int32_t* __restrict__ srev_edges, uint32_t N, uint32_t C, uint32_t k,
+                                                           const float* __restrict__ g_loss, float w, float* __restrict__ g_pred) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= N * C) return;
+  const uint32_t n = t / C, c = t - n * C;
+  const float p = pred[t];
+  float g = 0.f;
+  const uint32_t s0 = (uint32_t)srev_ranges[2 * (size_t)n], s1 = (uint32_t)srev_ranges[2 * (size_t)n + 1];
+  if (s0 < s1) {
+    const float lp = logf(p + F3_EPS), self = p / (p + F3_EPS);
+    for (uint32_t q = s0; q < s1; ++q) {
+      const uint32_t s = (uint32_t)srev_edges[q];
+      for (uint32_t slot = 0; slot < k; ++slot) {
+        const uint32_t j = (uint32_t)idx[(size_t)s * k + slot];
+        if (j < N) g += (lp - logf(pred[(size_t)j * C + c] + F3_EPS)) + self;
+      }
+    }
+  }
+  const uint32_t e0 = (uint32_t)rev_ranges[2 * (size_t)n], e1 = (uint32_t)rev_ranges[2 * (size_t)n + 1];
+  for (uint32_t q = e0; q < e1; ++q) {
+    const uint32_t r = (uint32_t)sample[(uint32_t)rev_edges[q] / k];
+    if (r < N) g -= pred[(size_t)r * C + c] / (p + F3_EPS);
+  }
+  g_pred[t] = (*g_loss * w) * g;
+}
+
 // the size rules every entry point shares: N >= 0, 1 <= k, N * k < 2^31
 static int graph_dims_ok(const char* who, int32_t N, int32_t k) {
   if (N < 0 || k < 1 || (int64_t)N * (int64_t)k >= ((int64_t)1 << 31)) {
@@ -390,6 +559,36 @@ static int graph_dims_ok(const char* who, int32_t N, int32_t k) {
   return TRASE_OK;
 }
 static inline int blocks_of(uint32_t n) { return (int)((n + 255u) / 256u); }
+static int graph_to_dims_ok(const char* who, int32_t rows, int32_t k, int32_t targets) {
+  if (int rc = graph_dims_ok(who, rows, k)) return rc;
+  if (rows < 1 || targets < 1 || targets == INT32_MAX) {
+    set_error("%s: need rows >= 1 and 1 <= targets < 2^31 - 1 (got rows %d, targets %d)", who, rows, targets);
+    return TRASE_ERR_INVALID;
+  }
+  return TRASE_OK;
+}
+
+// the transpose of idx (rows, k) over `targets` target rows (arguments checked by the caller): the stable radix sort of the
+// edges by target, the ranges of every target, then rev_edges (rows * k) and rev_ranges (targets, 2)
+static int graph_reverse(const char* who, const int32_t* idx, int32_t rows, int32_t k, int32_t targets, int32_t* rev_ranges,
+                         int32_t* rev_edges, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  RevWs w;
+  if (!ws || ws_bytes < rev_layout(nullptr, rows, k, targets, w)) { set_error("%s: workspace too small", who); return TRASE_ERR_WORKSPACE; }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  rev_layout(ws, rows, k, targets, w);
+  LaunchCtx c{stream, 0, 0};
+  const uint32_t M = (uint32_t)rows * (uint32_t)k, T = (uint32_t)targets;
+  TRASE_LAUNCH("graph_rev_keys", stream, 0, rev_keys_kernel, dim3(blocks_of(M)), dim3(256), 0, idx, M, T, w.sort.keys[0], w.n);
+  int out = 0;
+  int rc = radix_sort_pairs(c, w.sort, w.n, M, 0, rev_bits(targets), true, &out);
+  if (rc) return rc;
+  rc = launch_tile_ranges(c, w.sort.keys[out], w.n, M, w.ranges, targets + 1);
+  if (rc) return rc;
+  TRASE_LAUNCH("graph_rev_finish", stream, 0, rev_finish_kernel, dim3(blocks_of(M > T ? M : T)), dim3(256), 0, w.sort.vals[out], w.ranges, M,
+               T, rev_edges, rev_ranges);
+  return TRASE_OK;
+}
 
 }  // namespace trase
 
@@ -401,7 +600,7 @@ int trase_graph_reverse_ws_bytes(int32_t N, int32_t k, size_t* ws_bytes) {
   if (!ws_bytes) { set_error("trase_graph_reverse_ws_bytes: null pointer"); return TRASE_ERR_INVALID; }
   if (int rc = graph_dims_ok("trase_graph_reverse_ws_bytes", N, k)) return rc;
   RevWs w;
-  *ws_bytes = rev_layout(nullptr, N, k, w);
+  *ws_bytes = rev_layout(nullptr, N, k, N, w);
   return TRASE_OK;
 }
 
@@ -410,22 +609,22 @@ int trase_graph_reverse(const int32_t* idx, int32_t N, int32_t k, int32_t* rev_r
   if (int rc = graph_dims_ok("trase_graph_reverse", N, k)) return rc;
   if (N == 0) return TRASE_OK;
   if (!idx || !rev_ranges || !rev_edges) { set_error("trase_graph_reverse: null pointer"); return TRASE_ERR_INVALID; }
+  return graph_reverse("trase_graph_reverse", idx, N, k, N, rev_ranges, rev_edges, ws, ws_bytes, device, stream_);
+}
+
+int trase_graph_reverse_to_ws_bytes(int32_t rows, int32_t k, int32_t targets, size_t* ws_bytes) {
+  if (!ws_bytes) { set_error("trase_graph_reverse_to_ws_bytes: null pointer"); return TRASE_ERR_INVALID; }
+  if (int rc = graph_to_dims_ok("trase_graph_reverse_to_ws_bytes", rows, k, targets)) return rc;
   RevWs w;
-  if (!ws || ws_bytes < rev_layout(nullptr, N, k, w)) { set_error("trase_graph_reverse: workspace too small"); return TRASE_ERR_WORKSPACE; }
-  hipStream_t stream = (hipStream_t)stream_;
-  TRASE_CHECK(hipSetDevice(device));
-  rev_layout(ws, N, k, w);
-  LaunchCtx c{stream, 0, 0};
-  const uint32_t M = (uint32_t)N * (uint32_t)k;
-  TRASE_LAUNCH("graph_rev_keys", stream, 0, rev_keys_kernel, dim3(blocks_of(M)), dim3(256), 0, idx, M, (uint32_t)N, w.sort.keys[0], w.n);
-  int out = 0;
-  int rc = radix_sort_pairs(c, w.sort, w.n, M, 0, rev_bits(N), true, &out);
-  if (rc) return rc;
-  rc = launch_tile_ranges(c, w.sort.keys[out], w.n, M, w.ranges, N + 1);
-  if (rc) return rc;
-  TRASE_LAUNCH("graph_rev_finish", stream, 0, rev_finish_kernel, dim3(blocks_of(M > (uint32_t)N ? M : (uint32_t)N)), dim3(256), 0, w.sort.vals[out],
-               w.ranges, M, (uint32_t)N, rev_edges, rev_ranges);
+  *ws_bytes = rev_layout(nullptr, rows, k, targets, w);
   return TRASE_OK;
+}
+
+int trase_graph_reverse_to(const int32_t* idx, int32_t rows, int32_t k, int32_t targets, int32_t* rev_ranges, int32_t* rev_edges,
+                           void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  if (int rc = graph_to_dims_ok("trase_graph_reverse_to", rows, k, targets)) return rc;
+  if (!idx || !rev_ranges || !rev_edges) { set_error("trase_graph_reverse_to: null pointer"); return TRASE_ERR_INVALID; }
+  return graph_reverse("trase_graph_reverse_to", idx, rows, k, targets, rev_ranges, rev_edges, ws, ws_bytes, device, stream_);
 }
 
 static int f3_dims_ok(const char* who, int32_t N, int32_t D, int32_t k) {
@@ -583,6 +782,126 @@ int trase_rigid_fit_backward(const float* p1, const float* p2, const int32_t* id
   // (the row's own edges come from the saved sums: idx is not walked)
   TRASE_LAUNCH("rigid_fit_bwd", stream, 0, rigid_fit_bwd_kernel, dim3(blocks_of((uint32_t)N)), dim3(256), 0, p1, p2, rev_ranges, rev_edges, R,
                state, g, (uint32_t)N, (uint32_t)k, g1, g2);
+  return TRASE_OK;
+}
+
+static int fc_dims_ok(const char* who, int32_t rows, int32_t D, int32_t kp, int32_t kn) {
+  if (rows < 1 || D < 1 || D > F3_MAX_D || kp < 1 || kp > FC_MAX_K || kn < 1 || kn > FC_MAX_K || rows > (INT32_MAX >> 6)) {
+    set_error("%s: need 1 <= rows < 2^25, 1 <= D <= %d, 1 <= kp, kn <= %d (got rows %d, D %d, kp %d, kn %d)", who, F3_MAX_D, FC_MAX_K,
+              rows, D, kp, kn);
+    return TRASE_ERR_INVALID;
+  }
+  return TRASE_OK;
+}
+
+int trase_feature3d_ws_bytes(int32_t rows, size_t* ws_bytes) {
+  if (!ws_bytes) { set_error("trase_feature3d_ws_bytes: null pointer"); return TRASE_ERR_INVALID; }
+  if (int rc = fc_dims_ok("trase_feature3d_ws_bytes", rows, 1, 1, 1)) return rc;
+  double* p;
+  *ws_bytes = array_layout<double>(nullptr, (size_t)blocks_of((uint32_t)rows) + 1, p);
+  return TRASE_OK;
+}
+
+int trase_feature3d_forward(const float* feats, const int32_t* idx, int32_t rows, int32_t D, int32_t kp, int32_t kn, float lambda_p,
+                            float lambda_n, float* u_tab, float* nrm, float* loss, void* ws, size_t ws_bytes, int32_t device,
+                            trase_stream_t stream_) {
+  if (int rc = fc_dims_ok("trase_feature3d_forward", rows, D, kp, kn)) return rc;
+  if (!feats || !idx || !u_tab || !nrm || !loss) { set_error("trase_feature3d_forward: null pointer"); return TRASE_ERR_INVALID; }
+  const int nb = blocks_of((uint32_t)rows), dp = fc_dpad(D);
+  double* partial;
+  if (!ws || ws_bytes < array_layout<double>(nullptr, (size_t)nb + 1, partial)) {
+    set_error("trase_feature3d_forward: workspace too small"); return TRASE_ERR_WORKSPACE;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  array_layout<double>(ws, (size_t)nb + 1, partial);
+  const double wp = (double)lambda_p / ((double)rows * kp), wn = (double)lambda_n / ((double)rows * kn);
+#define TRASE_FC_FWD(DPV) hipLaunchKernelGGL((fc_forward_kernel<DPV>), dim3(nb), dim3(256), 0, stream, u_tab, idx, (uint32_t)rows, \
+                                             (uint32_t)kp, (uint32_t)kn, wp, wn, partial)
+  TRASE_LAUNCHES("feature3d_forward", stream, 0,
+    hipLaunchKernelGGL(fc_table_kernel, dim3(nb), dim3(256), 0, stream, feats, (uint32_t)rows, (uint32_t)D, (uint32_t)dp, u_tab, nrm);
+    if (dp == 8) TRASE_FC_FWD(8);
+    else if (dp == 16) TRASE_FC_FWD(16);
+    else if (dp == 32) TRASE_FC_FWD(32);
+    else TRASE_FC_FWD(64);
+    hipLaunchKernelGGL(f3_reduce_kernel, dim3(1), dim3(256), 0, stream, partial, (uint32_t)nb, 1.0, loss));
+#undef TRASE_FC_FWD
+  return TRASE_OK;
+}
+
+int trase_feature3d_backward(const float* u_tab, const float* nrm, const int32_t* idx, const int32_t* rev_ranges,
+                             const int32_t* rev_edges, int32_t rows, int32_t D, int32_t kp, int32_t kn, float lambda_p, float lambda_n,
+                             const float* g_loss, float* g_feats, int32_t device, trase_stream_t stream_) {
+  if (int rc = fc_dims_ok("trase_feature3d_backward", rows, D, kp, kn)) return rc;
+  if (!u_tab || !nrm || !idx || !rev_ranges || !rev_edges || !g_loss || !g_feats) {
+    set_error("trase_feature3d_backward: null pointer"); return TRASE_ERR_INVALID;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  const int nb = blocks_of((uint32_t)rows), dp = fc_dpad(D);
+  const float wp = (float)((double)lambda_p / ((double)rows * kp)), wn = (float)((double)lambda_n / ((double)rows * kn));
+#define TRASE_FC_BWD(DPV) hipLaunchKernelGGL((fc_backward_kernel<DPV>), dim3(nb), dim3(256), 0, stream, u_tab, nrm, idx, rev_ranges, \
+                                             rev_edges, (uint32_t)rows, (uint32_t)D, (uint32_t)kp, (uint32_t)kn, wp, wn, g_loss, g_feats)
+  TRASE_LAUNCHES("feature3d_backward", stream, 0,
+    if (dp == 8) TRASE_FC_BWD(8);
+    else if (dp == 16) TRASE_FC_BWD(16);
+    else if (dp == 32) TRASE_FC_BWD(32);
+    else TRASE_FC_BWD(64));
+#undef TRASE_FC_BWD
+  return TRASE_OK;
+}
+
+static int cls_dims_ok(const char* who, int32_t S, int32_t N, int32_t C, int32_t k) {
+  if (int rc = graph_dims_ok(who, S, k)) return rc;
+  if (S < 1 || N < 1 || N == INT32_MAX || C < 1 || C > CL_MAX_C || (int64_t)N * (int64_t)C >= ((int64_t)1 << 31) ||
+      (int64_t)S * (int64_t)C >= ((int64_t)1 << 31)) {
+    set_error("%s: need S >= 1, N >= 1, 1 <= C <= %d and S * C, N * C < 2^31 (got S %d, N %d, C %d)", who, CL_MAX_C, S, N, C);
+    return TRASE_ERR_INVALID;
+  }
+  return TRASE_OK;
+}
+
+int trase_cls3d_ws_bytes(int32_t S, int32_t C, size_t* ws_bytes) {
+  if (!ws_bytes) { set_error("trase_cls3d_ws_bytes: null pointer"); return TRASE_ERR_INVALID; }
+  if (int rc = cls_dims_ok("trase_cls3d_ws_bytes", S, S > 0 ? S : 1, C, 1)) return rc;
+  double* p;
+  *ws_bytes = array_layout<double>(nullptr, (size_t)blocks_of((uint32_t)S * (uint32_t)C) + 1, p);
+  return TRASE_OK;
+}
+
+int trase_cls3d_forward(const float* pred, const int32_t* sample, const int32_t* idx, int32_t S, int32_t N, int32_t C, int32_t k,
+                        float lambda_val, float* loss, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream_) {
+  if (int rc = cls_dims_ok("trase_cls3d_forward", S, N, C, k)) return rc;
+  if (S > N) { set_error("trase_cls3d_forward: need S <= N (got S %d, N %d)", S, N); return TRASE_ERR_INVALID; }
+  if (!pred || !sample || !idx || !loss) { set_error("trase_cls3d_forward: null pointer"); return TRASE_ERR_INVALID; }
+  const int nb = blocks_of((uint32_t)S * (uint32_t)C);
+  double* partial;
+  if (!ws || ws_bytes < array_layout<double>(nullptr, (size_t)nb + 1, partial)) {
+    set_error("trase_cls3d_forward: workspace too small"); return TRASE_ERR_WORKSPACE;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  array_layout<double>(ws, (size_t)nb + 1, partial);
+  TRASE_LAUNCHES("cls3d_forward", stream, 0,
+    hipLaunchKernelGGL(cls_forward_kernel, dim3(nb), dim3(256), 0, stream, pred, sample, idx, (uint32_t)S, (uint32_t)N, (uint32_t)C,
+                       (uint32_t)k, partial);
+    hipLaunchKernelGGL(f3_reduce_kernel, dim3(1), dim3(256), 0, stream, partial, (uint32_t)nb,
+                       (double)lambda_val / ((double)S * (double)k * (double)C), loss));
+  return TRASE_OK;
+}
+
+int trase_cls3d_backward(const float* pred, const int32_t* sample, const int32_t* idx, const int32_t* rev_ranges, const int32_t* rev_edges,
+                         const int32_t* srev_ranges, const int32_t* srev_edges, int32_t S, int32_t N, int32_t C, int32_t k,
+                         float lambda_val, const float* g_loss, float* g_pred, int32_t device, trase_stream_t stream_) {
+  if (int rc = cls_dims_ok("trase_cls3d_backward", S, N, C, k)) return rc;
+  if (!pred || !sample || !idx || !rev_ranges || !rev_edges || !srev_ranges || !srev_edges || !g_loss || !g_pred) {
+    set_error("trase_cls3d_backward: null pointer"); return TRASE_ERR_INVALID;
+  }
+  hipStream_t stream = (hipStream_t)stream_;
+  TRASE_CHECK(hipSetDevice(device));
+  TRASE_LAUNCH("cls3d_backward", stream, 0, cls_backward_kernel, dim3(blocks_of((uint32_t)N * (uint32_t)C)), dim3(256), 0, pred, sample, idx,
+               rev_ranges, rev_edges, srev_ranges, srev_edges, (uint32_t)N, (uint32_t)C, (uint32_t)k, g_loss,
+               (float)((double)lambda_val / ((double)S * (double)k * (double)C)), g_pred);
   return TRASE_OK;
 }
 

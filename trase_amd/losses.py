@@ -345,3 +345,5 @@ _NNFM_WARNED = False
 
 # the two k-NN graph losses of utils/loss_utils.py (:132-152, :179-221) live in trase_amd/neighbors.py
 from .neighbors import loss_reg_3d_feature, loss_rigid_body_motion_reg_loss, polar_rotation, rigid_fit  # noqa: E402,F401
+# the two dense-search losses (:154-175, :89-130) and their search too
+from .neighbors import dense_topk, loss_cls_3d, loss_feature3d  # noqa: E402,F401

@@ -9,7 +9,11 @@ the *neighbour* end of an edge -- no float atomics, so two calls give the same b
 ``edge_moments`` and ``edge_residual`` are the two edge sums of the rigid loss; by default the 3 x 3 SVD between them stays
 ``torch.svd`` with its own autograd, as in the reference.  ``polar_rotation`` is that rotation as a kernel with its closed-form
 gradient (trase_amd/csrc/rigid_math.h), ``rigid_fit`` the three steps in one launch each way, and
-``loss_rigid_body_motion_reg_loss(..., rotation="polar")`` the loss over it."""
+``loss_rigid_body_motion_reg_loss(..., rotation="polar")`` the loss over it.
+
+``dense_topk`` (trase_amd/csrc/dense.hip) is the exact all-pairs search at both ends of the distance order that never stores the
+M x N matrix; ``loss_feature3d`` (:154-175) and ``loss_cls_3d`` (:89-130) are the two losses of the reference that sit on
+``torch.cdist`` + ``topk``, here as gather kernels over its indices."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,6 +24,8 @@ from . import _lib
 from .rasterizer import _bytes, _stream, knn_points
 
 MAX_FEATURE_DIM = 64
+MAX_DENSE_K = 32
+MAX_CLASSES = 256
 
 
 def _dev_index(dev):
@@ -34,10 +40,15 @@ def _need_gpu(t, what):
 class NeighborGraph:
     """idx (N, k) int32 and its transpose: rev_edges (N * k) holds the edge numbers i * k + slot sorted by the row they point at,
     ascending among the edges of one row; rev_ranges (N, 2) the [begin, end) positions of every row's incoming edges.  An id
-    outside [0, N) is an edge to nowhere: it is in no range and contributes to no sum."""
+    outside [0, N) is an edge to nowhere: it is in no range and contributes to no sum.  With ``num_targets`` the N source rows
+    point into that many target rows instead: rev_ranges is (num_targets, 2) and the ids are valid in [0, num_targets)."""
 
     def __init__(self, idx, rev_ranges, rev_edges):
         self.idx, self.rev_ranges, self.rev_edges = idx, rev_ranges, rev_edges
+
+    @property
+    def num_targets(self):
+        return self.rev_ranges.shape[0]
 
     @property
     def N(self):
@@ -48,22 +59,33 @@ class NeighborGraph:
         return self.idx.shape[1]
 
     @classmethod
-    def from_idx(cls, idx: torch.Tensor) -> "NeighborGraph":
+    def from_idx(cls, idx: torch.Tensor, num_targets=None) -> "NeighborGraph":
         _need_gpu(idx, "NeighborGraph")
         if idx.dim() != 2 or idx.shape[1] < 1:
             raise ValueError("NeighborGraph: idx must be (N, k) with k >= 1")
         N, k = idx.shape
         if N * k >= 2 ** 31:
             raise ValueError(f"NeighborGraph: need N * k < 2^31 (got N {N}, k {k})")
+        if num_targets is not None and (N < 1 or not 1 <= int(num_targets) < 2 ** 31 - 1):
+            raise ValueError(f"NeighborGraph: with num_targets need N >= 1 and 1 <= num_targets < 2^31 - 1 (got N {N}, num_targets {num_targets})")
         if idx.dtype != torch.int32:
             big = torch.iinfo(torch.int32).max
             idx = idx.detach().clamp(-1, big).to(torch.int32)       # what does not fit is out of range either way
         idx = idx.detach().contiguous()
         dev = idx.device
-        rev_ranges = torch.empty(N, 2, dtype=torch.int32, device=dev)
-        rev_edges = torch.empty(N * k, dtype=torch.int32, device=dev)
         lib = _lib.load()
         nbytes = C.c_size_t()
+        if num_targets is not None:
+            T = int(num_targets)
+            rev_ranges = torch.empty(T, 2, dtype=torch.int32, device=dev)
+            rev_edges = torch.empty(N * k, dtype=torch.int32, device=dev)
+            _lib.check(lib.trase_graph_reverse_to_ws_bytes(N, k, T, C.byref(nbytes)), "trase_graph_reverse_to_ws_bytes")
+            ws = _bytes(nbytes.value, dev)
+            _lib.check(lib.trase_graph_reverse_to(_lib.ptr(idx), N, k, T, _lib.ptr(rev_ranges), _lib.ptr(rev_edges), _lib.ptr(ws),
+                                                  ws.numel(), _dev_index(dev), _stream(dev)), "trase_graph_reverse_to")
+            return cls(idx, rev_ranges, rev_edges)
+        rev_ranges = torch.empty(N, 2, dtype=torch.int32, device=dev)
+        rev_edges = torch.empty(N * k, dtype=torch.int32, device=dev)
         _lib.check(lib.trase_graph_reverse_ws_bytes(N, k, C.byref(nbytes)), "trase_graph_reverse_ws_bytes")
         ws = _bytes(nbytes.value, dev)
         _lib.check(lib.trase_graph_reverse(_lib.ptr(idx), N, k, _lib.ptr(rev_ranges), _lib.ptr(rev_edges), _lib.ptr(ws),
@@ -339,3 +361,216 @@ def loss_rigid_body_motion_reg_loss(xyz1, xyz2, cluster_ids, num_neighbors=128, 
             if p.requires_grad:
                 p.register_hook(lambda g, bad=bad: torch.where(bad, torch.zeros_like(g), g))
     return loss / valid_cluster_ids.shape[0]
+
+
+# ---- the dense search and the two losses over it --------------------------------------------------------------------------------
+def _dense_args(queries, points, k_near, k_far, what="dense_topk"):
+    for t, name in ((queries, "queries"), (points, "points")):
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise ValueError(f"{what}: {name} must be a 2-D tensor")
+    if queries.shape[1] != points.shape[1] or not 1 <= points.shape[1] <= MAX_FEATURE_DIM:
+        raise ValueError(f"{what}: queries (M, D) and points (N, D) need one D with 1 <= D <= {MAX_FEATURE_DIM}")
+    if queries.dtype != torch.float32 or points.dtype != torch.float32:
+        raise ValueError(f"{what}: queries and points must be float32")
+    k_near, k_far = int(k_near), int(k_far)
+    if not (0 <= k_near <= MAX_DENSE_K and 0 <= k_far <= MAX_DENSE_K) or k_near + k_far < 1:
+        raise ValueError(f"{what}: need 0 <= k_near, k_far <= {MAX_DENSE_K} and one of them positive (got {k_near}, {k_far})")
+    if max(k_near, k_far) > points.shape[0]:
+        raise ValueError(f"{what}: k = {max(k_near, k_far)} is larger than the {points.shape[0]} points")
+    if queries.shape[0] >= 2 ** 31 or points.shape[0] >= 2 ** 31:
+        raise ValueError(f"{what}: need M, N < 2^31")
+    if queries.device != points.device:
+        raise ValueError(f"{what}: queries and points must be on one device")
+    return k_near, k_far
+
+
+def dense_topk_splits(M, N, D, k_near=0, k_far=0):
+    """The number of column ranges S the search of these sizes runs with (S > 1: a merge launch follows the sweep)."""
+    nbytes, splits = C.c_size_t(), C.c_int32()
+    _lib.check(_lib.load().trase_dense_topk_ws_bytes(M, N, D, k_near, k_far, C.byref(nbytes), C.byref(splits)), "trase_dense_topk_ws_bytes")
+    return splits.value
+
+
+def dense_topk(queries, points, k_near=0, k_far=0):
+    """For every row of ``queries`` (M, D) the k_near nearest and the k_far farthest rows of ``points`` (N, D), exactly, without the
+    M x N matrix -> (near_d2 (M, k_near) fp32, near_idx (M, k_near) int64, far_d2 (M, k_far), far_idx (M, k_far)).  Squared
+    distances are the chain s = fmaf(q_d - p_d, q_d - p_d, s) in dimension order.  Near end: smaller distance first, then lower
+    id; far end: larger distance first, then lower id; a NaN distance ranks above +inf (last near, first far).  k > N raises
+    ValueError.  Not differentiable."""
+    k_near, k_far = _dense_args(queries, points, k_near, k_far)
+    _need_gpu(queries, "dense_topk")
+    dev = queries.device
+    M, D = queries.shape
+    N = points.shape[0]
+    near_d2, far_d2 = torch.empty(M, k_near, device=dev), torch.empty(M, k_far, device=dev)
+    near_idx = torch.empty(M, k_near, dtype=torch.int64, device=dev)
+    far_idx = torch.empty(M, k_far, dtype=torch.int64, device=dev)
+    if M == 0:
+        return near_d2, near_idx, far_d2, far_idx
+    q, p = queries.detach().contiguous(), points.detach().contiguous()
+    lib = _lib.load()
+    nbytes = C.c_size_t()
+    _lib.check(lib.trase_dense_topk_ws_bytes(M, N, D, k_near, k_far, C.byref(nbytes), None), "trase_dense_topk_ws_bytes")
+    ws = _bytes(nbytes.value, dev)
+    _lib.check(lib.trase_dense_topk(_lib.ptr(q), M, _lib.ptr(p), N, D, k_near, k_far,
+                                    _lib.ptr(near_d2) if k_near else None, _lib.ptr(near_idx) if k_near else None,
+                                    _lib.ptr(far_d2) if k_far else None, _lib.ptr(far_idx) if k_far else None,
+                                    _lib.ptr(ws), nbytes.value, _dev_index(dev), _stream(dev)), "trase_dense_topk")
+    return near_d2, near_idx, far_d2, far_idx
+
+
+def _dpad(D):
+    return 8 if D <= 8 else 16 if D <= 16 else 32 if D <= 32 else 64
+
+
+class _Feature3D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feats, graph, kp, kn, lambda_p, lambda_n):
+        lib = _lib.load()
+        dev = feats.device
+        rows, D = feats.shape
+        f = _f32(feats)
+        u_tab, nrm = torch.empty(rows, _dpad(D), device=dev), torch.empty(rows, device=dev)
+        loss = torch.empty((), device=dev)
+        nbytes = C.c_size_t()
+        _lib.check(lib.trase_feature3d_ws_bytes(rows, C.byref(nbytes)), "trase_feature3d_ws_bytes")
+        ws = _bytes(nbytes.value, dev)
+        _lib.check(lib.trase_feature3d_forward(_lib.ptr(f), _lib.ptr(graph.idx), rows, D, kp, kn, lambda_p, lambda_n, _lib.ptr(u_tab),
+                                               _lib.ptr(nrm), _lib.ptr(loss), _lib.ptr(ws), ws.numel(), _dev_index(dev), _stream(dev)),
+                   "trase_feature3d_forward")
+        ctx.save_for_backward(u_tab, nrm, graph.idx, graph.rev_ranges, graph.rev_edges)
+        ctx.meta = (rows, D, kp, kn, lambda_p, lambda_n, feats.dtype)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        lib = _lib.load()
+        u_tab, nrm, idx, rev_ranges, rev_edges = ctx.saved_tensors
+        rows, D, kp, kn, lambda_p, lambda_n, dtype = ctx.meta
+        dev = u_tab.device
+        g = _f32(g_loss).reshape(1)
+        g_f = torch.empty(rows, D, device=dev)
+        _lib.check(lib.trase_feature3d_backward(_lib.ptr(u_tab), _lib.ptr(nrm), _lib.ptr(idx), _lib.ptr(rev_ranges), _lib.ptr(rev_edges),
+                                                rows, D, kp, kn, lambda_p, lambda_n, _lib.ptr(g), _lib.ptr(g_f), _dev_index(dev),
+                                                _stream(dev)), "trase_feature3d_backward")
+        return g_f.to(dtype), None, None, None, None, None
+
+
+def _k_ok(what, name, k):
+    if int(k) != k or not 1 <= int(k) <= MAX_DENSE_K:
+        raise ValueError(f"{what}: need 1 <= {name} <= {MAX_DENSE_K} (got {k})")
+    return int(k)
+
+
+def loss_feature3d(gaussian_feats, gaussian_xyz, kp=16, kn=4, max_points=10000, lambda_p=1.0, lambda_n=1.0, *, neighbors=None):
+    """utils/loss_utils.py:154-175: lambda_p * mean over (i, slot < kp) of sigmoid(1 - cos(f_i, f_j)), j the kp nearest rows of i in
+    xyz (the row itself included, as cdist + topk has it), plus lambda_n * mean over (i, slot < kn) of sigmoid(cos(f_i, f_j)), j
+    the kn farthest rows; cos(a, b) = (a / max(|a|, 1e-8)) . (b / max(|b|, 1e-8)).  The gradient goes to the features only.
+    max_points: an integer is the reference's rule (more rows than that: torch.randperm(N)[:max_points] on the CPU generator);
+    None uses every row -- the search never holds the N x N matrix.  neighbors: (near_idx (rows, kp), far_idx (rows, kn)) of the
+    rows actually used, to skip the search."""
+    what = "loss_feature3d"
+    if not torch.is_tensor(gaussian_feats) or gaussian_feats.dim() != 2 or not 1 <= gaussian_feats.shape[1] <= MAX_FEATURE_DIM:
+        raise ValueError(f"{what}: features must be (N, D) with 1 <= D <= {MAX_FEATURE_DIM}")
+    kp, kn = _k_ok(what, "kp", kp), _k_ok(what, "kn", kn)
+    if max_points is not None and (int(max_points) != max_points or max_points < 1):
+        raise ValueError(f"{what}: max_points must be a positive integer or None (got {max_points!r})")
+    if not torch.is_tensor(gaussian_xyz) or gaussian_xyz.dim() != 2 or gaussian_xyz.shape[0] != gaussian_feats.shape[0] \
+            or not 1 <= gaussian_xyz.shape[1] <= MAX_FEATURE_DIM:
+        raise ValueError(f"{what}: xyz must be (N, 1..{MAX_FEATURE_DIM}) with the features' N")
+    rows = gaussian_feats.shape[0] if max_points is None else min(gaussian_feats.shape[0], int(max_points))
+    if rows < 1 or rows >= 2 ** 25:
+        raise ValueError(f"{what}: need 1 <= rows < 2^25 (got {rows})")
+    if max(kp, kn) > rows:
+        raise ValueError(f"{what}: kp = {kp} / kn = {kn} is larger than the {rows} rows")
+    if neighbors is not None:
+        if len(neighbors) != 2 or tuple(neighbors[0].shape) != (rows, kp) or tuple(neighbors[1].shape) != (rows, kn):
+            raise ValueError(f"{what}: neighbors must be (near_idx ({rows}, {kp}), far_idx ({rows}, {kn}))")
+    _need_gpu(gaussian_feats, what)
+    if max_points is not None and gaussian_feats.size(0) > max_points:
+        indices = torch.randperm(gaussian_feats.size(0))[:max_points].to(gaussian_feats.device)
+        feats, xyz = gaussian_feats[indices], gaussian_xyz[indices]
+    else:
+        feats, xyz = gaussian_feats, gaussian_xyz
+    if neighbors is None:
+        x = _f32(xyz)
+        _, near_idx, _, far_idx = dense_topk(x, x, kp, kn)
+    else:
+        near_idx, far_idx = neighbors
+    graph = NeighborGraph.from_idx(torch.cat([near_idx.to(feats.device), far_idx.to(feats.device)], dim=1))
+    return _Feature3D.apply(feats, graph, kp, kn, float(lambda_p), float(lambda_n))
+
+
+class _Cls3D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, preds, sample, graph, sgraph, lambda_val):
+        lib = _lib.load()
+        dev = preds.device
+        N, Cn = preds.shape
+        S, k = graph.idx.shape
+        p = _f32(preds)
+        loss = torch.empty((), device=dev)
+        nbytes = C.c_size_t()
+        _lib.check(lib.trase_cls3d_ws_bytes(S, Cn, C.byref(nbytes)), "trase_cls3d_ws_bytes")
+        ws = _bytes(nbytes.value, dev)
+        _lib.check(lib.trase_cls3d_forward(_lib.ptr(p), _lib.ptr(sample), _lib.ptr(graph.idx), S, N, Cn, k, lambda_val, _lib.ptr(loss),
+                                           _lib.ptr(ws), ws.numel(), _dev_index(dev), _stream(dev)), "trase_cls3d_forward")
+        ctx.save_for_backward(p, sample, graph.idx, graph.rev_ranges, graph.rev_edges, sgraph.rev_ranges, sgraph.rev_edges)
+        ctx.meta = (S, N, Cn, k, lambda_val, preds.dtype)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        lib = _lib.load()
+        p, sample, idx, rev_ranges, rev_edges, srev_ranges, srev_edges = ctx.saved_tensors
+        S, N, Cn, k, lambda_val, dtype = ctx.meta
+        dev = p.device
+        g = _f32(g_loss).reshape(1)
+        g_p = torch.empty(N, Cn, device=dev)
+        _lib.check(lib.trase_cls3d_backward(_lib.ptr(p), _lib.ptr(sample), _lib.ptr(idx), _lib.ptr(rev_ranges), _lib.ptr(rev_edges),
+                                            _lib.ptr(srev_ranges), _lib.ptr(srev_edges), S, N, Cn, k, lambda_val, _lib.ptr(g),
+                                            _lib.ptr(g_p), _dev_index(dev), _stream(dev)), "trase_cls3d_backward")
+        return g_p.to(dtype), None, None, None, None
+
+
+def loss_cls_3d(features, predictions, k=5, lambda_val=2.0, max_points=200000, sample_size=800, *, sample=None):
+    """utils/loss_utils.py:89-130: lambda_val / (S k C) * sum over (s, slot, c) of p_s (log(p_s + 1e-10) - log(p_j + 1e-10)) over S
+    sampled rows s and their k nearest rows j in FEATURE space (the sampled row itself is slot 0).  More than max_points rows
+    are first cut down with torch.randperm(N)[:max_points], the sample is torch.randperm(N)[:sample_size], both on the CPU
+    generator as in the reference; ``sample`` (an index tensor into the rows left after max_points) replaces the second draw.
+    The gradient goes to ``predictions`` only."""
+    what = "loss_cls_3d"
+    if not torch.is_tensor(features) or features.dim() != 2 or not 1 <= features.shape[1] <= MAX_FEATURE_DIM:
+        raise ValueError(f"{what}: features must be (N, D) with 1 <= D <= {MAX_FEATURE_DIM}")
+    if not torch.is_tensor(predictions) or predictions.dim() != 2 or predictions.shape[0] != features.shape[0] \
+            or not 1 <= predictions.shape[1] <= MAX_CLASSES:
+        raise ValueError(f"{what}: predictions must be (N, C) with the features' N and 1 <= C <= {MAX_CLASSES}")
+    k = _k_ok(what, "k", k)
+    if int(max_points) != max_points or max_points < 1 or int(sample_size) != sample_size or sample_size < 1:
+        raise ValueError(f"{what}: max_points and sample_size must be positive integers")
+    N = min(features.shape[0], int(max_points))
+    if N < 1 or N * predictions.shape[1] >= 2 ** 31:
+        raise ValueError(f"{what}: need N >= 1 and N * C < 2^31 (got N {N}, C {predictions.shape[1]})")
+    if k > N:
+        raise ValueError(f"{what}: k = {k} is larger than the {N} rows")
+    if sample is not None:
+        if not torch.is_tensor(sample) or sample.dim() != 1 or sample.numel() < 1 or sample.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{what}: sample must be a non-empty 1-D int32 / int64 index tensor")
+    _need_gpu(features, what)
+    dev = features.device
+    if features.size(0) > max_points:
+        indices = torch.randperm(features.size(0))[:max_points].to(dev)
+        features, predictions = features[indices], predictions[indices]
+    if sample is None:
+        sample = torch.randperm(features.size(0))[:sample_size]
+    sample = sample.to(dev)
+    if int(sample.min()) < 0 or int(sample.max()) >= N:
+        raise ValueError(f"{what}: sample holds an index outside [0, {N})")
+    f = _f32(features)
+    _, idx, _, _ = dense_topk(f[sample.long()], f, k_near=k)
+    graph = NeighborGraph.from_idx(idx, num_targets=N)
+    sample32 = sample.to(torch.int32).contiguous()
+    sgraph = NeighborGraph.from_idx(sample32.reshape(-1, 1), num_targets=N)
+    return _Cls3D.apply(predictions, sample32, graph, sgraph, float(lambda_val))
