@@ -1160,6 +1160,54 @@ int trase_lpips_forward(const void* pack, size_t pack_bytes, const float* x, con
 int trase_lpips_head(const float* a, const float* b, const float* lin, int32_t C, int32_t hw, double* out_layer, float* map, void* ws,
                      size_t ws_bytes, int32_t device, trase_stream_t stream);
 
+/* ---- the rest of utils/loss_utils.py (style.hip): image-space losses and the style statistics ----------------------------------
+ * No float atomics: two calls give the same bits.  Inputs are never modified; nothing is allocated or synchronised.  Every
+ * refusal is TRASE_ERR_INVALID (a workspace that is too small: TRASE_ERR_WORKSPACE) with a message, before a device is touched.
+ * trase_pixel_loss_*: x (C,H,W) fp32; gt the same (gt_pitch == 0) or the planes of a byte frame (gt_pitch > 0: C = 3, read as
+ *   float32(b) / float32(255)); C * H * W < 2^31.  kind / aux:
+ *     TRASE_PIXEL_MASKED_L1    sum(|x - gt| * m) / (C * sum(m)), m (H,W) bytes (AUX_U8, the value of the byte) or fp32 (AUX_F32);
+ *                              an all-zero mask gives 0 and a zero gradient
+ *     TRASE_PIXEL_WEIGHTED_L1  mean(|x - gt| * w), w (H,W) fp32 (AUX_F32) or (C,H,W) fp32 (AUX_F32_FULL)
+ *     TRASE_PIXEL_L2           mean((x - gt)^2), no aux
+ *   Terms are formed in fp32, each operation rounded on its own, and summed in float64; out: 1 float.  The forward leaves the
+ *   denominator in ws; the backward reads it: d_x = sign(x - gt) * (m * s) resp. (2 s) * (x - gt), s = g[0] * float(1 / denominator).
+ * trase_style_ws_bytes: the one workspace of the four calls below for (C, n) features, 1 <= C <= 512, 1 <= n < 2^31.
+ * trase_gram_matrix: G (C,C) = x x^T on the fp32 MFMA: fp32 chains of 1024 columns, chain results added in float64 in order and
+ *   rounded once; G[i][j] and G[j][i] are the same bits.
+ * trase_mean_std: per channel the mean and the unbiased standard deviation + eps (added in fp32), two passes in float64; n >= 2.
+ * trase_style_node_forward: out4 = {total, gram, adain, content}, each term weighted, formed in float64:
+ *     gram    = gram_weight * mean((G - style_gram)^2) / (C * n)
+ *     adain   = adain_weight * (mean((mean - style_mean)^2) + mean((std - style_std)^2)), eps = 1e-8      (n >= 2)
+ *     content = content_weight * mean((x - content)^2)                                                     (C * n < 2^31)
+ *   A term whose weight is 0 is not computed and its targets may be NULL.  saved: C * C + 2 * C floats = D | a | b for
+ *   trase_style_grad_gemm, with c = float(2 * content_weight / (C * n)).
+ * trase_style_grad_gemm: dx[i][k] = g * (2 * sum_j D[i][j] x[j][k] + a[i] + b[i] * x[i][k] + c * (x[i][k] - y[i][k])), one launch.
+ *   D NULL: no product; a, b NULL (together): no AdaIN part; y NULL: no content part; g NULL: 1. */
+#define TRASE_PIXEL_MASKED_L1 0
+#define TRASE_PIXEL_WEIGHTED_L1 1
+#define TRASE_PIXEL_L2 2
+#define TRASE_PIXEL_AUX_NONE 0
+#define TRASE_PIXEL_AUX_U8 1
+#define TRASE_PIXEL_AUX_F32 2
+#define TRASE_PIXEL_AUX_F32_FULL 3
+int trase_pixel_loss_ws_bytes(size_t* ws_bytes);
+int trase_pixel_loss_forward(const float* x, const void* gt, int32_t gt_pitch, int32_t C, int32_t H, int32_t W, int32_t kind,
+                             const void* aux, int32_t aux_kind, float* out, void* ws, size_t ws_bytes, int32_t device,
+                             trase_stream_t stream);
+int trase_pixel_loss_backward(const float* x, const void* gt, int32_t gt_pitch, int32_t C, int32_t H, int32_t W, int32_t kind,
+                              const void* aux, int32_t aux_kind, const float* g, const void* ws, size_t ws_bytes, float* d_x,
+                              int32_t device, trase_stream_t stream);
+int trase_style_ws_bytes(int32_t C, int64_t n, size_t* ws_bytes);
+int trase_gram_matrix(const float* x, int32_t C, int64_t n, float* G, void* ws, size_t ws_bytes, int32_t device, trase_stream_t stream);
+int trase_mean_std(const float* x, int32_t C, int64_t n, float eps, float* mean, float* std_, void* ws, size_t ws_bytes, int32_t device,
+                   trase_stream_t stream);
+int trase_style_node_forward(const float* x, int32_t C, int64_t n, const float* style_gram, const float* style_mean,
+                             const float* style_std, const float* content, double gram_weight, double adain_weight,
+                             double content_weight, float* out4, float* saved, void* ws, size_t ws_bytes, int32_t device,
+                             trase_stream_t stream);
+int trase_style_grad_gemm(const float* D, const float* a, const float* b, float c, const float* x, const float* y, int32_t C, int64_t n,
+                          const float* g, float* dx, int32_t device, trase_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -343,6 +343,357 @@ def loss_nnfm_style(feat1: torch.Tensor, feats2: torch.Tensor) -> torch.Tensor:
 _NNFM_WARNED = False
 
 
+# ---- image-space losses and style statistics (utils/loss_utils.py:33-44, :230-272; csrc/style.hip) ---------------------------------
+PIXEL_MASKED_L1, PIXEL_WEIGHTED_L1, PIXEL_L2 = 0, 1, 2                       # include/trase_rast.h TRASE_PIXEL_*
+AUX_NONE, AUX_U8, AUX_F32, AUX_F32_FULL = 0, 1, 2, 3                         # TRASE_PIXEL_AUX_*
+STYLE_MAX_C = 512
+_CONST_WARNED = set()
+
+
+def _constant(t, who, what):
+    """A ground truth, mask, weight or style / content target takes no gradient: one that requires grad is detached, with one
+    warning per function (as loss_nnfm_style does for its style features)."""
+    if torch.is_tensor(t) and t.requires_grad:
+        if who not in _CONST_WARNED:
+            import warnings
+            warnings.warn(f"{who}: the {what} requires grad; no gradient is produced for it -- detaching")
+            _CONST_WARNED.add(who)
+        return t.detach()
+    return t
+
+
+def _dev_index(dev):
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+class _PixelLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gt, pitch, aux, aux_kind, kind, chw):
+        lib = _lib.load()
+        dev = x.device
+        xc = x.detach().float().contiguous()
+        y = gt if pitch else gt.detach().float().contiguous()
+        nbytes = C.c_size_t()
+        _lib.check(lib.trase_pixel_loss_ws_bytes(C.byref(nbytes)), "trase_pixel_loss_ws_bytes")
+        ws = _bytes(nbytes.value, dev)
+        out = torch.empty(1, device=dev)
+        _lib.check(lib.trase_pixel_loss_forward(_lib.ptr(xc), _lib.ptr(y), pitch, chw[0], chw[1], chw[2], kind, _lib.ptr(aux), aux_kind,
+                                                _lib.ptr(out), _lib.ptr(ws), ws.numel(), _dev_index(dev), _stream(dev)),
+                   "trase_pixel_loss_forward")
+        ctx.save_for_backward(xc, y, ws, *(() if aux is None else (aux,)))
+        ctx.args = (pitch, aux_kind, kind, chw)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        xc, y, ws, *rest = ctx.saved_tensors
+        aux = rest[0] if rest else None
+        pitch, aux_kind, kind, chw = ctx.args
+        dev = xc.device
+        g1 = g.detach().float().reshape(1).contiguous()
+        d_x = torch.empty_like(xc)
+        _lib.check(lib.trase_pixel_loss_backward(_lib.ptr(xc), _lib.ptr(y), pitch, chw[0], chw[1], chw[2], kind, _lib.ptr(aux), aux_kind,
+                                                 _lib.ptr(g1), _lib.ptr(ws), ws.numel(), _lib.ptr(d_x), _dev_index(dev), _stream(dev)),
+                   "trase_pixel_loss_backward")
+        return d_x, None, None, None, None, None, None
+
+
+_GPU_ONLY = "trase_amd.losses runs on the GPU only (there is no CPU path)"
+
+
+def _pixel_operands(who, network_output, gt):
+    """(what the kernels read as ground truth, its pitch: 0 = an fp32 tensor).  Shapes are checked before the device."""
+    if not torch.is_tensor(network_output) or network_output.dim() != 3 or not (torch.is_tensor(gt) or isinstance(gt, ByteFrame)) \
+            or tuple(network_output.shape) != tuple(gt.shape) or network_output.numel() < 1:
+        raise ValueError(f"{who}: expected two (C,H,W) images of equal shape, got "
+                         f"{tuple(network_output.shape) if torch.is_tensor(network_output) else type(network_output).__name__} and "
+                         f"{tuple(gt.shape) if hasattr(gt, 'shape') else type(gt).__name__}")
+    if network_output.numel() >= 2 ** 31:
+        raise ValueError(f"{who}: fewer than 2^31 elements are supported")
+    if network_output.device.type != "cuda":
+        raise RuntimeError(_GPU_ONLY)
+    if gt.device != network_output.device:
+        raise ValueError(f"{who}: the ground truth is on {gt.device}, the image on {network_output.device}")
+    if isinstance(gt, ByteFrame):
+        return gt.data, gt.pitch
+    return _constant(gt, who, "ground truth"), 0
+
+
+def masked_l1_loss(network_output: torch.Tensor, gt, mask: torch.Tensor) -> torch.Tensor:
+    """utils/loss_utils.py:33-37: ``sum(|x - gt| * m) / (C * sum(m))``, mask (H, W) bool, uint8 or float (the value of a uint8 mask
+    counts, as ``mask.float()`` does); gt a tensor or a ByteFrame.  An all-zero mask gives 0 with a zero gradient (the reference
+    divides 0 by 0)."""
+    if not torch.is_tensor(mask) or mask.dim() != 2 or not torch.is_tensor(network_output) or tuple(mask.shape) != tuple(network_output.shape[1:]):
+        raise ValueError(f"masked_l1_loss: expected an (H, W) mask for a {tuple(network_output.shape)} image, got "
+                         f"{tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__}")
+    if not (mask.dtype in (torch.bool, torch.uint8) or mask.dtype.is_floating_point):
+        raise TypeError(f"masked_l1_loss: the mask must be bool, uint8 or float (got {mask.dtype})")
+    y, pitch = _pixel_operands("masked_l1_loss", network_output, gt)
+    if mask.device != network_output.device:
+        raise ValueError(f"masked_l1_loss: the mask is on {mask.device}, the image on {network_output.device}")
+    mask = _constant(mask, "masked_l1_loss", "mask")
+    if mask.dtype == torch.bool:
+        aux, kind = mask.contiguous().view(torch.uint8), AUX_U8
+    elif mask.dtype == torch.uint8:
+        aux, kind = mask.contiguous(), AUX_U8
+    else:
+        aux, kind = mask.float().contiguous(), AUX_F32
+    return _PixelLoss.apply(network_output, y, pitch, aux, kind, PIXEL_MASKED_L1, tuple(network_output.shape))
+
+
+def weighted_l1_loss(network_output: torch.Tensor, gt, weight: torch.Tensor) -> torch.Tensor:
+    """utils/loss_utils.py:39-41: ``mean(|x - gt| * w)``, weight (H, W), (1, H, W) or (C, H, W)."""
+    if not torch.is_tensor(network_output) or network_output.dim() != 3:
+        raise ValueError("weighted_l1_loss: expected a (C,H,W) image")
+    c, h, w = network_output.shape
+    if not torch.is_tensor(weight) or tuple(weight.shape) not in ((h, w), (1, h, w), (c, h, w)):
+        raise ValueError(f"weighted_l1_loss: expected an (H, W), (1, H, W) or (C, H, W) weight for a {(c, h, w)} image, got "
+                         f"{tuple(weight.shape) if torch.is_tensor(weight) else type(weight).__name__}")
+    if not weight.dtype.is_floating_point:
+        raise TypeError(f"weighted_l1_loss: the weight must be float (got {weight.dtype})")
+    y, pitch = _pixel_operands("weighted_l1_loss", network_output, gt)
+    if weight.device != network_output.device:
+        raise ValueError(f"weighted_l1_loss: the weight is on {weight.device}, the image on {network_output.device}")
+    weight = _constant(weight, "weighted_l1_loss", "weight")
+    kind = AUX_F32_FULL if weight.dim() == 3 and weight.shape[0] == c and c > 1 else AUX_F32
+    return _PixelLoss.apply(network_output, y, pitch, weight.float().contiguous(), kind, PIXEL_WEIGHTED_L1, (c, h, w))
+
+
+def l2_loss(network_output: torch.Tensor, gt) -> torch.Tensor:
+    """utils/loss_utils.py:43-44: ``mean((x - gt)^2)`` of an image and its ground truth (a tensor or a ByteFrame), or of any two
+    fp32 tensors of equal shape (fewer than 2^31 elements)."""
+    if isinstance(gt, ByteFrame):
+        y, pitch = _pixel_operands("l2_loss", network_output, gt)
+        return _PixelLoss.apply(network_output, y, pitch, None, AUX_NONE, PIXEL_L2, tuple(network_output.shape))
+    if not torch.is_tensor(network_output) or not torch.is_tensor(gt) or tuple(gt.shape) != tuple(network_output.shape) \
+            or network_output.numel() < 1:
+        raise ValueError(f"l2_loss: expected two non-empty tensors of equal shape, got "
+                         f"{tuple(network_output.shape) if torch.is_tensor(network_output) else type(network_output).__name__} and "
+                         f"{tuple(gt.shape) if torch.is_tensor(gt) else type(gt).__name__}")
+    if network_output.numel() >= 2 ** 31:
+        raise ValueError("l2_loss: fewer than 2^31 elements are supported")
+    if network_output.device.type != "cuda":
+        raise RuntimeError(_GPU_ONLY)
+    if gt.device != network_output.device:
+        raise ValueError(f"l2_loss: the second tensor is on {gt.device}, the first on {network_output.device}")
+    gt = _constant(gt, "l2_loss", "second tensor")
+    return _PixelLoss.apply(network_output, gt, 0, None, AUX_NONE, PIXEL_L2, (1, 1, network_output.numel()))
+
+
+def cal_mse_content_loss(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """utils/loss_utils.py:271-272: the l2 kernel on two feature tensors (bitwise the content term of style_statistics_loss)."""
+    return l2_loss(x, y)
+
+
+def _features_2d(t, who):
+    """(C, n) view of a (1, C, h, w) or (C, n) feature tensor"""
+    if not torch.is_tensor(t) or not ((t.dim() == 4 and t.shape[0] == 1) or t.dim() == 2):
+        raise ValueError(f"{who}: expected (1, C, h, w) or (C, n) features, got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    c = t.shape[1] if t.dim() == 4 else t.shape[0]
+    n = t.numel() // c if c else 0
+    if not 1 <= c <= STYLE_MAX_C or n < 1 or n >= 2 ** 31:
+        raise ValueError(f"{who}: need 1 <= C <= {STYLE_MAX_C} channels and 1 <= n < 2^31 positions, got {tuple(t.shape)}")
+    if t.device.type != "cuda":
+        raise RuntimeError(_GPU_ONLY)
+    return t.reshape(c, n) if t.dim() == 4 else t
+
+
+def _style_ws(c, n, dev):
+    nbytes = C.c_size_t()
+    _lib.check(_lib.load().trase_style_ws_bytes(c, n, C.byref(nbytes)), "trase_style_ws_bytes")
+    return _bytes(nbytes.value, dev)
+
+
+def _grad_gemm(D, a, b, cc, x, y, g):
+    """trase_style_grad_gemm: g * (2 D x + a + b * x + cc * (x - y)), every part optional"""
+    dev = x.device
+    dx = torch.empty_like(x)
+    g1 = None if g is None else g.detach().float().reshape(1).contiguous()
+    _lib.check(_lib.load().trase_style_grad_gemm(_lib.ptr(D), _lib.ptr(a), _lib.ptr(b), float(cc), _lib.ptr(x), _lib.ptr(y), x.shape[0],
+                                                 x.shape[1], _lib.ptr(g1), _lib.ptr(dx), _dev_index(dev), _stream(dev)),
+               "trase_style_grad_gemm")
+    return dx
+
+
+class _Gram(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f):
+        x = f.detach().float().contiguous()
+        dev = x.device
+        c, n = x.shape
+        ws = _style_ws(c, n, dev)
+        G = torch.empty(c, c, device=dev)
+        _lib.check(_lib.load().trase_gram_matrix(_lib.ptr(x), c, n, _lib.ptr(G), _lib.ptr(ws), ws.numel(), _dev_index(dev), _stream(dev)),
+                   "trase_gram_matrix")
+        ctx.save_for_backward(x)
+        return G
+
+    @staticmethod
+    def backward(ctx, gG):
+        (x,) = ctx.saved_tensors
+        D = (0.5 * (gG + gG.t())).float().contiguous()            # d / dx of <gG, x x^T> = (gG + gG^T) x = 2 D x
+        return _grad_gemm(D, None, None, 0.0, x, None, None)
+
+
+class _MeanStd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f, eps):
+        x = f.detach().float().contiguous()
+        dev = x.device
+        c, n = x.shape
+        ws = _style_ws(c, n, dev)
+        mean, std = torch.empty(c, device=dev), torch.empty(c, device=dev)
+        _lib.check(_lib.load().trase_mean_std(_lib.ptr(x), c, n, float(eps), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(ws), ws.numel(),
+                                              _dev_index(dev), _stream(dev)), "trase_mean_std")
+        ctx.save_for_backward(x, mean, std)
+        ctx.eps = float(eps)
+        return mean, std
+
+    @staticmethod
+    def backward(ctx, g_mean, g_std):
+        x, mean, std = ctx.saved_tensors
+        n = x.shape[1]
+        z = torch.zeros_like(mean)
+        g_mean = z if g_mean is None else g_mean.float()
+        g_std = z if g_std is None else g_std.float()
+        sd = std - ctx.eps
+        b = torch.where(sd > 0, g_std / ((n - 1) * sd), z)        # a channel of zero variance takes no gradient from the std
+        a = g_mean / n - b * mean
+        return _grad_gemm(None, a.contiguous(), b.contiguous(), 0.0, x, None, None), None
+
+
+def gram_matrix(tensor: torch.Tensor) -> torch.Tensor:
+    """utils/loss_utils.py:240-249: (1, C, h, w) or (C, n) features -> the (C, C) fp32 matrix ``X X^T`` on the exact-fp32 matrix
+    instruction: fp32 chains of 1024 positions, the chain results added in float64 in order and rounded once.  Symmetric bit for
+    bit; two calls give the same bits."""
+    return _Gram.apply(_features_2d(tensor, "gram_matrix"))
+
+
+def calc_mean_std(x: torch.Tensor, eps: float = 1e-8):
+    """utils/loss_utils.py:230-238: (mean, std), each (1, C, 1); std is the unbiased standard deviation with eps added in fp32.
+    Two passes in float64 (the sum, then the squared deviations from the float64 mean)."""
+    f = _features_2d(x, "calc_mean_std")
+    if f.shape[1] < 2:
+        raise ValueError("calc_mean_std: the unbiased standard deviation needs n >= 2 positions")
+    mean, std = _MeanStd.apply(f, eps)
+    return mean.reshape(1, -1, 1), std.reshape(1, -1, 1)
+
+
+class StyleTargets:
+    """What style_statistics_loss compares a feature map with: the style map's Gram matrix (C, C), channel means and standard
+    deviations (C,), and optionally a content map (C, n) of the rendered features' size.  Built once per style image."""
+
+    def __init__(self, gram=None, mean=None, std=None, content=None):
+        self.gram, self.mean, self.std, self.content = gram, mean, std, content
+
+    @staticmethod
+    def from_features(style_feats: torch.Tensor, content_feats: torch.Tensor = None) -> "StyleTargets":
+        with torch.no_grad():
+            f = _features_2d(style_feats, "StyleTargets.from_features").detach()
+            gram = gram_matrix(f)
+            mean = std = None
+            if f.shape[1] >= 2:
+                mean, std = (t.reshape(-1).contiguous() for t in calc_mean_std(f))
+            content = None
+            if content_feats is not None:
+                content = _features_2d(content_feats, "StyleTargets.from_features").detach().float().contiguous()
+        return StyleTargets(gram, mean, std, content)
+
+
+class _StyleNode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f, gram, mean, std, content, gw, aw, cw):
+        x = f.detach().float().contiguous()
+        dev = x.device
+        c, n = x.shape
+        ws = _style_ws(c, n, dev)
+        out4 = torch.empty(4, device=dev)
+        saved = torch.empty(c * c + 2 * c, device=dev)
+        _lib.check(_lib.load().trase_style_node_forward(_lib.ptr(x), c, n, _lib.ptr(gram), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(content),
+                                                        gw, aw, cw, _lib.ptr(out4), _lib.ptr(saved), _lib.ptr(ws), ws.numel(),
+                                                        _dev_index(dev), _stream(dev)), "trase_style_node_forward")
+        ctx.save_for_backward(x, saved, *(() if content is None else (content,)))
+        ctx.weights = (gw, aw, cw)
+        ctx.mark_non_differentiable(out4)
+        return out4[0], out4
+
+    @staticmethod
+    def backward(ctx, g, _g_parts):
+        x, saved, *rest = ctx.saved_tensors
+        gw, aw, cw = ctx.weights
+        c, n = x.shape
+        D = saved[:c * c] if gw != 0.0 else None
+        a = saved[c * c:c * c + c] if aw != 0.0 else None
+        b = saved[c * c + c:] if aw != 0.0 else None
+        y = rest[0] if cw != 0.0 else None
+        return _grad_gemm(D, a, b, 2.0 * cw / (float(c) * float(n)), x, y, g), None, None, None, None, None, None, None
+
+
+def style_statistics_loss(feats: torch.Tensor, targets: StyleTargets, *, gram_weight: float = 0.0, adain_weight: float = 0.0,
+                          content_weight: float = 0.0, with_parts: bool = False):
+    """``gram_weight * mean((G - G_s)^2) / (C h w) + adain_weight * (mse(mean, mean_s) + mse(std, std_s)) + content_weight *
+    mse(feats, content)`` of (1, C, h, w) or (C, n) features as ONE autograd node: a statistics pass, the Gram launches and one
+    reduction forward (no read-back), one GEMM-shaped launch backward.  A term whose weight is 0 costs nothing and needs no
+    target.  with_parts: also the detached weighted (gram, adain, content) terms.  A channel of zero variance takes no gradient
+    from the std term (the reference's torch.std gives 0 / 0 there)."""
+    if not isinstance(targets, StyleTargets):
+        raise TypeError("style_statistics_loss: targets must be a StyleTargets (StyleTargets.from_features(style_feats) makes one)")
+    gw, aw, cw = float(gram_weight), float(adain_weight), float(content_weight)
+    if gw == 0.0 and aw == 0.0 and cw == 0.0:
+        raise ValueError("style_statistics_loss: every weight is 0")
+    f = _features_2d(feats, "style_statistics_loss")
+    c, n = f.shape
+    gram = mean = std = content = None
+    if gw != 0.0:
+        if targets.gram is None or tuple(targets.gram.shape) != (c, c):
+            raise ValueError(f"style_statistics_loss: the Gram term needs a ({c}, {c}) style Gram matrix")
+        gram = _constant(targets.gram, "style_statistics_loss", "style target").float().contiguous()
+    if aw != 0.0:
+        if n < 2:
+            raise ValueError("style_statistics_loss: the AdaIN term needs n >= 2 positions")
+        if targets.mean is None or targets.std is None or targets.mean.numel() != c or targets.std.numel() != c:
+            raise ValueError(f"style_statistics_loss: the AdaIN term needs the style mean and std of {c} channels")
+        mean = _constant(targets.mean, "style_statistics_loss", "style target").float().reshape(-1).contiguous()
+        std = _constant(targets.std, "style_statistics_loss", "style target").float().reshape(-1).contiguous()
+    if cw != 0.0:
+        if targets.content is None or targets.content.numel() != c * n:
+            raise ValueError(f"style_statistics_loss: the content term needs a content map of the features' size ({c}, {n})")
+        if c * n >= 2 ** 31:
+            raise ValueError("style_statistics_loss: the content term supports fewer than 2^31 elements")
+        content = _constant(targets.content, "style_statistics_loss", "content target").float().reshape(c, n).contiguous()
+    for t in (gram, mean, std, content):
+        if t is not None and t.device != f.device:
+            raise ValueError(f"style_statistics_loss: a target is on {t.device}, the features on {f.device}")
+    loss, parts = _StyleNode.apply(f, gram, mean, std, content, gw, aw, cw)
+    return (loss, parts[1], parts[2], parts[3]) if with_parts else loss
+
+
+def cal_adain_style_loss(x: torch.Tensor, y) -> torch.Tensor:
+    """utils/loss_utils.py:251-262; y: the style features, or the ``(mean, std)`` pair of calc_mean_std computed once."""
+    if isinstance(y, (tuple, list)):
+        if len(y) != 2:
+            raise ValueError("cal_adain_style_loss: y is a feature tensor or a (mean, std) pair")
+        t = StyleTargets(mean=y[0], std=y[1])
+    else:
+        with torch.no_grad():
+            m, s = calc_mean_std(_constant(y, "cal_adain_style_loss", "style features"))
+        t = StyleTargets(mean=m, std=s)
+    return style_statistics_loss(x, t, adain_weight=1.0)
+
+
+def cal_style_loss(target: torch.Tensor, style: torch.Tensor, weight) -> torch.Tensor:
+    """utils/loss_utils.py:264-269: ``weight * mean((G_t - G_s)^2) / (C h w)`` with the target's dimensions; style: features of any
+    spatial size, or a (C, C) Gram matrix computed once."""
+    f = _features_2d(target, "cal_style_loss")
+    if torch.is_tensor(style) and style.dim() == 2 and tuple(style.shape) == (f.shape[0], f.shape[0]):
+        gram = style
+    else:
+        with torch.no_grad():
+            gram = gram_matrix(_constant(style, "cal_style_loss", "style features"))
+    return style_statistics_loss(target, StyleTargets(gram=gram), gram_weight=float(weight))
+
+
 # the two k-NN graph losses of utils/loss_utils.py (:132-152, :179-221) live in trase_amd/neighbors.py
 from .neighbors import loss_reg_3d_feature, loss_rigid_body_motion_reg_loss, polar_rotation, rigid_fit  # noqa: E402,F401
 # the two dense-search losses (:154-175, :89-130) and their search too
